@@ -10,9 +10,18 @@ rank encrypts its own shard (weak scaling) and the step ends with an RCCL
 all-gather of the ciphertext shards over xGMI, so every rank holds the whole
 vector (the reassembly step of SURVEY.md 8(e)).
 
-    python bench.py [--gpus N --steps K --warmup W --n ELEMENTS]
+    python bench.py [--gpus N --steps K --warmup W --n ELEMENTS] [--dump-outputs DIR] [--full]
+
+A plain run sets up the key, warms up, times the K steps and prints the result
+line. --full adds everything else to that line: the parity sample against the
+CPU port, the headline at the drop-in's window, the rates of the other
+operations and of the drop-in API (unless --no-ops) and the CPU baselines
+(unless --no-cpu-baseline). --dump-outputs DIR writes a fixed sample of the
+last timed step's ciphertexts to DIR; the plaintexts, the key and the
+obfuscation draws are seeded, so two builds can be compared file for file.
 """
 import argparse
+import hashlib
 import json
 import math
 import os
@@ -626,6 +635,30 @@ def cpu_baselines(bits, seconds):
     return rec
 
 
+DUMP_BYTES = 48 << 20  # per run, of float64 ciphertext words (the whole dump stays under 64 MB)
+
+
+def dump_outputs(path, ct, ex, rank, world):
+    """What the last timed step handed back for this rank's shard, as float64
+    .npy files under `path`: the ciphertexts' 32-bit words (exact in float64),
+    their exponents and the rows both were taken from - every row when the
+    shard fits DUMP_BYTES / world, else a fixed seeded sample of its rows in
+    ascending order. One rank's files are named ciphertexts, exponents and
+    sample_rows; with more ranks each name carries _rank<r>."""
+    import torch
+    os.makedirs(path, exist_ok=True)
+    rows, words = ct.shape
+    keep = max(1, DUMP_BYTES // world // (words * 8))
+    idx = np.arange(rows) if rows <= keep else np.sort(np.random.default_rng(20240)
+                                                       .choice(rows, keep, replace=False))
+    sel = torch.from_numpy(idx).to(ct.device)
+    tag = f"_rank{rank}" if world > 1 else ""
+    np.save(os.path.join(path, f"ciphertexts{tag}.npy"),
+            ct[sel].cpu().numpy().view(np.uint32).astype(np.float64))
+    np.save(os.path.join(path, f"exponents{tag}.npy"), ex[sel].cpu().numpy().astype(np.float64))
+    np.save(os.path.join(path, f"sample_rows{tag}.npy"), idx.astype(np.float64))
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -637,9 +670,15 @@ def main():
                     help="fixed-base window: w or ws (split, XHE_WIN_SPLIT); 0 = the uniform window with the fewest "
                          "table products whose tables leave 16 GiB of the GPU free (2048 bits: 23, 2 x 96.6 GB, 45 "
                          "products per prime)")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline also run and report the parity sample against the CPU port, the headline "
+                         "at the drop-in's window, the other operations' and the drop-in's rates and the CPU baselines")
+    ap.add_argument("--dump-outputs", metavar="DIR",
+                    help="write the last timed step's ciphertexts and exponents (a fixed seeded sample of the rows "
+                         "past 48 MB) as float64 DIR/<name>.npy")
     ap.add_argument("--cpu-seconds", type=float, default=12.0)
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-ops", action="store_true", help="skip the secondary-operation rates")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baselines")
+    ap.add_argument("--no-ops", action="store_true", help="with --full: skip the secondary-operation rates")
     ap.add_argument("--dist", action="store_true",
                     help="initialise the RCCL process group and gather through it even at --gpus 1 (the N-GPU "
                          "code path - init, async all-gather, barriers, max-over-ranks all-reduce - on one GPU)")
@@ -648,6 +687,8 @@ def main():
                          "the vector every step too (a one-GPU stand-in for the P-rank job's gather bytes and memory; "
                          "shard.GatherPipeline proxy_world)")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     env_world = os.environ.get("WORLD_SIZE")
     if env_world is None and args.gpus > 1:
@@ -692,7 +733,9 @@ def main():
     ex = torch.empty(N, dtype=torch.int32, device="cuda")
     st = torch.empty(N, dtype=torch.int32, device="cuda")
     rnd = torch.empty((N, dk.rand_words), dtype=torch.int32, device="cuda")
-    seed32 = os.urandom(32)
+    # a fixed ChaCha20 key per rank (the step number is the stream's counter):
+    # every run with the same arguments draws the same obfuscation exponents
+    seed32 = hashlib.sha256(b"bench.py obfuscation draws, rank %d" % rank).digest()
     stream = torch.cuda.current_stream().cuda_stream
 
     def encrypt_shard(i, ct):
@@ -703,33 +746,38 @@ def main():
 
     pipe = GatherPipeline(encrypt_shard, N, dk.n2w, world=world, rank=rank, device="cuda", collective=use_dist,
                           proxy_world=args.proxy_world or None)
-    last = 1_000_000 + max(args.warmup, 1) - 1  # the parity check below needs one finished step
+    # --full's parity sample needs one finished step
+    last = 1_000_000 + (max(args.warmup, 1) if args.full else args.warmup) - 1
     for i in range(1_000_000, last + 1):
         pipe.step(i)
     pipe.drain()
     torch.cuda.synchronize()
-    # parity check of this rank's output (not timed): 4,096 elements spread
-    # over the shard against the reference's encryption on the same draws -
-    # the oracle's encode (encoder.py:29-54) and the GMP port's DJN-CRT
-    # encryption (oracle/gmp_baseline.c, pinned to the golden ciphertexts);
-    # the pure-Python oracle on 4 of them when libgmp is not loadable
-    from oracle import bench_cpu
-    from oracle import paillier_oracle as O
-    okey = O.derive_private(p, q, h)
-    xs = x.cpu().numpy()
-    rnd_h = rnd.cpu().numpy().view(np.uint32)
-    idx = np.unique(np.concatenate([[0, 1, N // 2, N - 1], np.random.default_rng(7).integers(0, N, 4092)]))
-    ms = [O.encode_element(okey, float(xs[i]), 7)[0] for i in idx]
-    try:
-        want = bench_cpu.gmp_encrypt_batch(okey, nat.ints_to_words(ms, dk.nw), rnd_h[idx], threads=host_cores()[0])
-        want = dict(zip(idx.tolist(), nat.words_to_ints(want)))
-    except RuntimeError:
-        idx = idx[[0, 1, -2, -1]]
-        want = {int(i): O.encrypt_m(okey, O.encode_element(okey, float(xs[i]), 7)[0], nat.words_to_ints(rnd_h[i]))
-                for i in idx}
-    parity_n = len(idx)
-    parity_ok = shard_parity(pipe.shard(last), pipe.vector(last) if use_dist else None, rank, [int(i) for i in idx],
-                             want.__getitem__)
+    parity_ok = parity_n = None
+    if args.full:
+        # parity check of this rank's output (not timed): 4,096 elements spread
+        # over the shard against the reference's encryption on the same draws -
+        # the oracle's encode (encoder.py:29-54) and the GMP port's DJN-CRT
+        # encryption (oracle/gmp_baseline.c, pinned to the golden ciphertexts);
+        # the pure-Python oracle on 4 of them when libgmp is not loadable
+        from oracle import bench_cpu
+        from oracle import paillier_oracle as O
+        okey = O.derive_private(p, q, h)
+        xs = x.cpu().numpy()
+        rnd_h = rnd.cpu().numpy().view(np.uint32)
+        idx = np.unique(np.concatenate([[0, 1, N // 2, N - 1], np.random.default_rng(7).integers(0, N, 4092)]))
+        ms = [O.encode_element(okey, float(xs[i]), 7)[0] for i in idx]
+        try:
+            want = bench_cpu.gmp_encrypt_batch(okey, nat.ints_to_words(ms, dk.nw), rnd_h[idx],
+                                               threads=host_cores()[0])
+            want = dict(zip(idx.tolist(), nat.words_to_ints(want)))
+        except RuntimeError:
+            idx = idx[[0, 1, -2, -1]]
+            want = {int(i): O.encrypt_m(okey, O.encode_element(okey, float(xs[i]), 7)[0],
+                                        nat.words_to_ints(rnd_h[i]))
+                    for i in idx}
+        parity_n = len(idx)
+        parity_ok = shard_parity(pipe.shard(last), pipe.vector(last) if use_dist else None, rank,
+                                 [int(i) for i in idx], want.__getitem__)
 
     free_after = int(torch.cuda.mem_get_info(local)[0])
     L.xhe_profile(1)
@@ -759,11 +807,15 @@ def main():
         t = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
-        ok = torch.tensor([1 if parity_ok else 0], dtype=torch.int32, device="cuda")
-        dist.all_reduce(ok, op=dist.ReduceOp.MIN)
-        parity_ok = bool(ok.item())
+        if args.full:
+            ok = torch.tensor([1 if parity_ok else 0], dtype=torch.int32, device="cuda")
+            dist.all_reduce(ok, op=dist.ReduceOp.MIN)
+            parity_ok = bool(ok.item())
 
     value = world * N * args.steps / elapsed
+    if args.dump_outputs:
+        # before --full's legs below, which write into ct, ex and m again
+        dump_outputs(args.dump_outputs, ct, ex, rank, world)
     if rank == 0:
         w_elem, w_pow = algorithmic_macs_per_element(bits, args.win, dk.rand_bits)
         pow_avg_s = (tot.value / max(cnt.value, 1)) / 1e3
@@ -784,11 +836,12 @@ def main():
                          "traffic_source": traffic_src, "kernel": kname, "kernel_avg_ms": pow_avg_s * 1e3,
                          "alg_macs_per_element": w_pow,
                          "alg_table_bytes_per_launch": N * 2 * nat.win_layout(dk.rand_bits, args.win)[0] * TABLE_ROW_BYTES[bits]},
-            "parity_sample_ok": parity_ok,
-            "parity_sample_n": parity_n,
             "key_setup_s": t_key,
             "hbm_free_after_setup_bytes": free_after,
         }
+        if args.full:
+            rec["parity_sample_ok"] = parity_ok
+            rec["parity_sample_n"] = parity_n
         if pipe.proxy:
             rec["config"]["proxy_world"] = pipe.proxy
             rec["config"]["proxy_gather_bytes_per_step"] = (pipe.proxy - world) * N * dk.n2w * 4
@@ -803,10 +856,11 @@ def main():
             rec["roofline"].update({"pmc_clock_ghz": float(pmc["clock_ghz"]),
                                     "pmc_valu_busy_frac": pmc.get("valu_busy_frac")})
         rec["config"]["table_bytes"] = nat.table_bytes(bits, args.win)
-        if not args.no_ops and (args.win & 0xFF) != 16:
+        ops = args.full and not args.no_ops
+        if ops and (args.win & 0xFF) != 16:
             rec["headline_dropin_window"] = headline_at_window(nat, L, bits, (p, q, n, h), 16, x, m, ex, st, rnd, N,
                                                                stream, args.steps)
-        if not args.no_ops:
+        if ops:
             rec["ops"] = measure_ops(nat, L, dk, x, m, ex, ct, rnd, N, stream, (p, q, n, h))
             # the drop-in with its own context and window policy: the bench
             # key's tables (193 GB at window 23) are released first
@@ -818,7 +872,7 @@ def main():
             rec["ops"].update(measure_dropin(nat, dev, bits, xh, (p, q, n, h)))
             clock = float(pmc["clock_ghz"]) if pmc and pmc.get("clock_ghz") else None
             rec["ops"]["issued"] = issued_fractions(rec["ops"], bits, (p, q, n, h), args.win, N / pow_avg_s, clock)
-        if not args.no_cpu_baseline:
+        if args.full and not args.no_cpu_baseline:
             rec["cpu_baseline"] = cpu_baselines(bits, args.cpu_seconds)
         print(json.dumps(rec), flush=True)
     if use_dist:

@@ -115,7 +115,7 @@ def test_bench_dist_world1():
     """bench.py --gpus 1 --dist: init_process_group, async all-gather of every
     step, barriers and the max-over-ranks all-reduce of an N-rank run."""
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--dist", "--n", "8192", "--steps", "3",
-           "--warmup", "1", "--win", "12", "--no-ops", "--no-cpu-baseline"]
+           "--warmup", "1", "--win", "12", "--full", "--no-ops", "--no-cpu-baseline"]
     r = subprocess.run(cmd, capture_output=True, text=True, timeout=300, cwd=ROOT)
     assert r.returncode == 0, r.stdout[-2000:] + r.stderr[-3000:]
     rec = json.loads([ln for ln in r.stdout.splitlines() if ln.startswith("{")][-1])

@@ -28,7 +28,7 @@ for s in $STEPS; do
       cat "$OUT/smoke.log"
       ;;
     bench)
-      timeout -k 10 600 python -u bench.py ${BENCH_ARGS} > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 3; }
+      timeout -k 10 600 python -u bench.py --full ${BENCH_ARGS} > "$OUT/bench.json" 2> "$OUT/bench.err" || { tail -20 "$OUT/bench.err"; exit 3; }
       cat "$OUT/bench.json"
       ;;
     prof)
@@ -48,7 +48,7 @@ for s in $STEPS; do
     opstrace)
       # kernel trace of the bench incl. the secondary operations (ops)
       timeout -k 10 600 rocprofv3 --kernel-trace --stats -d "$OUT/ops_trace" -o ops --output-format csv -- \
-        python3 -u bench.py --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench_ops_prof.json" 2> "$OUT/ops_trace.err" \
+        python3 -u bench.py --full --steps 2 --warmup 1 --no-cpu-baseline > "$OUT/bench_ops_prof.json" 2> "$OUT/ops_trace.err" \
         || { tail -20 "$OUT/ops_trace.err"; exit 3; }
       ;;
     configs)
@@ -77,7 +77,7 @@ for s in $STEPS; do
       for r in 1 2; do
         for d in "" "--dist"; do
           f="$OUT/headline${d:+_dist}_$r.json"
-          timeout -k 10 300 python -u bench.py --steps 5 --warmup 2 --no-ops --no-cpu-baseline $d $BENCH_ARGS > "$f" \
+          timeout -k 10 300 python -u bench.py --full --steps 5 --warmup 2 --no-ops --no-cpu-baseline $d $BENCH_ARGS > "$f" \
             2> "$f.err" || { tail -5 "$f.err"; exit 3; }
           grep "^{" "$f" | cut -c1-300
         done
@@ -89,14 +89,14 @@ for s in $STEPS; do
       for r in 1 2; do
         for p in 0 8; do
           f="$OUT/proxy${p}_$r.json"
-          timeout -k 10 400 python -u bench.py --dist --proxy-world $p --steps 20 --warmup 2 --no-ops \
+          timeout -k 10 400 python -u bench.py --full --dist --proxy-world $p --steps 20 --warmup 2 --no-ops \
             --no-cpu-baseline $BENCH_ARGS > "$f" 2> "$f.err" || { tail -5 "$f.err"; exit 3; }
           grep "^{" "$f" | cut -c1-400
         done
       done
       ;;
     cfg4dist)
-      timeout -k 10 600 python -u bench.py --key-bits 3072 --n 500000 --gpus 1 --dist --steps 5 --warmup 2 --no-ops \
+      timeout -k 10 600 python -u bench.py --full --key-bits 3072 --n 500000 --gpus 1 --dist --steps 5 --warmup 2 --no-ops \
         --no-cpu-baseline > "$OUT/cfg4_bench_dist.json" 2> "$OUT/cfg4_bench_dist.err" \
         || { tail -20 "$OUT/cfg4_bench_dist.err"; exit 3; }
       cat "$OUT/cfg4_bench_dist.json"
