@@ -76,6 +76,34 @@ int xhe_decrypt(const xhe_key* key, const uint32_t* ct_dev, int64_t count, uint3
 int xhe_decode(const xhe_key* key, const uint32_t* m_dev, const int32_t* exp_dev, int64_t count, double* f64_dev,
                float* f32_dev, int32_t* status_dev, void* stream);
 
+/* SecureBoost / Pearson plaintext packing on the device. Geometry, for all
+ * four packed entry points: interval_bits (log2 of the reference's
+ * `interval`) a multiple of 32 in [64, 256], 0 <= precision <=
+ * interval_bits - 2, ncols / num >= 1 and ncols (num) * interval_bits <=
+ * bitlen(n) - 1; anything else is XHE_EINVAL and stays on the host.
+ *
+ * embed + the integer encode of Paillier.encrypt (algorithm/core/
+ * paillier_acceleration.py:21-32, encoder.py:48-54 at exponent 0; the callers
+ * are xgboost/decision_tree_label_trainer.py:111-119, core/tree_ray/
+ * xgb_actor.py:386-394, pearson/label_trainer.py:129-155): cols_dev holds
+ * ncols float64 columns of count values, column j contiguous;
+ * m = (sum_j int(cols[j][i] * 2^precision) * 2^(interval_bits * (ncols-1-j)))
+ * mod n, nw words per element. status 0, 1 = a non-finite input
+ * (OverflowError / ValueError in the reference), 4 = some scaled value
+ * reaches 2^(interval_bits - 1) and does not fit its slot (the caller packs
+ * on the host); m = 0 where status != 0. */
+int xhe_embed_f64(const xhe_key* key, const double* cols_dev, int ncols, int64_t count, int interval_bits,
+                  int precision, uint32_t* m_dev, int32_t* status_dev, void* stream);
+/* decode_single at exponent 0 + umbed (encoder.py:56-64,
+ * paillier_acceleration.py:35-59; decision_tree_label_trainer.py:249,280,
+ * pearson/label_trainer.py:147-155, pearson/trainer.py:168-183) of decrypted
+ * m: the num centred base-2^interval_bits digits of each signed value, each
+ * divided by 2^precision. f64_dev / f32_dev: num columns of count values,
+ * column j the reference's res[j] (most significant digit first); f32 is the
+ * reference's astype(np.float32) of f64. status 1 = decode OverflowError. */
+int xhe_umbed(const xhe_key* key, const uint32_t* m_dev, int64_t count, int num, int interval_bits, int precision,
+              double* f64_dev, float* f32_dev, int32_t* status_dev, void* stream);
+
 /* Ciphertext addition PaillierCiphertext._add_encrypted (paillier.py:106-123,
  * 79-86, 153-154): out = a' * b' mod n^2 where the operand with the larger
  * exponent is first raised to 2^(e - min(ea, eb)); eout = min(ea, eb).
@@ -167,6 +195,15 @@ int xhe_encrypt_words_host(const xhe_key* key, const uint32_t* m, int64_t count,
  * m_out (nullable) receives the encoded integers. */
 int xhe_decrypt_decode_host(const xhe_key* key, const uint32_t* ct, const int32_t* exps, int64_t count, double* f64,
                             float* f32, int32_t* status, uint32_t* m_out);
+/* The packed calls on host buffers: embed's columns (ncols x count float64,
+ * column j contiguous) -> encoded m words and status, for
+ * xhe_encrypt_words_host; and Paillier.decrypt(out_origin=True) + umbed
+ * (paillier.py:370-417, paillier_acceleration.py:35-59) of ciphertext words
+ * -> num x count f64 / f32 and a status per element. */
+int xhe_embed_f64_host(const xhe_key* key, const double* cols, int ncols, int64_t count, int interval_bits,
+                       int precision, uint32_t* m, int32_t* status);
+int xhe_decrypt_umbed_host(const xhe_key* key, const uint32_t* ct, int64_t count, int num, int interval_bits,
+                           int precision, double* f64, float* f32, int32_t* status);
 int xhe_encrypt_host(const xhe_key* key, const uint32_t* m, const uint32_t* rand, int64_t count, uint32_t* ct);
 int xhe_decrypt_host(const xhe_key* key, const uint32_t* ct, int64_t count, uint32_t* m);
 

@@ -246,6 +246,29 @@ def cfg5(steps, world=1, rank=0):
         ok &= all(np.float32(gs[b] / (1 << 64)) == g_sum[f * NB + b] and np.float32(hs[b] / (1 << 64)) == h_sum[f * NB + b]
                   for b in range(NB))
     rec.update({"decrypt_umbed_16384_bins_s": t_dec, "bins_bit_exact_4_features": bool(ok)})
+    # the same two label-side steps through the drop-in with the packing on the
+    # device (embed_packed -> Paillier.encrypt resident, decrypt_umbed), checked
+    # against the host results above
+    from xfl_amd.paillier import Paillier, PaillierArray, PaillierContext
+    from xfl_amd.paillier_acceleration import decrypt_umbed, embed_packed
+    ctx = PaillierContext().init(p, q, djn_h_pow_n=h)
+    enc = {}
+
+    def enc_dev():
+        enc["a"] = Paillier.encrypt(ctx, embed_packed([gr[lo:hi], he[lo:hi]]), precision=0)
+    t_enc_dev = _timed(enc_dev, steps)
+    m_back = Paillier.decrypt(ctx, enc["a"], out_origin=True)
+    ok_enc = enc["a"].is_resident and [int(v) for v in m_back] == [int(v) for v in packed]
+    bins_arr = PaillierArray.from_device(ctx, hist, np.zeros(F * NB, dtype=np.int32))
+    out = {}
+
+    def dec_dev():
+        out["gh"] = decrypt_umbed(ctx, bins_arr, 2)
+    t_dec_dev = _timed(dec_dev, steps)
+    ok_dec = all(np.array_equal(np.array(w, np.float32).view(np.uint32), d.view(np.uint32))
+                 for w, d in zip((g_sum, h_sum), out["gh"]))
+    rec.update({"embed_encrypt_device_s": t_enc_dev, "decrypt_umbed_device_s": t_dec_dev,
+                "device_packing_bit_exact": bool(ok_enc and ok_dec)})
     return rec
 
 

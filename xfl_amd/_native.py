@@ -42,6 +42,14 @@ SIGNATURES = {
     "xhe_encrypt": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp]),
     "xhe_decrypt": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp]),
     "xhe_decode": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
+    "xhe_embed_f64": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, _vp,
+                                     _vp]),
+    "xhe_umbed": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
+                                 _vp]),
+    "xhe_embed_f64_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp,
+                                          _vp]),
+    "xhe_decrypt_umbed_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                              _vp, _vp, _vp]),
     "xhe_mulmod": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
     "xhe_powmod": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _vp, _vp]),
     "xhe_invert": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp]),

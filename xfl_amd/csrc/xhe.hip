@@ -2737,6 +2737,131 @@ int xhe_decode(const xhe_key* key, const uint32_t* m_dev, const int32_t* exp_dev
   });
 }
 
+}  // extern "C"
+
+namespace {
+// The packing geometry the kernels handle: whole-word slots of 64..256 bits,
+// a precision that keeps every digit / 2^precision a normal double, and all
+// the slots below n's top bit (|x| < 2^(slots * bits - 1) < n / 2).
+bool pack_geometry_ok(const xhe_key* key, int slots, int interval_bits, int precision) {
+  return interval_bits >= 64 && interval_bits <= 256 && interval_bits % 32 == 0 && precision >= 0 &&
+         precision <= interval_bits - 2 && slots >= 1 && (int64_t)slots * interval_bits <= key->n_bits - 1;
+}
+
+void embed_launch(const xhe_key* key, const double* cols_dev, int64_t cstride, int ncols, int64_t count,
+                  int interval_bits, int precision, uint32_t* m_dev, int32_t* status_dev, hipStream_t s) {
+  int blocks = (int)((count * (key->nw / 4) + 255) / 256);  // one thread per 16-byte quad of m
+  hipLaunchKernelGGL(k_embed_f64, dim3(blocks), dim3(256), 0, s, cols_dev, cstride, ncols, count, interval_bits,
+                     precision, key->kd.n_words, key->nw, m_dev, status_dev);
+  HIPCHK(hipGetLastError());
+}
+
+void umbed_launch(const xhe_key* key, const uint32_t* m_dev, int64_t count, int num, int interval_bits, int precision,
+                  double* f64_dev, float* f32_dev, int64_t ostride, int32_t* status_dev, hipStream_t s) {
+  int blocks = (int)((count + 255) / 256);
+  hipLaunchKernelGGL(k_umbed, dim3(blocks), dim3(256), 0, s, m_dev, count, num, interval_bits, precision, key->kd,
+                     f64_dev, f32_dev, ostride, status_dev);
+  HIPCHK(hipGetLastError());
+}
+}  // namespace
+
+extern "C" {
+
+int xhe_embed_f64(const xhe_key* key, const double* cols_dev, int ncols, int64_t count, int interval_bits,
+                  int precision, uint32_t* m_dev, int32_t* status_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (!key || (count > 0 && (!cols_dev || !m_dev || !status_dev)))
+      return fail(XHE_EINVAL, "xhe_embed_f64: null argument");
+    if (!pack_geometry_ok(key, ncols, interval_bits, precision))
+      return fail(XHE_EINVAL, "xhe_embed_f64: unsupported packing geometry");
+    if (count <= 0) return XHE_OK;
+    DevGuard dg(key->device);
+    embed_launch(key, cols_dev, count, ncols, count, interval_bits, precision, m_dev, status_dev, (hipStream_t)stream);
+    return XHE_OK;
+  });
+}
+
+int xhe_umbed(const xhe_key* key, const uint32_t* m_dev, int64_t count, int num, int interval_bits, int precision,
+              double* f64_dev, float* f32_dev, int32_t* status_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (!key || (count > 0 && (!m_dev || !f64_dev || !f32_dev || !status_dev)))
+      return fail(XHE_EINVAL, "xhe_umbed: null argument");
+    if (!pack_geometry_ok(key, num, interval_bits, precision))
+      return fail(XHE_EINVAL, "xhe_umbed: unsupported packing geometry");
+    if (count <= 0) return XHE_OK;
+    DevGuard dg(key->device);
+    umbed_launch(key, m_dev, count, num, interval_bits, precision, f64_dev, f32_dev, count, status_dev,
+                 (hipStream_t)stream);
+    return XHE_OK;
+  });
+}
+
+// The packed host calls go chunk by chunk on one stream (columns are
+// contiguous per column, not per element, so they do not fit host_pipeline's
+// per-element parts): the columns of a chunk sit side by side in one device
+// buffer whose column stride is the chunk size.
+int xhe_embed_f64_host(const xhe_key* key, const double* cols, int ncols, int64_t count, int interval_bits,
+                       int precision, uint32_t* m, int32_t* status) {
+  return guarded([&]() -> int {
+    if (!key || (count > 0 && (!cols || !m || !status))) return fail(XHE_EINVAL, "xhe_embed_f64_host: null argument");
+    if (!pack_geometry_ok(key, ncols, interval_bits, precision))
+      return fail(XHE_EINVAL, "xhe_embed_f64_host: unsupported packing geometry");
+    if (count <= 0) return XHE_OK;
+    DevGuard dg(key->device);
+    Stream st;
+    const int64_t chunk = std::min<int64_t>(host_chunk(1 << 18), count);
+    const size_t mb = (size_t)key->nw * 4;
+    DevBuf dc((size_t)ncols * chunk * 8, st.s), dm((size_t)chunk * mb, st.s), ds((size_t)chunk * 4, st.s);
+    for (int64_t off = 0; off < count; off += chunk) {
+      const int64_t n = std::min(chunk, count - off);
+      for (int j = 0; j < ncols; ++j)
+        HIPCHK(hipMemcpyAsync(dc.as<double>() + (size_t)j * chunk, cols + (size_t)j * count + off, (size_t)n * 8,
+                              hipMemcpyHostToDevice, st.s));
+      embed_launch(key, dc.as<double>(), chunk, ncols, n, interval_bits, precision, dm.as<uint32_t>(),
+                   ds.as<int32_t>(), st.s);
+      HIPCHK(hipMemcpyAsync(m + (size_t)off * key->nw, dm.p, (size_t)n * mb, hipMemcpyDeviceToHost, st.s));
+      HIPCHK(hipMemcpyAsync(status + off, ds.p, (size_t)n * 4, hipMemcpyDeviceToHost, st.s));
+      HIPCHK(hipStreamSynchronize(st.s));
+    }
+    return XHE_OK;
+  });
+}
+
+int xhe_decrypt_umbed_host(const xhe_key* key, const uint32_t* ct, int64_t count, int num, int interval_bits,
+                           int precision, double* f64, float* f32, int32_t* status) {
+  return guarded([&]() -> int {
+    if (!key || (count > 0 && (!ct || !f64 || !f32 || !status)))
+      return fail(XHE_EINVAL, "xhe_decrypt_umbed_host: null argument");
+    if (!key->priv) return fail(XHE_EINVAL, "Try to decrypt a paillier ciphertext by a public key.");
+    if (!pack_geometry_ok(key, num, interval_bits, precision))
+      return fail(XHE_EINVAL, "xhe_decrypt_umbed_host: unsupported packing geometry");
+    if (count <= 0) return XHE_OK;
+    DevGuard dg(key->device);
+    Stream st;
+    const int64_t chunk = std::min<int64_t>(host_chunk(1 << 17), count);
+    const size_t cb = (size_t)key->n2w * 4;
+    DevBuf dct((size_t)chunk * cb, st.s), dm((size_t)chunk * key->nw * 4, st.s), d64((size_t)num * chunk * 8, st.s),
+        d32((size_t)num * chunk * 4, st.s), ds((size_t)chunk * 4, st.s);
+    for (int64_t off = 0; off < count; off += chunk) {
+      const int64_t n = std::min(chunk, count - off);
+      HIPCHK(hipMemcpyAsync(dct.p, ct + (size_t)off * key->n2w, (size_t)n * cb, hipMemcpyHostToDevice, st.s));
+      int rc = xhe_decrypt(key, dct.as<uint32_t>(), n, dm.as<uint32_t>(), st.s);
+      if (rc != XHE_OK) return rc;
+      umbed_launch(key, dm.as<uint32_t>(), n, num, interval_bits, precision, d64.as<double>(), d32.as<float>(), chunk,
+                   ds.as<int32_t>(), st.s);
+      for (int j = 0; j < num; ++j) {
+        HIPCHK(hipMemcpyAsync(f64 + (size_t)j * count + off, d64.as<double>() + (size_t)j * chunk, (size_t)n * 8,
+                              hipMemcpyDeviceToHost, st.s));
+        HIPCHK(hipMemcpyAsync(f32 + (size_t)j * count + off, d32.as<float>() + (size_t)j * chunk, (size_t)n * 4,
+                              hipMemcpyDeviceToHost, st.s));
+      }
+      HIPCHK(hipMemcpyAsync(status + off, ds.p, (size_t)n * 4, hipMemcpyDeviceToHost, st.s));
+      HIPCHK(hipStreamSynchronize(st.s));
+    }
+    return XHE_OK;
+  });
+}
+
 int xhe_encrypt_host(const xhe_key* key, const uint32_t* m, const uint32_t* rand, int64_t count, uint32_t* ct) {
   return guarded([&]() -> int {
     if (!key || (count > 0 && (!m || !ct))) return fail(XHE_EINVAL, "xhe_encrypt_host: null argument");

@@ -243,6 +243,103 @@ __global__ void k_encode_f64(const double* __restrict__ x, int64_t count, int mo
   }
 }
 
+// ============================================================== embed
+enum : int32_t { ST_SLOT = 4 };  // a packed value does not fit its slot
+
+// t = trunc_toward_zero(v * 2^p) for one column value of embed
+// (paillier_acceleration.py:21-32), exactly from the double's mantissa and
+// exponent: |t| as three words at word offset w (EncVal; neg is clear for
+// t == 0). st: ST_OVERFLOW for a non-finite v, ST_SLOT when |t| >= 2^(ib - 1).
+XHE_DEV EncVal embed_value(double v, int ib, int p) {
+  EncVal r{ST_OK, 0, 0, 0, 0u, 0u, 0u};
+  const uint64_t bits = __double_as_longlong(v);
+  const int bexp = (int)((bits >> 52) & 0x7FF);
+  const uint64_t frac = bits & ((1ull << 52) - 1);
+  if (bexp == 0x7FF) { r.st = ST_OVERFLOW; return r; }
+  uint64_t M;
+  int E;
+  if (bexp == 0) { M = frac; E = -1074; } else { M = frac | (1ull << 52); E = bexp - 1075; }
+  if (M == 0) return r;
+  const int sh = E + p;  // |t| = floor(M * 2^sh)
+  if (sh >= 0) {
+    if (64 - __clzll(M) + sh >= ib) { r.st = ST_SLOT; return r; }  // ib <= 256: sh < 256 from here
+    const int b = sh & 31;
+    const uint64_t lo = M << b;
+    r.w = sh >> 5;
+    r.v0 = (uint32_t)lo;
+    r.v1 = (uint32_t)(lo >> 32);
+    r.v2 = b ? (uint32_t)(M >> (64 - b)) : 0u;
+  } else {
+    const uint64_t q = -sh >= 64 ? 0ull : M >> -sh;  // < 2^53 <= 2^(ib - 1)
+    r.v0 = (uint32_t)q;
+    r.v1 = (uint32_t)(q >> 32);
+  }
+  r.neg = (r.v0 | r.v1 | r.v2) != 0u ? (int)(bits >> 63) : 0;
+  return r;
+}
+
+// ncols float64 columns (column j at cols + j * cstride) -> m = x mod n,
+// x = sum_j t_j * 2^(ib * (ncols - 1 - j)) (embed followed by encode_single
+// at exponent 0, encoder.py:48-54). k_encode_f64's layout: one thread per
+// 16-byte quad of m. ib is a multiple of 32 and every |t_j| < 2^(ib - 1), so
+// the slots are whole words and do not overlap: word w of x's positive and
+// negative parts comes from the one column whose slot holds w, and
+// m = (x < 0 ? n : 0) + x is one chain with a signed carry from word 0 up.
+// x has the sign of its most significant nonzero t_j. Above the slots only
+// n's words carry on. status: 0, ST_OVERFLOW (a non-finite input), ST_SLOT;
+// m = 0 unless 0.
+__global__ void k_embed_f64(const double* __restrict__ cols, int64_t cstride, int ncols, int64_t count, int ib,
+                            int p, const uint32_t* __restrict__ n_words, int nw, uint32_t* __restrict__ m_out,
+                            int32_t* __restrict__ status) {
+  const int nq = nw >> 2;
+  const int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  const int64_t i = t / nq;
+  if (i >= count) return;
+  const int q = (int)(t - i * nq);
+  int32_t st = ST_OK;
+  int sgn = 0;
+  for (int j = 0; j < ncols; ++j) {
+    const EncVal y = embed_value(cols[(size_t)j * cstride + i], ib, p);
+    if (y.st == ST_OVERFLOW) st = ST_OVERFLOW;
+    else if (y.st == ST_SLOT && st == ST_OK) st = ST_SLOT;
+    if (sgn == 0 && (y.v0 | y.v1 | y.v2) != 0u) sgn = y.neg ? -1 : 1;
+  }
+  if (q == 0) status[i] = st;
+  uint32_t o[4] = {0u, 0u, 0u, 0u};
+  if (st == ST_OK && sgn != 0) {
+    const int iw = ib >> 5, wend = 4 * q + 4;
+    int64_t c = 0;  // the chain's carry: -1, 0 or 1
+    int w = 0;
+    auto step = [&](int64_t xw) {
+      const int64_t acc = c + (sgn < 0 ? (int64_t)n_words[w] : 0) + xw;
+      const int kk = w - 4 * q;
+#pragma unroll
+      for (int u = 0; u < 4; ++u)
+        if (u == kk) o[u] = (uint32_t)acc;
+      c = acc >> 32;
+      ++w;
+    };
+    for (int sl = 0; sl < ncols && w < wend; ++sl) {
+      const EncVal y = embed_value(cols[(size_t)(ncols - 1 - sl) * cstride + i], ib, p);
+      for (int d = 0; d < iw && w < wend; ++d) {
+        const int64_t yw = (int64_t)enc_word(y, d);
+        step(y.neg ? -yw : yw);
+      }
+    }
+    while (w < wend) {
+      if (c == 0 && w < 4 * q) w = 4 * q;  // nothing carries into this quad
+      step(0);
+    }
+  }
+  uint32_t* dst = m_out + (size_t)i * nw + 4 * q;
+  if ((reinterpret_cast<uintptr_t>(m_out) & 15u) == 0u) {
+    *reinterpret_cast<uint4*>(dst) = make_uint4(o[0], o[1], o[2], o[3]);
+  } else {  // a caller's buffer that is not 16-byte aligned
+#pragma unroll
+    for (int k = 0; k < 4; ++k) dst[k] = o[k];
+  }
+}
+
 // ============================================================== ChaCha20
 XHE_DEV uint32_t rotl32(uint32_t x, int r) { return (x << r) | (x >> (32 - r)); }
 #define XHE_QR(a, b, c, d) \
@@ -2645,6 +2742,61 @@ __global__ void k_mont_rows(ModDev md, const uint32_t* x, const uint32_t* y, uin
 }
 
 // ============================================================== decode
+// A magnitude read word by word from the bottom, kept as the four words ending
+// at its highest nonzero one (w4[3] = word hk) and the OR of every word below
+// them (the rounding's sticky part).
+XHE_DEV void magwin_push(uint32_t w4[4], uint32_t& low_or, int& hk, uint32_t w, int k) {
+  if (!w) return;
+  const int g = k - hk;  // >= 1: words hk+1 .. k-1 are zero
+#pragma unroll
+  for (int t = 0; t < 4; ++t)
+    if (t < g) low_or |= w4[t];  // leaves the window
+  uint32_t nw4[4];
+#pragma unroll
+  for (int t = 0; t < 4; ++t) nw4[t] = t == 3 ? w : (t + g <= 3 ? w4[t + g] : 0u);
+#pragma unroll
+  for (int t = 0; t < 4; ++t) w4[t] = nw4[t];
+  hk = k;
+}
+
+// |v| of bl > 0 bits in such a window -> (mant, shift), |v| ~ mant * 2^shift:
+// exact up to 53 bits, else the top 53 bits rounded to nearest even (rne) or
+// truncated.
+XHE_DEV void magwin_round53(const uint32_t w4[4], uint32_t low_or, int hk, int bl, bool rne, uint64_t& mant,
+                            int& shift) {
+  auto magw = [&](int k) -> uint32_t {  // word k of |v| for k >= hk - 3
+    const int t = 3 - (hk - k);
+    return (k > hk || t < 0) ? 0u : w4[t];
+  };
+  if (bl <= 53) {
+    mant = (uint64_t)magw(0) | ((uint64_t)magw(1) << 32);
+    shift = 0;
+    return;
+  }
+  int s = bl - 53;
+  // extract 53 bits starting at bit s, plus round/sticky (all inside the
+  // window: s - 1 >= 32 hk - 53)
+  auto bitsat = [&](int pos) -> uint64_t {  // 64 bits starting at pos
+    int k = pos >> 5, o = pos & 31;
+    uint64_t w0 = magw(k), w1 = magw(k + 1), w2 = magw(k + 2);
+    uint64_t lo = (w0 | (w1 << 32)) >> o;
+    if (o) lo |= w2 << (64 - o);
+    return lo;
+  };
+  mant = bitsat(s) & ((1ull << 53) - 1);
+  uint64_t rbit = (bitsat(s - 1) & 1ull);
+  bool sticky = low_or != 0;
+  for (int k = hk - 3; k < ((s - 1) >> 5); ++k)
+    if (k >= 0) sticky |= magw(k) != 0;
+  int sb = (s - 1) & 31;
+  if (sb) sticky |= (magw((s - 1) >> 5) & ((1u << sb) - 1u)) != 0;
+  shift = s;
+  if (rne && rbit && (sticky || (mant & 1))) {
+    mant += 1;
+    if (mant >> 53) { mant >>= 1; shift += 1; }
+  }
+}
+
 // m (nw words) and exponent -> float64 as Paillier.decrypt would hand it to
 // astype(np.float32): e < 0: RNE53(v * 2^e) with 2^e a double (0 below
 // 2^-1074), subnormals rounded again, overflow to inf (encoder.py:63);
@@ -2684,62 +2836,20 @@ __global__ void k_decode(const uint32_t* __restrict__ m_words, const int32_t* __
     } else {
       w = m[k];
     }
-    if (w) {
-      const int g = k - hk;  // >= 1: words hk+1 .. k-1 are zero
-#pragma unroll
-      for (int t = 0; t < 4; ++t)
-        if (t < g) low_or |= w4[t];  // leaves the window
-      uint32_t nw4[4];
-#pragma unroll
-      for (int t = 0; t < 4; ++t) nw4[t] = t == 3 ? w : (t + g <= 3 ? w4[t + g] : 0u);
-#pragma unroll
-      for (int t = 0; t < 4; ++t) w4[t] = nw4[t];
-      hk = k;
-    }
+    magwin_push(w4, low_or, hk, w, k);
   }
   const int bl = hk < 0 ? 0 : 32 * hk + 32 - __clz(w4[3]);
-  auto magw = [&](int k) -> uint32_t {  // word k of |v| for k >= hk - 3
-    const int t = 3 - (hk - k);
-    return (k > hk || t < 0) ? 0u : w4[t];
-  };
   double res;
   if (st != 0) { res = 0.0; }
   else if (bl == 0) {
     res = 0.0;
     if (e < -1074 && neg) res = -0.0;  // never: v == 0 is not negative
   } else {
-    // q = RNE53(|v|) as (mant, shift): |v| ~ mant * 2^shift
+    // q = RNE53(|v|) as (mant, shift): |v| ~ mant * 2^shift; for e >= 0
+    // gmpy2's mpz->float truncates instead
     uint64_t mant;
     int shift;
-    if (bl <= 53) {
-      mant = (uint64_t)magw(0) | ((uint64_t)(nw > 1 ? magw(1) : 0) << 32);
-      shift = 0;
-    } else {
-      int s = bl - 53;
-      // extract 53 bits starting at bit s, plus round/sticky (all inside the
-      // window: s - 1 >= 32 hk - 53)
-      auto bitsat = [&](int pos) -> uint64_t {  // 64 bits starting at pos
-        int k = pos >> 5, o = pos & 31;
-        uint64_t w0 = magw(k), w1 = magw(k + 1), w2 = magw(k + 2);
-        uint64_t lo = (w0 | (w1 << 32)) >> o;
-        if (o) lo |= w2 << (64 - o);
-        return lo;
-      };
-      mant = bitsat(s) & ((1ull << 53) - 1);
-      uint64_t rbit = (bitsat(s - 1) & 1ull);
-      bool sticky = low_or != 0;
-      for (int k = hk - 3; k < ((s - 1) >> 5); ++k)
-        if (k >= 0) sticky |= magw(k) != 0;
-      int sb = (s - 1) & 31;
-      if (sb) sticky |= (magw((s - 1) >> 5) & ((1u << sb) - 1u)) != 0;
-      shift = s;
-      if (e >= 0) {
-        // gmpy2 mpz->float truncates: keep mant, no rounding
-      } else if (rbit && (sticky || (mant & 1))) {
-        mant += 1;
-        if (mant >> 53) { mant >>= 1; shift += 1; }
-      }
-    }
+    magwin_round53(w4, low_or, hk, bl, e < 0, mant, shift);
     if (e >= 0) {
       int top = bl + e;
       if (top > 1024) { st = 3; res = 0.0; }
@@ -2769,6 +2879,92 @@ __global__ void k_decode(const uint32_t* __restrict__ m_words, const int32_t* __
   out_f64[i] = res;
   out_f32[i] = (float)res;
   status[i] = st;
+}
+
+// ============================================================== umbed
+// Decrypted m (nw words) -> the `num` centred base-2^ib digits of the signed
+// value (decode_single's sign rule at exponent 0, then umbed,
+// paillier_acceleration.py:35-59), each as f64 = d / 2^p (RNE53(d) scaled
+// exactly: p <= ib - 2 keeps it a normal double) and f32 = (float)f64, the
+// reference's astype(np.float32). One thread per element; column j of the
+// outputs (at j * ostride) is the reference's res[j], most significant digit
+// first. The digits come from the two's complement words of the value, least
+// significant slot first: field + carry, where a digit above 2^(ib - 1)
+// becomes digit - 2^ib and carries one into the next slot; what remains above
+// the last slot is dropped, as in the reference. status 1: max_pos < m <
+// min_neg (outputs 0).
+__global__ void k_umbed(const uint32_t* __restrict__ m_words, int64_t count, int num, int ib, int p, KeyDev key,
+                        double* __restrict__ out_f64, float* __restrict__ out_f32, int64_t ostride,
+                        int32_t* __restrict__ status) {
+  int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= count) return;
+  const int nw = key.nw, iw = ib >> 5;
+  const uint32_t* m = m_words + (size_t)i * nw;
+  auto cmpw = [&](const uint32_t* a, const uint32_t* b) {
+    for (int k = nw - 1; k >= 0; --k) if (a[k] != b[k]) return a[k] < b[k] ? -1 : 1;
+    return 0;
+  };
+  const int neg = cmpw(m, key.minneg) >= 0;
+  const int32_t st = (!neg && cmpw(m, key.maxpos) > 0) ? 1 : 0;
+  status[i] = st;
+  uint32_t br = 0u, cy = 0u;  // borrow of m - n, carry between digits
+  for (int sl = 0; sl < num; ++sl) {
+    // the slot's field plus the carry, as a magnitude and a sign
+    uint32_t f[8];
+    uint32_t any_low = 0u;  // OR of the words below the top one
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+      f[d] = 0u;
+      if (d < iw) {
+        const int k = sl * iw + d;
+        uint32_t w = m[k];
+        if (neg) {
+          const uint64_t x = (uint64_t)w - (uint64_t)key.n_words[k] - br;
+          w = (uint32_t)x;
+          br = (uint32_t)(x >> 63);
+        }
+        const uint64_t s = (uint64_t)w + cy;
+        f[d] = (uint32_t)s;
+        cy = (uint32_t)(s >> 32);
+      }
+    }
+    uint32_t top = 0u;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+      if (d == iw - 1) top = f[d];
+      else if (d < iw) any_low |= f[d];
+    }
+    // cy set: field + carry = 2^ib, digit 0 and the carry goes on
+    const bool dneg = !cy && (top > 0x80000000u || (top == 0x80000000u && any_low));
+    if (dneg) cy = 1u;
+    uint32_t w4[4] = {0u, 0u, 0u, 0u};
+    uint32_t low_or = 0u, nb = 0u;
+    int hk = -1;
+#pragma unroll
+    for (int d = 0; d < 8; ++d) {
+      if (d < iw) {
+        uint32_t w = f[d];
+        if (dneg) {  // 2^ib - field
+          const uint64_t x = 0ull - (uint64_t)w - nb;
+          w = (uint32_t)x;
+          nb = (uint32_t)(x >> 63);
+        }
+        magwin_push(w4, low_or, hk, w, d);
+      }
+    }
+    double res = 0.0;
+    if (st == 0 && hk >= 0) {
+      const int bl = 32 * hk + 32 - __clz(w4[3]);
+      uint64_t mant;
+      int shift;
+      magwin_round53(w4, low_or, hk, bl, true, mant, shift);
+      res = ldexp((double)mant, shift - p);
+      if (dneg) res = -res;
+    }
+    const size_t at = (size_t)(num - 1 - sl) * ostride + i;
+    out_f64[at] = res;
+    out_f32[at] = (float)res;
+  }
 }
 
 }  // namespace xhe

@@ -128,6 +128,22 @@ def encrypt_encoded_words(ctx, mw, obfuscation, num_cores=-1):
     return ct
 
 
+def embed_words(ctx, cols, ib, precision, num_cores=-1):
+    """embed's float64 columns [k, n] -> (encoded m words [n, nw], status):
+    packed and reduced mod n on the device (xhe_embed_f64_host), the input of
+    encrypt_encoded_words. One call on the first shard device: the columns are
+    contiguous per column, not per element."""
+    cols = np.ascontiguousarray(cols, dtype=np.float64)
+    k, n = cols.shape
+    mw = nat.empty((n, nw_of(ctx)), np.uint32)
+    st = np.empty(n, dtype=np.int32)
+    if n:
+        dk = ctx.device_key(ctx.shard_devices(num_cores)[0])
+        nat.check(nat.lib().xhe_embed_f64_host(dk.handle, _vp(cols), k, n, int(ib), int(precision), _vp(mw), _vp(st)),
+                  "embed")
+    return mw, st
+
+
 def obfuscate_words(ctx, cw, num_cores=-1):
     """PaillierCiphertext.obfuscate for a batch: c * X, X a fresh obfuscator
     (an encryption of 0), paillier.py:189-232."""
@@ -171,6 +187,23 @@ def decrypt_decode_words(ctx, cw, exps, num_cores=-1, want_m=False):
                                                         _vp(f32, lo), _vp(st, lo), _vp(m, lo)), "decrypt")
         sharded(ctx, n, body, num_cores)
     return (f64, f32, st, m) if want_m else (f64, f32, st)
+
+
+def decrypt_umbed_words(ctx, cw, num, ib, precision, num_cores=-1):
+    """decrypt + centred digits / 2^precision + float32 on the device ->
+    (f32 [num, n], status) (Paillier.decrypt(out_origin=True) followed by
+    umbed, paillier_acceleration.py:35-59). One call on the first shard
+    device: the outputs are contiguous per digit, not per element."""
+    cw = _u32(cw)
+    n = cw.shape[0]
+    f64 = np.empty((num, n), dtype=np.float64)
+    f32 = np.empty((num, n), dtype=np.float32)
+    st = np.empty(n, dtype=np.int32)
+    if n:
+        dk = ctx.device_key(ctx.shard_devices(num_cores)[0])
+        nat.check(nat.lib().xhe_decrypt_umbed_host(dk.handle, _vp(cw), n, int(num), int(ib), int(precision), _vp(f64),
+                                                   _vp(f32), _vp(st)), "decrypt")
+    return f32, st
 
 
 # ------------------------------------------------------------ homomorphic ops

@@ -280,7 +280,13 @@ class Paillier(object):
         words + exponents, ciphertext objects on element access); num_cores
         spreads the elements over GPUs (PaillierContext.shard_devices) where
         the reference spreads them over processes."""
+        from ..paillier_acceleration import PackedPlain
         from .array import PaillierArray
+        if isinstance(data, PackedPlain):  # embed_packed's columns: packed on the device where it can be
+            out = cls._encrypt_packed(context, data, precision, max_exponent, obfuscation, num_cores)
+            if out is not None:
+                return out
+            data = np.asarray(data)  # embed's object array, on the path below
         if isinstance(data, np.ndarray):
             shape = data.shape
             flat = data.reshape(-1)
@@ -342,6 +348,34 @@ class Paillier(object):
             return PaillierCiphertext(context, ops.encrypt_encoded(context, ms, obfuscation)[0], es[0])
         else:
             raise TypeError(f"Unsupported data type {type(data)}, accepted types are 'np.ndarray', 'int', 'float'.")
+
+    @staticmethod
+    def _encrypt_packed(context, data, precision, max_exponent, obfuscation, num_cores):
+        """Paillier.encrypt of embed_packed's result with the packing done by
+        xhe_embed_f64: the integers encode at exponent 0 (precision 0 or None,
+        no negative max_exponent), the geometry is one the device packs, and
+        every value fits its slot. Otherwise None: the caller encrypts embed's
+        integers on the existing path, so the answer is always the reference's."""
+        from ..paillier_acceleration import packed_geometry
+        from .array import PaillierArray
+        n = len(data)
+        if n == 0 or precision not in (0, None) or (max_exponent is not None and max_exponent < 0):
+            return None
+        ib = packed_geometry(context.n, data.cols.shape[0], data.interval, data.precision)
+        if ib is None:
+            return None
+        exps = np.zeros(n, dtype=np.int32)
+        dev = resident.device_for(context, num_cores, n, 4 * ops.n2w_of(context) + 16)
+        if dev is not None:  # results stay in HBM (resident.py)
+            if obfuscation:
+                context.note_encrypt_volume(n)
+            d, st = resident.encrypt_packed(context.device_key(dev), data.cols, ib, data.precision, obfuscation)
+            return None if st.any() else PaillierArray.from_device(context, d, exps, (n,))
+        mw, st = ops.embed_words(context, data.cols, ib, data.precision, num_cores)
+        if st.any():
+            return None
+        return PaillierArray.from_buffers(context, ops.encrypt_encoded_words(context, mw, obfuscation, num_cores),
+                                          exps, (n,))
 
     @staticmethod
     def _raise_status(st):

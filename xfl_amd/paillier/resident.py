@@ -253,11 +253,45 @@ def encrypt_floats(dk, x, precision, max_exponent, obfuscation):
     """encode + ChaCha20 draws + encrypt of float64 values (paillier.py:273-339)
     -> (device ct [n, n2w], exponents, status), exponents and status on the
     host (they decide the reference's exceptions)."""
+    dev = dk.device
+    L = nat.lib()
+    xd = upload(np.ascontiguousarray(x, dtype=np.float64), dev)
+    prec = -1 if precision is None else int(precision)
+    has_max = max_exponent is not None
+
+    def encode(lo, k, m, es):
+        nat.check(L.xhe_encode_f64(dk.handle, _dp(xd[lo:]), k, prec, int(has_max),
+                                   int(max_exponent) if has_max else 0, _dp(m), _dp(es[0, lo:]), _dp(es[1, lo:]),
+                                   _sp(dev)), "encrypt")
+    return _encrypt_pipeline(dk, x.shape[0], encode, obfuscation)
+
+
+def encrypt_packed(dk, cols, ib, precision, obfuscation):
+    """embed's float64 columns [k, n] -> (device ct [n, n2w], status): packed
+    and reduced mod n on the device (xhe_embed_f64), then the draws and the
+    encryption as encrypt_floats; every exponent is 0. A nonzero status (4: a
+    value does not fit its slot) sends the caller to the host path."""
+    dev = dk.device
+    L = nat.lib()
+    ncols, n = cols.shape
+
+    def encode(lo, k, m, es):
+        cd = upload(cols if k == n else cols[:, lo:lo + k], dev)  # the pass's columns, contiguous
+        nat.check(L.xhe_embed_f64(dk.handle, _dp(cd), ncols, k, int(ib), int(precision), _dp(m), _dp(es[1, lo:]),
+                                  _sp(dev)), "embed")
+    ct, _, st = _encrypt_pipeline(dk, n, encode, obfuscation)
+    return ct, st
+
+
+def _encrypt_pipeline(dk, n, encode, obfuscation):
+    """The encryption of n values behind an encoder: encode(lo, k, m, es)
+    queues the encoding of elements [lo, lo + k) on the drop-in stream - their
+    m words into m, exponents into es[0, lo:] (may be left unwritten: the
+    caller then ignores them) and statuses into es[1, lo:] -> (device ct,
+    exponents, status)."""
     torch = _torch()
     dev = dk.device
     L = nat.lib()
-    n = x.shape[0]
-    xd = upload(np.ascontiguousarray(x, dtype=np.float64), dev)
     c = max(1, min(n, CHUNK))
     from . import wire
     # large arrays: the encryption in launches of wire.ENC_SUB rows, each
@@ -274,8 +308,6 @@ def encrypt_floats(dk, x, precision, max_exponent, obfuscation):
         bits = torch.empty(n, dtype=torch.int16, device=f"cuda:{dev}") if n >= wire.PIPE_MIN else None
         rnds = [torch.empty((min(sub, c), dk.rand_words), dtype=torch.int32, device=f"cuda:{dev}")
                 for _ in range(2 if sub < c and ENC_STREAMS > 1 else 1)] if obfuscation else [None, None]
-    prec = -1 if precision is None else int(precision)
-    has_max = max_exponent is not None
     main = stream(dev)
     streams = [main, aux_stream(dev)] if sub < c and ENC_STREAMS > 1 else [main]
     es_h = None
@@ -283,9 +315,7 @@ def encrypt_floats(dk, x, precision, max_exponent, obfuscation):
     j = 0
     for lo in range(0, n, c):
         k = min(c, n - lo)
-        nat.check(L.xhe_encode_f64(dk.handle, _dp(xd[lo:]), k, prec, int(has_max),
-                                   int(max_exponent) if has_max else 0, _dp(m), _dp(es[0, lo:]), _dp(es[1, lo:]),
-                                   _sp(dev)), "encrypt")
+        encode(lo, k, m, es)
         if n <= c:
             # one pass: the exponents and statuses come back as soon as the
             # encoder has run (a bad input raises before any encryption is
@@ -395,6 +425,26 @@ def decrypt_decode(dk, c, exps):
     nat.check(L.xhe_decrypt(dk.handle, _dp(c), n, _dp(m), s), "decrypt")
     nat.check(L.xhe_decode(dk.handle, _dp(m), _dp(ed), n, _dp(f64), _dp(f32), _dp(st), s), "decrypt")
     return download(f64, np.float64), download(f32, np.float32), download(st, np.int32)
+
+
+def decrypt_umbed(dk, c, num, ib, precision):
+    """device ct -> host (f32 [num, n], status): decrypt, then the centred
+    digits / 2^precision and the float32 cast on the device (xhe_umbed); 4 B
+    per digit come back."""
+    torch = _torch()
+    dev = dk.device
+    L = nat.lib()
+    n = c.shape[0]
+    with _On(dev):
+        m = torch.empty((n, dk.nw), dtype=torch.int32, device=f"cuda:{dev}")
+        f64 = torch.empty((num, n), dtype=torch.float64, device=f"cuda:{dev}")
+        f32 = torch.empty((num, n), dtype=torch.float32, device=f"cuda:{dev}")
+        st = torch.empty(n, dtype=torch.int32, device=f"cuda:{dev}")
+    s = _sp(dev)
+    nat.check(L.xhe_decrypt(dk.handle, _dp(c), n, _dp(m), s), "decrypt")
+    nat.check(L.xhe_umbed(dk.handle, _dp(m), n, int(num), int(ib), int(precision), _dp(f64), _dp(f32), _dp(st), s),
+              "umbed")
+    return download(f32, np.float32), download(st, np.int32)
 
 
 def mulmod(dk, a, ea, b, eb, dmax):

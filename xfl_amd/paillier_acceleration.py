@@ -14,6 +14,13 @@ integers int(v * 2^precision) are formed exactly from each float's mantissa
 and exponent (numpy, no per-element Python float arithmetic), then the packed
 Python ints are assembled; umbed / unpack work on Python ints exactly as the
 reference does (their inputs are decrypted Python ints).
+
+Two additions move both ends onto the GPU, next to the encryption and
+decryption they feed (xhe_embed_f64 / xhe_umbed, include/xhe.h):
+  embed_packed(p_list, interval, precision) -> PackedPlain: embed's result
+      kept as its float64 columns; Paillier.encrypt packs them on the device
+  decrypt_umbed(context, data, num, interval, precison, num_cores): umbed of
+      Paillier.decrypt(..., out_origin=True), unpacked behind the decryption
 """
 from typing import List
 
@@ -50,6 +57,105 @@ def embed(p_list: List[np.ndarray], interval: int = (1 << 128), precision: int =
             x = x * interval + c[i]
         out[i] = x
     return np.array(out)
+
+
+def packed_geometry(n: int, slots: int, interval: int, precision: int):
+    """log2(interval) when the device packs / unpacks this geometry for the
+    modulus n (include/xhe.h: whole-word slots of 64..256 bits, precision at
+    most two bits below the slot, every slot below n's top bit), else None."""
+    if not isinstance(interval, int) or not isinstance(precision, int) or interval <= 0:
+        return None
+    ib = interval.bit_length() - 1
+    if interval != 1 << ib or ib % 32 or not 64 <= ib <= 256 or not 0 <= precision <= ib - 2:
+        return None
+    if slots < 1 or slots * ib > int(n).bit_length() - 1:
+        return None
+    return ib
+
+
+class PackedPlain:
+    """What embed(p_list, interval, precision) returns, kept as its float64
+    columns so that Paillier.encrypt can pack on the GPU: 8 bytes per value go
+    up and no Python integer is made. Wherever it is looked at it is the
+    object array embed returns: len, shape, ndim, dtype, x[i] (a Python int),
+    slices (a PackedPlain), iteration, and np.asarray(x) (embed's array,
+    built on first use)."""
+    __slots__ = ("cols", "interval", "precision", "_arr")
+
+    def __init__(self, cols: np.ndarray, interval: int, precision: int):
+        self.cols = cols  # [k, N] float64, C-contiguous, finite
+        self.interval = interval
+        self.precision = precision
+        self._arr = None
+
+    def __len__(self):
+        return self.cols.shape[1]
+
+    @property
+    def shape(self):
+        return (self.cols.shape[1],)
+
+    ndim = 1
+    dtype = np.dtype(object)
+
+    def __array__(self, dtype=None, copy=None):
+        if self._arr is None:
+            self._arr = embed(list(self.cols), self.interval, self.precision)
+        return self._arr if dtype is None else self._arr.astype(dtype)
+
+    def __getitem__(self, i):
+        if isinstance(i, slice):
+            return PackedPlain(np.ascontiguousarray(self.cols[:, i]), self.interval, self.precision)
+        if isinstance(i, (int, np.integer)):
+            if self._arr is not None:
+                return int(self._arr[i])
+            j = range(len(self))[i]  # IndexError and negative indices as a sequence's
+            return int(embed(list(self.cols[:, j:j + 1]), self.interval, self.precision)[0])
+        return self.__array__()[i]
+
+    def __iter__(self):
+        return iter(self.__array__())
+
+
+def embed_packed(p_list: List[np.ndarray], interval: int = (1 << 128), precision: int = 64) -> PackedPlain:
+    """embed for values on their way to Paillier.encrypt: the same packed
+    integers (np.asarray of the result is embed's array), formed on the GPU by
+    Paillier.encrypt instead of one Python int per sample here."""
+    cols = np.ascontiguousarray([np.asarray(p, dtype=np.float64).reshape(-1) for p in p_list], dtype=np.float64)
+    if not np.all(np.isfinite(cols)):
+        raise OverflowError("cannot convert float infinity to integer")
+    return PackedPlain(cols, interval, precision)
+
+
+def decrypt_umbed(context, data, num: int, interval: int = (1 << 128), precison: int = 64, num_cores: int = -1):
+    """umbed(Paillier.decrypt(context, data, num_cores=num_cores,
+    out_origin=True), num, interval, precison) as `num` float32 arrays, bit for
+    bit: for a ciphertext array the digits are taken and scaled on the GPU
+    behind the decryption, and only the floats come back. Missing entries,
+    nonzero exponents and geometries outside packed_geometry take the two
+    steps on the host."""
+    from .paillier import Paillier, PaillierCiphertext, ops, resident
+    from .paillier.array import SMALL, PaillierArray
+    if not context.is_private():
+        raise TypeError("Try to decrypt a paillier ciphertext by a public key.")
+    ib = packed_geometry(context.n, num, interval, precison)
+    arr = data
+    if ib is not None and isinstance(arr, np.ndarray) and arr.dtype == object and arr.ndim == 1 and arr.size and \
+            all(isinstance(c, PaillierCiphertext) for c in arr):
+        arr = PaillierArray(arr, context=context)
+    if ib is not None and isinstance(arr, PaillierArray) and arr.ndim == 1 and arr.size and not arr._has_na() and \
+            not arr.exponents.any():
+        arr = arr._aligned_words(ops.n2w_of(context))
+        dev = resident.device_for(context, num_cores)
+        if arr._resident_on(dev) or (dev is not None and arr.size <= SMALL):
+            f32, st = resident.decrypt_umbed(context.device_key(dev), arr._dw(dev), num, ib, precison)
+        else:
+            f32, st = ops.decrypt_umbed_words(context, arr.words, num, ib, precison, num_cores)
+        if np.any(st != 0):
+            raise OverflowError("Overflow detected during decoding encrypted number.")
+        return [f32[j] for j in range(num)]
+    vals = Paillier.decrypt(context, data, num_cores=num_cores, out_origin=True)
+    return [np.array(col, dtype=np.float32) for col in umbed(vals, num, interval, precison)]
 
 
 def _centred_digits(x, num: int, interval: int):
