@@ -47,3 +47,38 @@ def _run(counts, seed=7):
 def test_invert_batch_sizes(counts):
     _run(counts)
 
+
+def test_invert_no_inverse_level_tree():
+    """The level-by-level tree's no-inverse return, in both of its shapes: 300
+    elements (above the whole-block tree's 256: 16 lanes) and 4,100 (above
+    kN2RowMax = 4096: 4 lanes), each with one multiple of p in the middle;
+    the next valid batch in the same process still inverts."""
+    import torch
+
+    from xfl_amd import _native as nat
+    k = load_fixture("paillier_2048_djn.json")["key"]
+    n, p = hx(k["n"]), hx(k["p"])
+    n2 = n * n
+    dk = nat.DeviceKey(2048, n, None, None, None, device=0)
+    L = nat.lib()
+    rng = random.Random(11)
+    s = torch.cuda.current_stream().cuda_stream
+
+    def batch(count, bad):
+        cs = [rng.randrange(1, n2) for _ in range(count)]
+        cs = [c if c % p and c % (n // p) else c + 1 for c in cs]
+        if bad:
+            cs[count // 2] = p * 5
+        dc = torch.from_numpy(nat.ints_to_words(cs, dk.n2w).view(np.int32).copy()).cuda()
+        return cs, dc, torch.empty_like(dc)
+
+    for count in (300, 4100):
+        _, dc, out = batch(count, True)
+        assert L.xhe_invert(dk.handle, dc.data_ptr(), count, out.data_ptr(), s) == nat.XHE_ENOINV, count
+    cs, dc, out = batch(300, False)
+    nat.check(L.xhe_invert(dk.handle, dc.data_ptr(), 300, out.data_ptr(), s), "invert")
+    torch.cuda.synchronize()
+    got = nat.words_to_ints(out.cpu().numpy().view(np.uint32))
+    for i, (c, g) in enumerate(zip(cs, got)):
+        assert g == pow(c, -1, n2), i
+

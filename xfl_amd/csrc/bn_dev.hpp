@@ -27,33 +27,9 @@ namespace xhe {
 #define XHE_DEV __device__ __forceinline__
 #define XHE_INL __attribute__((always_inline))  // on lambdas holding Montgomery products: a call would put T[] in scratch
 
-// Build switches (A/B measurement; defaults are the measured-best variant)
-#ifndef XHE_NPIPE
-#define XHE_NPIPE 1  // TPI==1: modulus limbs loaded one block ahead (Mont::step1)
-#endif
-#ifndef XHE_MAC_SPLIT
-#define XHE_MAC_SPLIT 1  // a*b mads of a block before its m*N mads
-#endif
-#ifndef XHE_LDS_ROWS
-#define XHE_LDS_ROWS 1  // k_djn_pow_lds: table rows staged in LDS by LDS-DMA bursts
-#endif
-#ifndef XHE_SQ_LDS
-#define XHE_SQ_LDS 1  // variable-base exponentiations: squaring operand through LDS (SqLds)
-#endif
-#ifndef XHE_DJN_FOLD
-#define XHE_DJN_FOLD 1  // k_djn_pow_lds: (1 + n m) as the last (plain) multiplier, nwin + 1 products
-#endif
+// Build tunable (A/B measurement; the default is the measured-best value)
 #ifndef XHE_SQ_ACC
 #define XHE_SQ_ACC 2  // partial sums per column of Mont::sqr's product scan
-#endif
-#ifndef XHE_PMD
-#define XHE_PMD 1  // 2048-bit DJN tables as Montgomery digits, encrypted by k_djn_pmd (pdigit_dev.hpp)
-#endif
-#ifndef XHE_PMDX
-#define XHE_PMDX 1  // 3072/4096-bit DJN tables as Montgomery digits, encrypted by k_djn_pmdx over 4 lanes
-#endif
-#ifndef XHE_NDIG
-#define XHE_NDIG 1  // 2048-bit n^2 exponentiations (public non-DJN r^n, scalar mul c^k) in Montgomery digits mod n^2
 #endif
 // d = a*b + c with one v_mad_u64_u32. Inline asm keeps a and b 32-bit: the
 // C form (uint64_t)a*b + c makes the compiler hold every limb as a
@@ -378,7 +354,6 @@ struct Mont {
 #pragma unroll
     for (int k = 0; k < 8; ++k) r.t[k] = k < TL ? Np[J8 + k] : 0u;
   }
-#if XHE_MAC_SPLIT
   // all a_i*b products of the block first, then the m*N products: each m*N
   // mad reads an accumulator written 4 (8) instructions earlier instead of
   // by the instruction right before it
@@ -408,34 +383,6 @@ struct Mont {
   "v_mad_u64_u32 %5, vcc, %10, %24, %5\n\t"  \
   "v_mad_u64_u32 %6, vcc, %10, %25, %6\n\t"  \
   "v_mad_u64_u32 %7, vcc, %10, %26, %7"
-#else
-#define XHE_MAC4V_ASM                       \
-  "v_mad_u64_u32 %0, vcc, %5, %7, %1\n\t"   \
-  "v_mad_u64_u32 %0, vcc, %6, %11, %0\n\t"  \
-  "v_mad_u64_u32 %1, vcc, %5, %8, %2\n\t"   \
-  "v_mad_u64_u32 %1, vcc, %6, %12, %1\n\t"  \
-  "v_mad_u64_u32 %2, vcc, %5, %9, %3\n\t"   \
-  "v_mad_u64_u32 %2, vcc, %6, %13, %2\n\t"  \
-  "v_mad_u64_u32 %3, vcc, %5, %10, %4\n\t"  \
-  "v_mad_u64_u32 %3, vcc, %6, %14, %3"
-#define XHE_MAC8V_ASM                        \
-  "v_mad_u64_u32 %0, vcc, %9, %11, %1\n\t"   \
-  "v_mad_u64_u32 %0, vcc, %10, %19, %0\n\t"  \
-  "v_mad_u64_u32 %1, vcc, %9, %12, %2\n\t"   \
-  "v_mad_u64_u32 %1, vcc, %10, %20, %1\n\t"  \
-  "v_mad_u64_u32 %2, vcc, %9, %13, %3\n\t"   \
-  "v_mad_u64_u32 %2, vcc, %10, %21, %2\n\t"  \
-  "v_mad_u64_u32 %3, vcc, %9, %14, %4\n\t"   \
-  "v_mad_u64_u32 %3, vcc, %10, %22, %3\n\t"  \
-  "v_mad_u64_u32 %4, vcc, %9, %15, %5\n\t"   \
-  "v_mad_u64_u32 %4, vcc, %10, %23, %4\n\t"  \
-  "v_mad_u64_u32 %5, vcc, %9, %16, %6\n\t"   \
-  "v_mad_u64_u32 %5, vcc, %10, %24, %5\n\t"  \
-  "v_mad_u64_u32 %6, vcc, %9, %17, %7\n\t"   \
-  "v_mad_u64_u32 %6, vcc, %10, %25, %6\n\t"  \
-  "v_mad_u64_u32 %7, vcc, %9, %18, %8\n\t"   \
-  "v_mad_u64_u32 %7, vcc, %10, %26, %7"
-#endif
   XHE_DEV void mac4v(uint64_t (&T)[L], const uint32_t (&b)[L], uint32_t ai, uint32_t m, int j,
                      const uint32_t* n) const {
     asm(XHE_MAC4V_ASM
@@ -641,7 +588,7 @@ struct Mont {
   // limbs go through `hi` (the caller's per-lane LDS slot: put4 / load4) into
   // the reduction. Bounds: a column sum is below (S/2+1) 2^(2W+1) + carry; the
   // reduction adds S terms below 2^(2W) to limbs below 2^W - as in mul().
-  static constexpr bool kSqr = TPI == 1 && L >= 13 && XHE_NPIPE;
+  static constexpr bool kSqr = TPI == 1 && L >= 13;
   template <class HI>
   XHE_DEV void sqr(uint32_t (&b)[L], const HI& hi) const {
     uint32_t lo[L];
@@ -811,8 +758,7 @@ struct Mont {
     uint64_t x0 = mad64(cur.x, b[0], T[0]);
     uint32_t m = G::bcast0(((uint32_t)x0 * n0inv) & MASK);
     int i = 0;
-#if XHE_NPIPE
-    if constexpr (TPI == 1 && L >= 13) {
+    if constexpr (TPI == 1 && L >= 13) {  // modulus limbs loaded one block ahead (step1)
       NRes R;
       load_res(Np, R);
       for (; i + 4 <= S; i += 4) {
@@ -833,7 +779,6 @@ struct Mont {
         step1(Np, R, T, b, comp4(cur, r), r + 1 < (S & 3) ? comp4(cur, r + 1) : 0u, m, x0, lead);
       return;
     }
-#endif
     for (; i + 4 <= S; i += 4) {
       uint4 nxt = a.load4(i + 4 < S4 ? i + 4 : i);
       __builtin_amdgcn_sched_barrier(0);

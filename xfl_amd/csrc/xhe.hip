@@ -12,6 +12,7 @@
 #include <atomic>
 #include <stdexcept>
 #include <unordered_map>
+#include <utility>
 #include <string>
 #include <type_traits>
 #include <vector>
@@ -39,6 +40,27 @@ struct HipError : std::runtime_error {
     hipError_t _e = (x);                                                                   \
     if (_e != hipSuccess) throw HipError(std::string(#x) + ": " + hipGetErrorString(_e)); \
   } while (0)
+
+// Every kernel launch of this file: no dynamic LDS, launch errors thrown.
+// The arguments convert to the kernel's parameters implicitly, as in a direct
+// hipLaunchKernelGGL (nullptr and int literals included).
+template <class... KArgs, class... Args>
+void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t s, Args&&... args) {
+  hipLaunchKernelGGL(kernel, grid, block, 0, s, std::forward<Args>(args)...);
+  HIPCHK(hipGetLastError());
+}
+
+// Run-time switches ($XHE_*; INTEGRATION.md "Other kernel switches"). The
+// callers keep the value in a function-local static: read once per process.
+const char* env_str(const char* name) { return getenv(name); }
+bool env_on(const char* name) {  // on unless the value starts with '0'
+  const char* e = env_str(name);
+  return !(e && e[0] == '0');
+}
+int64_t env_int(const char* name, int64_t dflt) {
+  const char* e = env_str(name);
+  return e ? atoll(e) : dflt;
+}
 
 // ------------------------------------------------------------------ shapes
 // Limb shapes per key size: MP2 for residues mod p^2/q^2, MP for mod p/q.
@@ -130,16 +152,11 @@ decltype(auto) with_shape(int K, F&& f) {
 }
 #endif
 
-#if XHE_NDIG
 // $XHE_NDIG_PUB=0: public DJN keys keep Montgomery n^2 tables (k_djn_pub; A/B)
 bool ndig_pub_on() {
-  static const bool on = [] {
-    const char* e = getenv("XHE_NDIG_PUB");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("XHE_NDIG_PUB");
   return on;
 }
-#endif
 
 struct ModSpec {
   int S, W;
@@ -471,26 +488,18 @@ template <class MP2, int RW>
 void build_tables_seg(const ModDev& md, const uint32_t* d_base, int win, int nwin, int nbases, uint32_t* d_tab,
                       int64_t rs, uint32_t* d_chain, uint32_t* d_ws, hipStream_t s) {
   const int half = win / 2;
-  hipLaunchKernelGGL(k_tab_bases<MP2>, dim3(1), dim3(64), 0, s, md, d_base, win, nbases, d_chain, d_ws);
-  HIPCHK(hipGetLastError());
+  launch(k_tab_bases<MP2>, dim3(1), dim3(64), s, md, d_base, win, nbases, d_chain, d_ws);
   auto blocks = [&](int64_t groups) { return dim3((unsigned)std::max<int64_t>(1, (groups * MP2::TPI + 255) / 256)); };
-  hipLaunchKernelGGL(k_tab_one<MP2>, blocks(nwin), dim3(256), 0, s, md, win, nwin, d_chain);
-  HIPCHK(hipGetLastError());
+  launch(k_tab_one<MP2>, blocks(nwin), dim3(256), s, md, win, nwin, d_chain);
   const int lim_lo = (1 << half) + 1, lim_hi = 1 << (win - half);
   for (int t = 0; (1 << t) < lim_lo - 1; ++t) {
-    hipLaunchKernelGGL(k_tab_level<MP2>, blocks((int64_t)nwin << t), dim3(256), 0, s, md, md.N, win, nwin, t, 0,
-                       lim_lo, d_chain);
-    HIPCHK(hipGetLastError());
+    launch(k_tab_level<MP2>, blocks((int64_t)nwin << t), dim3(256), s, md, md.N, win, nwin, t, 0, lim_lo, d_chain);
   }
   for (int t = 0; (1 << t) < lim_hi - 1; ++t) {
-    hipLaunchKernelGGL(k_tab_level<MP2>, blocks((int64_t)nwin << t), dim3(256), 0, s, md, md.N, win, nwin, t, half,
-                       lim_hi, d_chain);
-    HIPCHK(hipGetLastError());
+    launch(k_tab_level<MP2>, blocks((int64_t)nwin << t), dim3(256), s, md, md.N, win, nwin, t, half, lim_hi, d_chain);
   }
   int64_t rows = (int64_t)nwin << win;
-  hipLaunchKernelGGL((k_tab_combine<MP2, RW>), blocks(rows), dim3(256), 0, s, md, md.N, win, nwin, d_chain, d_tab,
-                     rs);
-  HIPCHK(hipGetLastError());
+  launch((k_tab_combine<MP2, RW>), blocks(rows), dim3(256), s, md, md.N, win, nwin, d_chain, d_tab, rs);
 }
 
 // A key's tables (layout win_layout / win_digit): uniform, or the nhi wide
@@ -553,7 +562,6 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
     o_nR2n2 = bl.put_limbs(mulmod(n, mulmod(Rn2, Rn2, n2), n2), k->mn2);
     if (h && !p) o_hMn2 = bl.put_limbs(mulmod(mod(*h, n2), Rn2, n2), k->mn2);  // public DJN table base
   }
-#if XHE_NDIG
   // Montgomery digits mod n^2 (PMDX<80, 4>, pdigit_dev.hpp): n in 80 limbs of
   // 27 bits, R = 2^2160; ceil(R/n) n^2 (the input conversion's offset), R - n,
   // the digits (e, f) of R^2 mod n^2 and of 1 (R e + n f = X R^2 mod n^2),
@@ -595,7 +603,6 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
     for (auto& x : tc) x += (1u << 27) - 1u;
     on.topc = bl.put(tc);
   }
-#endif
   // randomness bound (paillier.py:195 djn_exp_bound = 2^(bitlen(n)//2); :215 r < n)
   k->rand_bits = k->djn ? (int)(n.bits() / 2) : (int)n.bits();
   k->rand_words = (k->rand_bits + 31) / 32;
@@ -698,7 +705,6 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
     o.hqR = bl.put_limbs(mulmod(hq, Rq, Q), s1);
     o.qinvpR = bl.put_limbs(mulmod(modinv(Q, P), Rp, P), s1);  // context.py:43
     o.q_lim = bl.put_limbs(Q, s1);
-#if XHE_PMD && XHE_LDS_ROWS
     if (K == 2048) {
       // Montgomery-digit kernels (k_djn_pmd, k_dec_pmd): MASK + E_i, E = (1 - R) mod P,
       // R = 2^(28*37) (= the mod-p shape's R, so R mod P is kd.p.R1)
@@ -710,8 +716,6 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
       o.topc_p = topc(P);
       o.topc_q = topc(Q);
     }
-#endif
-#if XHE_PMDX
     if (K == 3072 || K == 4096 || K == 8192) {
       // Montgomery digits mod P^2 over 4 lanes (k_djn_pmdx, k_dec_pmdx_*): per
       // prime the modulus P in K limbs of 27 bits (R = 2^(27 K)), ceil(R/P)
@@ -757,7 +761,6 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
         o.xhpR[i] = bl.put_limbs(mulmod(i ? hq : hp, RdX, X), sd);
       }
     }
-#endif
     o.p2x = bl.put_limbs(shl(P, 1), s1);
     o.p_lim = bl.put_limbs(P, s1);
     // non-DJN private obfuscation exponents ep = n mod phi(p^2) (context.py:51-52)
@@ -793,7 +796,6 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
   }
   kd.nR2_n2 = B + o_nR2n2;
   kd.n_bits = (int)n.bits();
-#if XHE_NDIG
   if (K == 2048) {
     kd.ndig = 1;
     kd.nd = moddev(B, on.nd);
@@ -804,7 +806,6 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
     kd.nd_d1 = reinterpret_cast<const uint2*>(B + on.d1);
     kd.nd_dwt = reinterpret_cast<const uint2*>(B + on.dwt);
   }
-#endif
   if (k->priv) {
     kd.p2 = moddev(B, o.p2);
     kd.p2L = moddev(B, o.p2L);
@@ -850,13 +851,10 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
       kd.rns_p = B + o.rns_p;
       kd.rns_q = B + o.rns_q;
     }
-#if XHE_PMD && XHE_LDS_ROWS
     if (K == 2048) {
       kd.topc_p = B + o.topc_p;
       kd.topc_q = B + o.topc_q;
     }
-#endif
-#if XHE_PMDX
     if (K == 3072 || K == 4096 || K == 8192) {
       kd.pmdx_dec = 1;
       kd.x_dw_p = reinterpret_cast<const uint2*>(B + o.xdw[0]);
@@ -876,7 +874,6 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
       kd.x_dwt_p = reinterpret_cast<const uint2*>(B + o.xdwt[0]);
       kd.x_dwt_q = reinterpret_cast<const uint2*>(B + o.xdwt[1]);
     }
-#endif
     if (k->djn) {
       kd.win = win & 0xff;
       win_layout(k->rand_bits, kd.win, (win & XHE_WIN_SPLIT) != 0, &kd.nwin, &kd.nhi);
@@ -893,21 +890,17 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
         using Sh = decltype(sh);
         build_tables_sync<typename Sh::MP2, Sh::RW>(k, mds, hms, tabs, 2);
       });
-#if XHE_PMD && XHE_LDS_ROWS
       if (K == 2048) {
         // rows as Montgomery digits (e, f) for k_djn_pmd
         kd.pmd = 1;
         const int64_t trows = (int64_t)(kd.nwin + kd.nhi) << kd.win;
         const ModDev mp[2] = {kd.p, kd.q};
         for (int i = 0; i < 2; ++i) {
-          hipLaunchKernelGGL((k_tab_to_pmd<37, 64>), dim3((unsigned)((trows + 255) / 256)), dim3(256), 0, nullptr,
-                             mp[i].N, mp[i].n0inv, mp[i].R1, tabs[i], trows, (int64_t)kd.tab_rs);
-          HIPCHK(hipGetLastError());
+          launch((k_tab_to_pmd<37, 64>), dim3((unsigned)((trows + 255) / 256)), dim3(256), nullptr, mp[i].N,
+                 mp[i].n0inv, mp[i].R1, tabs[i], trows, (int64_t)kd.tab_rs);
         }
         HIPCHK(hipDeviceSynchronize());
       }
-#endif
-#if XHE_PMDX
       if (K == 3072 || K == 4096 || K == 8192) {
         // rows as Montgomery digits (e, f) for k_djn_pmdx
         kd.pmdx = 1;
@@ -917,15 +910,13 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
           if constexpr (Sh::K == 3072 || Sh::K == 4096 || Sh::K == 8192) {
             using D = typename Sh::PDXO;
             for (int i = 0; i < 2; ++i) {
-              hipLaunchKernelGGL((k_tab_to_pmdx<D, Sh::RW>), dim3((unsigned)((trows * D::TPI + 127) / 128)),
-                                 dim3(128), 0, nullptr, kd, i, tabs[i], trows, (int64_t)kd.tab_rs);
-              HIPCHK(hipGetLastError());
+              launch((k_tab_to_pmdx<D, Sh::RW>), dim3((unsigned)((trows * D::TPI + 127) / 128)), dim3(128), nullptr, kd,
+                     i, tabs[i], trows, (int64_t)kd.tab_rs);
             }
           }
         });
         HIPCHK(hipDeviceSynchronize());
       }
-#endif
     }
   }
   if (!k->priv && k->djn) {
@@ -941,18 +932,15 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
       using Sh = decltype(sh);
       build_tables_sync<typename Sh::MN2, Sh::RW2>(k, &kd.n2, &hm, &tab, 1);
     });
-#if XHE_NDIG
     if (K == 2048 && ndig_pub_on()) {
       // rows as canonical Montgomery digits of n (e, f < n: 64 + 64 words,
       // still 512 B) for k_djn_pub_nd
       kd.pub_nd = 1;
       using D = PMDX<80, 4>;
-      hipLaunchKernelGGL((k_tab_to_pmdx<D, 128>), dim3((unsigned)((rows * D::TPI + 127) / 128)), dim3(128), 0, nullptr,
-                         kd, 2, tab, (int64_t)rows, (int64_t)128);
-      HIPCHK(hipGetLastError());
+      launch((k_tab_to_pmdx<D, 128>), dim3((unsigned)((rows * D::TPI + 127) / 128)), dim3(128), nullptr, kd, 2, tab,
+             (int64_t)rows, (int64_t)128);
       HIPCHK(hipDeviceSynchronize());
     }
-#endif
   }
 }
 
@@ -1045,7 +1033,10 @@ void ws_alloc(void** p, size_t bytes, hipStream_t s) {
   w.size[*p] = bytes;
 }
 
-void ws_free(void* p, hipStream_t s) {
+// Called from WsScope's destructor: errors of the stream-ordered free are
+// dropped; a failed host allocation in the bookkeeping (bad_alloc from the
+// free lists) ends the process, as in any destructor.
+void ws_free(void* p, hipStream_t s) noexcept {
   if (t_ws)
     for (auto& b : t_ws->blk)
       if (b.p == p) {
@@ -1072,8 +1063,66 @@ void ws_free(void* p, hipStream_t s) {
       }
     }
   }
-  for (void* q : drop) HIPCHK(hipFreeAsync(q, s));
+  for (void* q : drop) (void)hipFreeAsync(q, s);
 }
+
+// The workspaces of one entry-point call: get() allocates through ws_alloc;
+// at scope exit (also when a launch throws) they go back through ws_free in
+// allocation order. That is the order of the explicit frees this replaces,
+// and the stream free lists above depend on it: which block the next call
+// reuses, and which one is dropped first over kStreamWsKeep.
+class WsScope {
+  static constexpr int kMax = 8;  // encrypt_impl and dec_pmdx_launch hold 4
+  hipStream_t s_;
+  void* held_[kMax];
+  int n_ = 0;
+
+ public:
+  explicit WsScope(hipStream_t s) : s_(s) {}
+  WsScope(const WsScope&) = delete;
+  WsScope& operator=(const WsScope&) = delete;
+  ~WsScope() {
+    for (int i = 0; i < n_; ++i) ws_free(held_[i], s_);
+  }
+  template <class T>
+  T* get(size_t bytes) {
+    if (n_ == kMax) throw std::logic_error("WsScope: too many workspaces in one call (raise kMax)");
+    ws_alloc(&held_[n_], bytes, s_);
+    return (T*)held_[n_++];
+  }
+};
+
+// Owner of a stream-ordered allocation that bypasses the workspace caches.
+// Released by a synchronous hipFree, or with kAsync by hipFreeAsync on the
+// allocating stream (no host sync: for buffers no host frame feeds). Where a
+// call holds several, they are declared empty in reverse and filled in
+// allocation order, so that scope exit frees them in allocation order as the
+// explicit frees did (the pool hands blocks out by that order).
+struct DevBuf {
+  enum Release { kSync, kAsync };
+  void* p = nullptr;
+  hipStream_t s = nullptr;
+  Release rel = kSync;
+  DevBuf() = default;
+  DevBuf(size_t bytes, hipStream_t st, Release r = kSync) : s(st), rel(r) {
+    HIPCHK(hipMallocAsync(&p, std::max<size_t>(bytes, 4), s));
+  }
+  DevBuf(DevBuf&& o) noexcept : p(o.p), s(o.s), rel(o.rel) { o.p = nullptr; }
+  DevBuf& operator=(DevBuf&& o) noexcept {  // releases what it held, at this point
+    std::swap(p, o.p);
+    std::swap(s, o.s);
+    std::swap(rel, o.rel);
+    o.reset();
+    return *this;
+  }
+  ~DevBuf() { reset(); }
+  void reset() {
+    if (p) (void)(rel == kAsync ? hipFreeAsync(p, s) : hipFree(p));
+    p = nullptr;
+  }
+  template <class T>
+  T* as() const { return (T*)p; }
+};
 
 constexpr int64_t kChunk = 1 << 20;  // elements per launch chunk (bounds workspace)
 
@@ -1116,10 +1165,7 @@ struct ProfScope {
 // pins it.
 constexpr int64_t kEncRowMax = 20480;
 bool enc_row(int64_t count) {
-  static const int pin = [] {
-    const char* e = std::getenv("XHE_ENC_TPI");
-    return e ? std::atoi(e) : -1;
-  }();
+  static const int pin = (int)env_int("XHE_ENC_TPI", -1);
   return pin >= 0 ? pin == 16 : count <= kEncRowMax;
 }
 
@@ -1129,21 +1175,16 @@ template <class Sh, class MP2 = typename Sh::MP2>
 void crt_enc_launch(const xhe_key* k, int64_t n, uint32_t* ws, uint32_t* ct, hipStream_t s) {
   const int blocks = (int)((n * MP2::TPI + 255) / 256);
   if constexpr (MP2::TPI == 1)
-    hipLaunchKernelGGL((k_crt_enc_w<MP2, 2 * Sh::K / 32>), dim3(blocks), dim3(256), 0, s, k->kd, k->kd.p2.N, n, ws,
-                       ct);
+    launch((k_crt_enc_w<MP2, 2 * Sh::K / 32>), dim3(blocks), dim3(256), s, k->kd, k->kd.p2.N, n, ws, ct);
   else
-    hipLaunchKernelGGL(k_crt_enc<MP2>, dim3(blocks), dim3(256), 0, s, k->kd, k->kd.p2.N, n, ws, ct);
-  HIPCHK(hipGetLastError());
+    launch(k_crt_enc<MP2>, dim3(blocks), dim3(256), s, k->kd, k->kd.p2.N, n, ws, ct);
 }
 
 // lanes per element of k_djn_pmd: 16 up to 2 k elements, 4 up to 16 k, else
 // 1 (the chip holds ~128 k one-lane residues: 2 waves x 1024 SIMDs x 64);
 // $XHE_PMD_SPLIT pins it (1, 4 or 16)
 int pmd_split(int64_t n) {
-  static const int pin = [] {
-    const char* e = getenv("XHE_PMD_SPLIT");
-    return e ? atoi(e) : 0;
-  }();
+  static const int pin = (int)env_int("XHE_PMD_SPLIT", 0);
   if (pin == 1 || pin == 4 || pin == 16) return pin;
   return n <= 2048 ? 16 : n <= 16384 ? 4 : 1;
 }
@@ -1152,14 +1193,13 @@ template <class Sh>
 void encrypt_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r, int64_t count, uint32_t* ct, hipStream_t s) {
   using MP2 = typename Sh::MP2;
   int64_t chunk = std::min<int64_t>(count, kChunk);
-  uint32_t* ws = nullptr;
-  ws_alloc((void**)&ws, (size_t)2 * 2 * MP2::S4 * chunk * sizeof(uint32_t), s);
+  WsScope wsc(s);
+  uint32_t* ws = wsc.get<uint32_t>((size_t)2 * 2 * MP2::S4 * chunk * sizeof(uint32_t));
   uint2* xst = nullptr;  // k_djn_pmdx workspaces (allocated on first use)
   uint32_t *xrows = nullptr, *xwords = nullptr;
   for (int64_t off = 0; off < count; off += chunk) {
     int64_t n = std::min(chunk, count - off);
     int blocks = (int)((n * MP2::TPI + 255) / 256);
-#if XHE_PMD && XHE_LDS_ROWS
     if constexpr (Sh::K == 2048) {
       if (k->kd.pmd) {
         ProfScope ps("k_djn_pmd", s);
@@ -1167,76 +1207,58 @@ void encrypt_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r, int64_
         // ~nwin/G + log2 G dependent products instead of nwin)
         const int G = pmd_split(n);
         const dim3 grid((unsigned)((n * G + 127) / 128), 2);
-        auto launch = [&](auto kern) {
-          hipLaunchKernelGGL(kern, grid, dim3(128), 0, s, k->kd, k->kd.p.N, k->kd.q.N, k->kd.p2.N, k->kd.q2.N,
-                             m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, ws);
+        auto run = [&](auto kern) {
+          launch(kern, grid, dim3(128), s, k->kd, k->kd.p.N, k->kd.q.N, k->kd.p2.N, k->kd.q2.N, m + (size_t)off * k->nw,
+                 r + (size_t)off * k->rand_words, k->rand_words, n, ws);
         };
-        if (G == 16) launch(k_djn_pmd<MP2, 37, Sh::RW, 16>);
-        else if (G == 4) launch(k_djn_pmd<MP2, 37, Sh::RW, 4>);
-        else launch(k_djn_pmd<MP2, 37, Sh::RW, 1>);
-        HIPCHK(hipGetLastError());
+        if (G == 16) run(k_djn_pmd<MP2, 37, Sh::RW, 16>);
+        else if (G == 4) run(k_djn_pmd<MP2, 37, Sh::RW, 4>);
+        else run(k_djn_pmd<MP2, 37, Sh::RW, 1>);
         crt_enc_launch<Sh>(k, n, ws, ct + (size_t)off * k->n2w, s);
         continue;
       }
     }
-#endif
-#if XHE_PMDX
     if constexpr (Sh::K == 3072 || Sh::K == 4096 || Sh::K == 8192) {
       if (k->kd.pmdx) {
         using D = typename Sh::PDX;
         if (!xst) {
-          ws_alloc((void**)&xst, (size_t)2 * D::K * chunk * sizeof(uint2), s);
-          ws_alloc((void**)&xrows, (size_t)2 * 2 * Sh::PDXO::MN::S4 * chunk * sizeof(uint32_t), s);
-          ws_alloc((void**)&xwords, (size_t)2 * chunk * Sh::RW * sizeof(uint32_t), s);
+          xst = wsc.get<uint2>((size_t)2 * D::K * chunk * sizeof(uint2));
+          xrows = wsc.get<uint32_t>((size_t)2 * 2 * Sh::PDXO::MN::S4 * chunk * sizeof(uint32_t));
+          xwords = wsc.get<uint32_t>((size_t)2 * chunk * Sh::RW * sizeof(uint32_t));
         }
         const dim3 g4((unsigned)((n * D::TPI + 127) / 128), 2);
         {
           ProfScope ps("k_djn_pmdx", s);
-          hipLaunchKernelGGL((k_djn_pmdx<D, Sh::RW>), g4, dim3(128), 0, s, k->kd, r + (size_t)off * k->rand_words,
-                             k->rand_words, n, xst);
-          HIPCHK(hipGetLastError());
+          launch((k_djn_pmdx<D, Sh::RW>), g4, dim3(128), s, k->kd, r + (size_t)off * k->rand_words, k->rand_words, n,
+                 xst);
         }
         using DO = typename Sh::PDXO;  // the same state layout ([pair][count]) whatever the lanes per element
-        hipLaunchKernelGGL((k_pmdx_enc_out<DO, Sh::RW>), dim3((unsigned)((n * DO::TPI + 127) / 128), 2), dim3(128), 0,
-                           s, k->kd, m + (size_t)off * k->nw, n, xst, xrows, xwords);
-        HIPCHK(hipGetLastError());
-        hipLaunchKernelGGL(k_words_to_rows<MP2>, dim3((unsigned)((n * MP2::TPI + 255) / 256), 2), dim3(256), 0, s,
-                           xwords, Sh::RW, n, ws);
-        HIPCHK(hipGetLastError());
+        launch((k_pmdx_enc_out<DO, Sh::RW>), dim3((unsigned)((n * DO::TPI + 127) / 128), 2), dim3(128), s, k->kd,
+               m + (size_t)off * k->nw, n, xst, xrows, xwords);
+        launch(k_words_to_rows<MP2>, dim3((unsigned)((n * MP2::TPI + 255) / 256), 2), dim3(256), s, xwords, Sh::RW, n,
+               ws);
         crt_enc_launch<Sh>(k, n, ws, ct + (size_t)off * k->n2w, s);
         continue;
       }
     }
-#endif
     if (enc_row(n)) {
       // small batch: one 16-lane DPP row per residue (latency-bound regime)
       using MX = typename Sh::MP2X;
-      hipLaunchKernelGGL((k_djn_pow_x<MX, MP2::S4, Sh::RW>), dim3((unsigned)((n * MX::TPI + 255) / 256), 2), dim3(256), 0, s,
-                         k->kd, m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, ws);
-      HIPCHK(hipGetLastError());
+      launch((k_djn_pow_x<MX, MP2::S4, Sh::RW>), dim3((unsigned)((n * MX::TPI + 255) / 256), 2), dim3(256), s, k->kd,
+             m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, ws);
     } else {
       // labelled by the kernel rocprof shows (k_djn_pow_lds / k_djn_pow)
-      ProfScope ps(XHE_LDS_ROWS && MP2::TPI == 1 ? "k_djn_pow_lds" : "k_djn_pow", s);
-#if XHE_LDS_ROWS
-      if constexpr (MP2::TPI == 1) {
+      ProfScope ps(MP2::TPI == 1 ? "k_djn_pow_lds" : "k_djn_pow", s);
+      if constexpr (MP2::TPI == 1) {  // table rows staged in LDS by LDS-DMA bursts
         const dim3 grid((unsigned)((n + 127) / 128), 2);
-        hipLaunchKernelGGL((k_djn_pow_lds<MP2, Sh::RW>), grid, dim3(128), 0, s, k->kd,
-                           k->kd.p2.N, k->kd.q2.N, m + (size_t)off * k->nw, r + (size_t)off * k->rand_words,
-                           k->rand_words, n, ws);
-      } else
-#endif
-      hipLaunchKernelGGL((k_djn_pow<MP2, Sh::RW>), dim3(blocks, 2), dim3(256), 0, s, k->kd, k->kd.p2.N, k->kd.q2.N,
-                         m + (size_t)off * k->nw,
-                         r + (size_t)off * k->rand_words, k->rand_words, n, ws);
-      HIPCHK(hipGetLastError());
+        launch((k_djn_pow_lds<MP2, Sh::RW>), grid, dim3(128), s, k->kd, k->kd.p2.N, k->kd.q2.N, m + (size_t)off * k->nw,
+               r + (size_t)off * k->rand_words, k->rand_words, n, ws);
+      } else {
+        launch((k_djn_pow<MP2, Sh::RW>), dim3(blocks, 2), dim3(256), s, k->kd, k->kd.p2.N, k->kd.q2.N,
+               m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, ws);
+      }
     }
     crt_enc_launch<Sh>(k, n, ws, ct + (size_t)off * k->n2w, s);
-  }
-  ws_free(ws, s);
-  if (xst) {
-    ws_free(xst, s);
-    ws_free(xrows, s);
-    ws_free(xwords, s);
   }
 }
 
@@ -1249,59 +1271,46 @@ int pow_grid(int64_t count, int cap_blocks) {
 template <class Sh>
 void encrypt_pub_djn_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r, int64_t count, uint32_t* ct,
                           hipStream_t s) {
-#if XHE_NDIG
   if constexpr (Sh::K == 2048) {
     if (k->kd.pub_nd) {
       // fixed-base products in Montgomery digits of n (k_djn_pub_nd), then
       // (1 + n m) folded in base n on the way out (k_ndig_out)
       using D = PMDX<80, 4>;  // ND2048
       const int64_t chunk = std::min<int64_t>(count, kChunk);
-      uint2* st = nullptr;
-      uint32_t* rows = nullptr;
-      ws_alloc((void**)&st, (size_t)D::K * chunk * sizeof(uint2), s);
-      ws_alloc((void**)&rows, (size_t)2 * D::MN::S4 * chunk * sizeof(uint32_t), s);
+      WsScope wsc(s);
+      uint2* st = wsc.get<uint2>((size_t)D::K * chunk * sizeof(uint2));
+      uint32_t* rows = wsc.get<uint32_t>((size_t)2 * D::MN::S4 * chunk * sizeof(uint32_t));
       for (int64_t off = 0; off < count; off += chunk) {
         const int64_t n = std::min(chunk, count - off);
         const int eb = (int)((n * D::TPI + 127) / 128);
         {
           ProfScope ps("k_djn_pub", s);
-          hipLaunchKernelGGL((k_djn_pub_nd<D, Sh::RW2>), dim3(eb), dim3(128), 0, s, k->kd,
-                             r + (size_t)off * k->rand_words, k->rand_words, n, st);
-          HIPCHK(hipGetLastError());
+          launch((k_djn_pub_nd<D, Sh::RW2>), dim3(eb), dim3(128), s, k->kd, r + (size_t)off * k->rand_words,
+                 k->rand_words, n, st);
         }
-        hipLaunchKernelGGL((k_ndig_out<D, true>), dim3(eb), dim3(128), 0, s, k->kd, st, m + (size_t)off * k->nw, n,
-                           ct + (size_t)off * k->n2w, rows);
-        HIPCHK(hipGetLastError());
+        launch((k_ndig_out<D, true>), dim3(eb), dim3(128), s, k->kd, st, m + (size_t)off * k->nw, n,
+               ct + (size_t)off * k->n2w, rows);
       }
-      ws_free(st, s);
-      ws_free(rows, s);
       return;
     }
   }
-#endif
   using MN2 = typename Sh::MN2;
   int64_t chunk = std::min<int64_t>(count, kChunk);
-  uint32_t* ws = nullptr;
-  ws_alloc((void**)&ws, (size_t)MN2::S4 * chunk * sizeof(uint32_t), s);
+  WsScope wsc(s);
+  uint32_t* ws = wsc.get<uint32_t>((size_t)MN2::S4 * chunk * sizeof(uint32_t));
   for (int64_t off = 0; off < count; off += chunk) {
     int64_t n = std::min(chunk, count - off);
     int blocks = (int)((n * MN2::TPI + 255) / 256);
     ProfScope ps("k_djn_pub", s);
-    hipLaunchKernelGGL((k_djn_pub<MN2, Sh::RW2>), dim3(blocks), dim3(256), 0, s, k->kd, k->kd.n2.N, m + (size_t)off * k->nw,
-                       r + (size_t)off * k->rand_words, k->rand_words, n, ws, ct + (size_t)off * k->n2w);
-    HIPCHK(hipGetLastError());
+    launch((k_djn_pub<MN2, Sh::RW2>), dim3(blocks), dim3(256), s, k->kd, k->kd.n2.N, m + (size_t)off * k->nw,
+           r + (size_t)off * k->rand_words, k->rand_words, n, ws, ct + (size_t)off * k->n2w);
   }
-  ws_free(ws, s);
 }
 
-#if XHE_NDIG
 using ND2048 = PMDX<80, 4>;
 // $XHE_NDIG=0: the Montgomery mod-n^2 kernels instead (A/B measurement)
 bool ndig_on() {
-  static const bool on = [] {
-    const char* e = getenv("XHE_NDIG");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("XHE_NDIG");
   return on;
 }
 // in -> exponentiation -> out over chunks of up to kChunk elements; the
@@ -1312,34 +1321,22 @@ void ndig_run(int64_t count, hipStream_t s, IN&& in, POW&& pw, OUT&& out) {
   using D = ND2048;
   const int64_t chunk = std::min<int64_t>(count, kChunk);
   const int pblocks = (int)std::min<int64_t>((chunk + NdigWs<D>::GPB - 1) / NdigWs<D>::GPB, 1024);
-  uint2 *st = nullptr, *tab = nullptr;
-  uint32_t* rows = nullptr;
-  ws_alloc((void**)&st, (size_t)D::K * chunk * sizeof(uint2), s);
-  ws_alloc((void**)&tab, NdigWs<D>::tab_bytes_per_slot() * (size_t)pblocks * NdigWs<D>::GPB, s);
-  ws_alloc((void**)&rows, (size_t)2 * D::MN::S4 * chunk * sizeof(uint32_t), s);
+  WsScope wsc(s);
+  uint2* st = wsc.get<uint2>((size_t)D::K * chunk * sizeof(uint2));
+  uint2* tab = wsc.get<uint2>(NdigWs<D>::tab_bytes_per_slot() * (size_t)pblocks * NdigWs<D>::GPB);
+  uint32_t* rows = wsc.get<uint32_t>((size_t)2 * D::MN::S4 * chunk * sizeof(uint32_t));
   for (int64_t off = 0; off < count; off += chunk) {
     const int64_t n = std::min(chunk, count - off);
     const int eblocks = (int)((n * D::TPI + 127) / 128);
     in(eblocks, off, n, st);
-    HIPCHK(hipGetLastError());
     pw(std::min<int>(pblocks, (int)((n + NdigWs<D>::GPB - 1) / NdigWs<D>::GPB)), off, n, st, tab);
-    HIPCHK(hipGetLastError());
     out(eblocks, off, n, st, rows);
-    HIPCHK(hipGetLastError());
   }
-  ws_free(st, s);
-  ws_free(tab, s);
-  ws_free(rows, s);
 }
-#endif
 
-#if XHE_PMD && XHE_LDS_ROWS
 // $XHE_NODJN_PMD=0: the Montgomery k_nodjn_crt instead (A/B measurement)
 bool nodjn_pmd_on() {
-  static const bool on = [] {
-    const char* e = getenv("XHE_NODJN_PMD");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("XHE_NODJN_PMD");
   return on;
 }
 
@@ -1355,45 +1352,35 @@ void encrypt_nodjn_pmd(const xhe_key* k, const uint32_t* m, const uint32_t* r, i
   const int64_t chunk = std::min<int64_t>(count, kChunk);
   const int pow_blocks = (int)std::min<int64_t>((chunk + 127) / 128, 1024);
   const int64_t lanes = (int64_t)pow_blocks * 128;
-  uint4 *ws = nullptr, *st = nullptr;
-  uint32_t* rows = nullptr;
-  ws_alloc((void**)&ws, (size_t)2 * 16 * NQ * lanes * sizeof(uint4), s);
-  ws_alloc((void**)&st, (size_t)2 * NQ * chunk * sizeof(uint4), s);
-  ws_alloc((void**)&rows, (size_t)2 * 2 * MP2::S4 * chunk * sizeof(uint32_t), s);
+  WsScope wsc(s);
+  uint4* ws = wsc.get<uint4>((size_t)2 * 16 * NQ * lanes * sizeof(uint4));
+  uint4* st = wsc.get<uint4>((size_t)2 * NQ * chunk * sizeof(uint4));
+  uint32_t* rows = wsc.get<uint32_t>((size_t)2 * 2 * MP2::S4 * chunk * sizeof(uint32_t));
   for (int64_t off = 0; off < count; off += chunk) {
     const int64_t n = std::min(chunk, count - off);
     const dim3 g1((unsigned)((n + 127) / 128), 2);
-    hipLaunchKernelGGL((k_dec_pmd_in<MP2, 37>), g1, dim3(128), 0, s, k->kd, k->kd.p.N, k->kd.q.N, k->kd.p2.N,
-                       k->kd.q2.N, r + (size_t)off * k->rand_words, k->rand_words, n, st);
-    HIPCHK(hipGetLastError());
+    launch((k_dec_pmd_in<MP2, 37>), g1, dim3(128), s, k->kd, k->kd.p.N, k->kd.q.N, k->kd.p2.N, k->kd.q2.N,
+           r + (size_t)off * k->rand_words, k->rand_words, n, st);
     {
       ProfScope ps("k_nodjn_crt", s);
-      hipLaunchKernelGGL((k_dec_pmd_pow<37>), dim3((unsigned)std::min<int64_t>((n + 127) / 128, pow_blocks), 2),
-                         dim3(128), 0, s, k->kd, k->kd.p.N, k->kd.q.N, 1, n, st, ws);
-      HIPCHK(hipGetLastError());
+      launch((k_dec_pmd_pow<37>), dim3((unsigned)std::min<int64_t>((n + 127) / 128, pow_blocks), 2), dim3(128), s,
+             k->kd, k->kd.p.N, k->kd.q.N, 1, n, st, ws);
     }
-    hipLaunchKernelGGL((k_nodjn_pmd_out<MP2, 37>), g1, dim3(128), 0, s, k->kd, k->kd.p.N, k->kd.q.N, k->kd.p2.N,
-                       k->kd.q2.N, m + (size_t)off * k->nw, n, st, rows);
-    HIPCHK(hipGetLastError());
+    launch((k_nodjn_pmd_out<MP2, 37>), g1, dim3(128), s, k->kd, k->kd.p.N, k->kd.q.N, k->kd.p2.N, k->kd.q2.N,
+           m + (size_t)off * k->nw, n, st, rows);
     crt_enc_launch<Sh>(k, n, rows, ct + (size_t)off * k->n2w, s);
   }
-  ws_free(ws, s);
-  ws_free(st, s);
-  ws_free(rows, s);
 }
-#endif
 
 template <class Sh>
 void encrypt_nodjn_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r, int64_t count, uint32_t* ct,
                         hipStream_t s) {
-#if XHE_PMD && XHE_LDS_ROWS
   if constexpr (Sh::K == 2048) {
     if (k->priv && nodjn_pmd_on()) {
       encrypt_nodjn_pmd<Sh>(k, m, r, count, ct, s);
       return;
     }
   }
-#endif
   if (k->priv) {
     using MP2 = typename Sh::MP2;
     // 2-lane batch shapes (3072 bits, 55 limbs per lane) spill in this
@@ -1403,59 +1390,52 @@ void encrypt_nodjn_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r, 
     int64_t chunk = std::min<int64_t>(count, kChunk);
     int pb = pow_grid<MPE>(chunk, 512);
     int64_t groups = (int64_t)pb * 256 / MPE::TPI;
-    uint32_t *ws = nullptr, *rows = nullptr;
-    ws_alloc((void**)&ws, (size_t)2 * 18 * MPE::S4 * groups * sizeof(uint32_t), s);
-    ws_alloc((void**)&rows, (size_t)2 * 2 * MP2::S4 * chunk * sizeof(uint32_t), s);
+    WsScope wsc(s);
+    uint32_t* ws = wsc.get<uint32_t>((size_t)2 * 18 * MPE::S4 * groups * sizeof(uint32_t));
+    uint32_t* rows = wsc.get<uint32_t>((size_t)2 * 2 * MP2::S4 * chunk * sizeof(uint32_t));
     for (int64_t off = 0; off < count; off += chunk) {
       int64_t n = std::min(chunk, count - off);
       {
         ProfScope ps("k_nodjn_crt", s);
         const ModDev& mp = wide ? k->kd.p2L : k->kd.p2;
         const ModDev& mq = wide ? k->kd.q2L : k->kd.q2;
-        hipLaunchKernelGGL((k_nodjn_crt<MPE, wide ? 1 : 0, MP2::S4>), dim3(pb, 2), dim3(256), 0, s, k->kd, mp.N, mq.N,
-                           m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, rows, ws);
-        HIPCHK(hipGetLastError());
+        launch((k_nodjn_crt<MPE, wide ? 1 : 0, MP2::S4>), dim3(pb, 2), dim3(256), s, k->kd, mp.N, mq.N,
+               m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, rows, ws);
       }
       crt_enc_launch<Sh>(k, n, rows, ct + (size_t)off * k->n2w, s);
     }
-    ws_free(ws, s);
-    ws_free(rows, s);
   } else {
-#if XHE_NDIG
     if constexpr (Sh::K == 2048) {
       if (k->kd.ndig && ndig_on()) {
         ndig_run(
             count, s,
             [&](int b, int64_t off, int64_t n, uint2* st) {
-              hipLaunchKernelGGL((k_ndig_in<ND2048, false>), dim3(b), dim3(128), 0, s, k->kd,
-                                 r + (size_t)off * k->rand_words, k->rand_words, n, st);
+              launch((k_ndig_in<ND2048, false>), dim3(b), dim3(128), s, k->kd, r + (size_t)off * k->rand_words,
+                     k->rand_words, n, st);
             },
             [&](int b, int64_t, int64_t n, uint2* st, uint2* tab) {
               ProfScope ps("k_nodjn_pub", s);
-              hipLaunchKernelGGL(k_ndig_pow_n<ND2048>, dim3(b), dim3(128), 0, s, k->kd, n, st, tab);
+              launch(k_ndig_pow_n<ND2048>, dim3(b), dim3(128), s, k->kd, n, st, tab);
             },
             [&](int b, int64_t off, int64_t n, uint2* st, uint32_t* rows) {
-              hipLaunchKernelGGL((k_ndig_out<ND2048, true>), dim3(b), dim3(128), 0, s, k->kd, st,
-                                 m + (size_t)off * k->nw, n, ct + (size_t)off * k->n2w, rows);
+              launch((k_ndig_out<ND2048, true>), dim3(b), dim3(128), s, k->kd, st, m + (size_t)off * k->nw, n,
+                     ct + (size_t)off * k->n2w, rows);
             });
         return;
       }
     }
-#endif
     using MN2 = typename Sh::MN2;
     int64_t chunk = std::min<int64_t>(count, kChunk);
     int pb = pow_grid<MN2>(chunk, 512);
     int64_t groups = (int64_t)pb * 256 / MN2::TPI;
-    uint32_t* ws = nullptr;
-    ws_alloc((void**)&ws, (size_t)18 * MN2::S4 * groups * sizeof(uint32_t), s);
+    WsScope wsc(s);
+    uint32_t* ws = wsc.get<uint32_t>((size_t)18 * MN2::S4 * groups * sizeof(uint32_t));
     for (int64_t off = 0; off < count; off += chunk) {
       int64_t n = std::min(chunk, count - off);
       ProfScope ps("k_nodjn_pub", s);
-      hipLaunchKernelGGL(k_nodjn_pub<MN2>, dim3(pb), dim3(256), 0, s, k->kd, k->kd.n2.N, m + (size_t)off * k->nw,
-                         r + (size_t)off * k->rand_words, k->rand_words, n, ct + (size_t)off * k->n2w, ws);
-      HIPCHK(hipGetLastError());
+      launch(k_nodjn_pub<MN2>, dim3(pb), dim3(256), s, k->kd, k->kd.n2.N, m + (size_t)off * k->nw,
+             r + (size_t)off * k->rand_words, k->rand_words, n, ct + (size_t)off * k->n2w, ws);
     }
-    ws_free(ws, s);
   }
 }
 
@@ -1472,12 +1452,8 @@ const ModDev& n2h(const xhe_key* k) {
 // 4 lanes beyond. $XHE_N2_TPI (4 or 16) pins one shape (A/B measurement).
 constexpr int64_t kN2RowMax = 4096;
 bool n2_row(int64_t count) {
-  static const int pin = [] {
-    const char* e = std::getenv("XHE_N2_TPI");
-    int t = e ? std::atoi(e) : 0;
-    return (t == 4 || t == 16) ? t : 0;
-  }();
-  return pin ? pin == 16 : count <= kN2RowMax;
+  static const int pin = (int)env_int("XHE_N2_TPI", 0);
+  return pin == 4 || pin == 16 ? pin == 16 : count <= kN2RowMax;
 }
 
 // Adds of a few elements run one 16-wave block per element (k_mulmod_wave,
@@ -1488,10 +1464,7 @@ bool n2_row(int64_t count) {
 constexpr int64_t kWaveAddMax = 256;
 constexpr int kWaveAddMinD = 0;
 bool add_wave_on() {
-  static const bool on = [] {
-    const char* e = getenv("XHE_ADD_WAVE");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("XHE_ADD_WAVE");
   return on;
 }
 
@@ -1500,10 +1473,7 @@ bool add_wave_on() {
 // one-product Barrett kernel (k_add_barrett); $XHE_ADD_BAR=0 keeps the
 // Montgomery pair (k_mulmod_n2) for the A/B.
 bool add_bar_on() {
-  static const bool on = [] {
-    const char* e = getenv("XHE_ADD_BAR");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("XHE_ADD_BAR");
   return on;
 }
 
@@ -1512,9 +1482,7 @@ void mulmod_impl(const xhe_key* k, const uint32_t* a, const int32_t* ea, const u
                  int64_t count, int dmax, uint32_t* out, int32_t* eout, hipStream_t s) {
   if constexpr (Sh::K == 2048) {
     if (count <= kWaveAddMax && dmax >= kWaveAddMinD && add_wave_on()) {
-      hipLaunchKernelGGL((k_mulmod_wave<154, 16>), dim3((unsigned)count), dim3(1024), 0, s, k->kd, a, ea, b, eb, count,
-                         out, eout);
-      HIPCHK(hipGetLastError());
+      launch((k_mulmod_wave<154, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, a, ea, b, eb, count, out, eout);
       return;
     }
   }
@@ -1522,64 +1490,54 @@ void mulmod_impl(const xhe_key* k, const uint32_t* a, const int32_t* ea, const u
     if (dmax == 0 && add_bar_on()) {
       ProfScope ps("k_add_barrett", s);
       const int64_t blocks = (count + bar::EPB - 1) / bar::EPB;
-      hipLaunchKernelGGL(k_add_barrett, dim3((unsigned)blocks), dim3(bar::TPB), 0, s, k->kd, a, ea, b, eb, count, out,
-                         eout);
-      HIPCHK(hipGetLastError());
+      launch(k_add_barrett, dim3((unsigned)blocks), dim3(bar::TPB), s, k->kd, a, ea, b, eb, count, out, eout);
       return;
     }
   }
   int64_t chunk = std::min<int64_t>(count, kChunk);
-  uint32_t* ws = nullptr;
-  ws_alloc((void**)&ws, (size_t)2 * MN2::S4 * chunk * sizeof(uint32_t), s);
+  WsScope wsc(s);
+  uint32_t* ws = wsc.get<uint32_t>((size_t)2 * MN2::S4 * chunk * sizeof(uint32_t));
   for (int64_t off = 0; off < count; off += chunk) {
     int64_t n = std::min(chunk, count - off);
     int blocks = (int)((n * MN2::TPI + 255) / 256);
-    hipLaunchKernelGGL(k_mulmod_n2<MN2>, dim3(blocks), dim3(256), 0, s, k->kd, n2h<MN2>(k).N, a + (size_t)off * k->n2w,
-                       ea ? ea + off : nullptr, b + (size_t)off * k->n2w, eb ? eb + off : nullptr, n, dmax,
-                       out + (size_t)off * k->n2w, eout ? eout + off : nullptr, ws);
-    HIPCHK(hipGetLastError());
+    launch(k_mulmod_n2<MN2>, dim3(blocks), dim3(256), s, k->kd, n2h<MN2>(k).N, a + (size_t)off * k->n2w,
+           ea ? ea + off : nullptr, b + (size_t)off * k->n2w, eb ? eb + off : nullptr, n, dmax,
+           out + (size_t)off * k->n2w, eout ? eout + off : nullptr, ws);
   }
-  ws_free(ws, s);
 }
 
 template <class Sh, class MN2 = typename Sh::MN2>
 void powmod_impl(const xhe_key* k, const uint32_t* c, const uint32_t* kw_, int kw, int kbits, int64_t count,
                  uint32_t* out, hipStream_t s) {
-#if XHE_NDIG
   if constexpr (Sh::K == 2048 && MN2::TPI == 4) {
     if (k->kd.ndig && ndig_on()) {
       ndig_run(
           count, s,
           [&](int b, int64_t off, int64_t n, uint2* st) {
-            hipLaunchKernelGGL((k_ndig_in<ND2048, true>), dim3(b), dim3(128), 0, s, k->kd, c + (size_t)off * k->n2w,
-                               k->n2w, n, st);
+            launch((k_ndig_in<ND2048, true>), dim3(b), dim3(128), s, k->kd, c + (size_t)off * k->n2w, k->n2w, n, st);
           },
           [&](int b, int64_t off, int64_t n, uint2* st, uint2* tab) {
             ProfScope ps("k_powmod_n2", s);
-            hipLaunchKernelGGL(k_ndig_pow_k<ND2048>, dim3(b), dim3(128), 0, s, k->kd, kw_ + (size_t)off * kw, kw,
-                               kbits, n, st, tab);
+            launch(k_ndig_pow_k<ND2048>, dim3(b), dim3(128), s, k->kd, kw_ + (size_t)off * kw, kw, kbits, n, st, tab);
           },
           [&](int b, int64_t off, int64_t n, uint2* st, uint32_t* rows) {
-            hipLaunchKernelGGL((k_ndig_out<ND2048, false>), dim3(b), dim3(128), 0, s, k->kd, st, nullptr, n,
-                               out + (size_t)off * k->n2w, rows);
+            launch((k_ndig_out<ND2048, false>), dim3(b), dim3(128), s, k->kd, st, nullptr, n,
+                   out + (size_t)off * k->n2w, rows);
           });
       return;
     }
   }
-#endif
   int64_t chunk = std::min<int64_t>(count, kChunk);
   int pb = pow_grid<MN2>(chunk, 512);
   int64_t groups = (int64_t)pb * 256 / MN2::TPI;
-  uint32_t* ws = nullptr;
-  ws_alloc((void**)&ws, (size_t)17 * MN2::S4 * groups * sizeof(uint32_t), s);
+  WsScope wsc(s);
+  uint32_t* ws = wsc.get<uint32_t>((size_t)17 * MN2::S4 * groups * sizeof(uint32_t));
   for (int64_t off = 0; off < count; off += chunk) {
     int64_t n = std::min(chunk, count - off);
     ProfScope ps("k_powmod_n2", s);
-    hipLaunchKernelGGL(k_powmod_n2<MN2>, dim3(pb), dim3(256), 0, s, k->kd, n2h<MN2>(k).N, c + (size_t)off * k->n2w,
-                       kw_ + (size_t)off * kw, kw, kbits, n, out + (size_t)off * k->n2w, ws);
-    HIPCHK(hipGetLastError());
+    launch(k_powmod_n2<MN2>, dim3(pb), dim3(256), s, k->kd, n2h<MN2>(k).N, c + (size_t)off * k->n2w,
+           kw_ + (size_t)off * kw, kw, kbits, n, out + (size_t)off * k->n2w, ws);
   }
-  ws_free(ws, s);
 }
 
 // Batch inversion mod n^2 via a product tree (Montgomery's trick in parallel).
@@ -1606,93 +1564,67 @@ int invert_impl(const xhe_key* k, const uint32_t* c, int64_t count, uint32_t* ou
       wtot += n;
     }
     const int nlev = (int)sizes.size();
-    uint32_t *lv = nullptr, *inv = nullptr, *wds = nullptr;
-    HIPCHK(hipMallocAsync((void**)&lv, (size_t)wtot * KW * 4, s));
-    HIPCHK(hipMallocAsync((void**)&inv, (size_t)wtot * KW * 4, s));
-    HIPCHK(hipMallocAsync((void**)&wds, (size_t)2 * k->n2w * 4, s));
+    DevBuf wds_, inv_, lv_;
+    lv_ = DevBuf((size_t)wtot * KW * 4, s, DevBuf::kAsync);
+    inv_ = DevBuf((size_t)wtot * KW * 4, s, DevBuf::kAsync);
+    wds_ = DevBuf((size_t)2 * k->n2w * 4, s, DevBuf::kAsync);
+    uint32_t *lv = lv_.as<uint32_t>(), *inv = inv_.as<uint32_t>(), *wds = wds_.as<uint32_t>();
     auto node = [&](uint32_t* b, int l) { return b + (size_t)woff[l] * KW; };
-    hipLaunchKernelGGL((k_wtree_in<KW, 16>), dim3((unsigned)count), dim3(1024), 0, s, k->kd, c, lv);
-    HIPCHK(hipGetLastError());
+    launch((k_wtree_in<KW, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, c, lv);
     for (int l = 1; l < nlev; ++l) {
-      hipLaunchKernelGGL((k_wtree_up<KW, 16>), dim3((unsigned)sizes[l]), dim3(1024), 0, s, k->kd, node(lv, l - 1),
-                         sizes[l - 1], node(lv, l));
-      HIPCHK(hipGetLastError());
+      launch((k_wtree_up<KW, 16>), dim3((unsigned)sizes[l]), dim3(1024), s, k->kd, node(lv, l - 1), sizes[l - 1],
+             node(lv, l));
     }
-    hipLaunchKernelGGL((k_wtree_out<KW, 16>), dim3(1), dim3(1024), 0, s, k->kd, node(lv, nlev - 1), wds);
-    HIPCHK(hipGetLastError());
+    launch((k_wtree_out<KW, 16>), dim3(1), dim3(1024), s, k->kd, node(lv, nlev - 1), wds);
     std::vector<uint32_t> root(k->n2w), yinv(k->n2w);
     HIPCHK(hipMemcpyAsync(root.data(), wds, (size_t)k->n2w * 4, hipMemcpyDeviceToHost, s));
     HIPCHK(hipStreamSynchronize(s));
-    if (!modinv_words(root.data(), k->n2_host.data(), k->n2w, yinv.data())) {
-      (void)hipFreeAsync(lv, s);
-      (void)hipFreeAsync(inv, s);
-      (void)hipFreeAsync(wds, s);
+    if (!modinv_words(root.data(), k->n2_host.data(), k->n2w, yinv.data()))
       return fail(XHE_ENOINV, "invert(a, b) no inverse exists");
-    }
     HIPCHK(hipMemcpyAsync(wds + k->n2w, yinv.data(), (size_t)k->n2w * 4, hipMemcpyHostToDevice, s));
-    hipLaunchKernelGGL((k_wtree_in<KW, 16>), dim3(1), dim3(1024), 0, s, k->kd, wds + k->n2w, node(inv, nlev - 1));
-    HIPCHK(hipGetLastError());
+    launch((k_wtree_in<KW, 16>), dim3(1), dim3(1024), s, k->kd, wds + k->n2w, node(inv, nlev - 1));
     for (int l = nlev - 2; l >= 0; --l) {
-      hipLaunchKernelGGL((k_wtree_down<KW, 16>), dim3((unsigned)sizes[l]), dim3(1024), 0, s, k->kd, node(inv, l + 1),
-                         node(lv, l), sizes[l], node(inv, l));
-      HIPCHK(hipGetLastError());
+      launch((k_wtree_down<KW, 16>), dim3((unsigned)sizes[l]), dim3(1024), s, k->kd, node(inv, l + 1), node(lv, l),
+             sizes[l], node(inv, l));
     }
-    hipLaunchKernelGGL((k_wtree_out<KW, 16>), dim3((unsigned)count), dim3(1024), 0, s, k->kd, inv, out);
-    HIPCHK(hipGetLastError());
+    launch((k_wtree_out<KW, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, inv, out);
     HIPCHK(hipStreamSynchronize(s));  // yinv is host memory of this frame
-    (void)hipFreeAsync(lv, s);
-    (void)hipFreeAsync(inv, s);
-    (void)hipFreeAsync(wds, s);
     return XHE_OK;
   }
   }
-  uint32_t *lv = nullptr, *inv = nullptr, *scr = nullptr;
-  int32_t* st = nullptr;
-  HIPCHK(hipMallocAsync((void**)&lv, tot * 4, s));
-  HIPCHK(hipMallocAsync((void**)&inv, tot * 4, s));
-  HIPCHK(hipMallocAsync((void**)&scr, (size_t)(4 * (k->n2w + 1) + 2 * k->n2w + 8) * 4, s));
-  HIPCHK(hipMallocAsync((void**)&st, 4, s));
+  // (freed synchronously on return; st_ is read by no kernel, kept so that the call allocates as it did)
+  DevBuf st_, scr_, inv_, lv_;
+  lv_ = DevBuf(tot * 4, s);
+  inv_ = DevBuf(tot * 4, s);
+  scr_ = DevBuf((size_t)(4 * (k->n2w + 1) + 2 * k->n2w + 8) * 4, s);
+  st_ = DevBuf(4, s);
+  uint32_t *lv = lv_.as<uint32_t>(), *inv = inv_.as<uint32_t>(), *scr = scr_.as<uint32_t>();
   auto blocks = [&](int64_t n) { return dim3((unsigned)((n * MN2::TPI + 255) / 256)); };
-  hipLaunchKernelGGL(k_to_mont_rows<MN2>, blocks(count), dim3(256), 0, s, k->kd, n2h<MN2>(k).N, c, count, lv);
-  HIPCHK(hipGetLastError());
+  launch(k_to_mont_rows<MN2>, blocks(count), dim3(256), s, k->kd, n2h<MN2>(k).N, c, count, lv);
   for (size_t l = 1; l < sizes.size(); ++l) {
-    hipLaunchKernelGGL(k_tree_up<MN2>, blocks(sizes[l]), dim3(256), 0, s, k->kd, n2h<MN2>(k).N, lv + offs[l - 1],
-                       sizes[l - 1], lv + offs[l], sizes[l]);
-    HIPCHK(hipGetLastError());
+    launch(k_tree_up<MN2>, blocks(sizes[l]), dim3(256), s, k->kd, n2h<MN2>(k).N, lv + offs[l - 1], sizes[l - 1],
+           lv + offs[l], sizes[l]);
   }
   size_t top = offs.back();
   uint32_t* y_words = scr + 4 * (k->n2w + 1);
   uint32_t* r_words = y_words + k->n2w;
-  hipLaunchKernelGGL(k_row_pack<MN2>, dim3(1), dim3(64), 0, s, k->kd, n2h<MN2>(k).N, lv + top, r_words);
-  HIPCHK(hipGetLastError());
+  launch(k_row_pack<MN2>, dim3(1), dim3(64), s, k->kd, n2h<MN2>(k).N, lv + top, r_words);
   // The one scalar inverse of the batch (the tree root, (prod c_i) R) is a
   // sequential extended Euclid: ~1 ms on a host core vs a single GPU lane's
   // tens of milliseconds. Everything per element stays on the device.
   std::vector<uint32_t> root(k->n2w), yinv(k->n2w);
   HIPCHK(hipMemcpyAsync(root.data(), r_words, (size_t)k->n2w * 4, hipMemcpyDeviceToHost, s));
   HIPCHK(hipStreamSynchronize(s));
-  if (!modinv_words(root.data(), k->n2_host.data(), k->n2w, yinv.data())) {
-    (void)hipFree(lv);
-    (void)hipFree(inv);
-    (void)hipFree(scr);
-    (void)hipFree(st);
+  if (!modinv_words(root.data(), k->n2_host.data(), k->n2w, yinv.data()))
     return fail(XHE_ENOINV, "invert(a, b) no inverse exists");
-  }
   HIPCHK(hipMemcpyAsync(y_words, yinv.data(), (size_t)k->n2w * 4, hipMemcpyHostToDevice, s));
-  hipLaunchKernelGGL(k_inv_to_row<MN2>, dim3(1), dim3(64), 0, s, k->kd, n2h<MN2>(k).N, y_words, inv + top);
-  HIPCHK(hipGetLastError());
+  launch(k_inv_to_row<MN2>, dim3(1), dim3(64), s, k->kd, n2h<MN2>(k).N, y_words, inv + top);
   for (size_t l = sizes.size() - 1; l >= 1; --l) {
-    hipLaunchKernelGGL(k_tree_down<MN2>, blocks(sizes[l - 1]), dim3(256), 0, s, k->kd, n2h<MN2>(k).N, inv + offs[l],
-                       sizes[l], lv + offs[l - 1], sizes[l - 1], inv + offs[l - 1]);
-    HIPCHK(hipGetLastError());
+    launch(k_tree_down<MN2>, blocks(sizes[l - 1]), dim3(256), s, k->kd, n2h<MN2>(k).N, inv + offs[l], sizes[l],
+           lv + offs[l - 1], sizes[l - 1], inv + offs[l - 1]);
   }
-  hipLaunchKernelGGL(k_from_mont_rows<MN2>, blocks(count), dim3(256), 0, s, k->kd, n2h<MN2>(k).N, inv, count, out);
-  HIPCHK(hipGetLastError());
+  launch(k_from_mont_rows<MN2>, blocks(count), dim3(256), s, k->kd, n2h<MN2>(k).N, inv, count, out);
   HIPCHK(hipStreamSynchronize(s));
-  (void)hipFree(lv);
-  (void)hipFree(inv);
-  (void)hipFree(scr);
-  (void)hipFree(st);
   return XHE_OK;
 }
 
@@ -1742,12 +1674,12 @@ HostStage& host_stage() {
 // Reduce segment-ordered rows [S4][count] to one Montgomery row per segment
 // (seg: nseg+1 offsets) by levels of k_chunk_prod (C rows per chunk). The
 // input rows are Montgomery rows, or plain residues with raw = true (the
-// first level then returns each chunk to Montgomery form). Takes ownership
-// of `rows`; returns a new [S4][nseg] buffer (hipFree by the caller); an
-// empty segment yields the Montgomery one.
+// first level then returns each chunk to Montgomery form). Returns the
+// [S4][nseg] rows (`rows` itself when there is nothing to multiply); an empty
+// segment yields the Montgomery one.
 template <class Sh, class MN2 = typename Sh::MN2>
-uint32_t* reduce_segments(const xhe_key* k, uint32_t* rows, int64_t count, std::vector<int64_t> seg, hipStream_t s,
-                          bool raw = false, const uint32_t* words = nullptr) {
+DevBuf reduce_segments(const xhe_key* k, DevBuf rows, int64_t count, std::vector<int64_t> seg, hipStream_t s,
+                       bool raw = false, const uint32_t* words = nullptr) {
   // words: raw input as ciphertext words ([count][n2w]) instead of rows
   // (the first level unpacks them itself; rows is then unused)
   const int S4 = MN2::S4;
@@ -1813,26 +1745,23 @@ uint32_t* reduce_segments(const xhe_key* k, uint32_t* rows, int64_t count, std::
     first = false;
   }
   if (plan.empty()) return rows;  // already one Montgomery row per segment
-  int64_t* dplan = nullptr;
+  DevBuf dplan_;
   if (!all.empty()) {
-    HIPCHK(hipMallocAsync((void**)&dplan, all.size() * 8, s));
-    host_stage().upload(dplan, all.data(), all.size() * 8, s, k->device);  // no host sync
+    dplan_ = DevBuf(all.size() * 8, s, DevBuf::kAsync);
+    host_stage().upload(dplan_.p, all.data(), all.size() * 8, s, k->device);  // no host sync
   }
-  uint32_t* cur = rows;
+  const int64_t* dplan = dplan_.as<int64_t>();
+  DevBuf cur = std::move(rows);
   for (const Level& L : plan) {
-    uint32_t* nxt = nullptr;
-    HIPCHK(hipMallocAsync((void**)&nxt, (size_t)S4 * std::max<int64_t>(L.n_out, 1) * 4, s));
+    DevBuf nxt((size_t)S4 * std::max<int64_t>(L.n_out, 1) * 4, s, DevBuf::kAsync);
     if (L.raw && words)
-      hipLaunchKernelGGL((k_chunk_prod_words<MN2, Sh::RW2>), blocks(L.n_out), dim3(256), 0, s, k->kd,
-                         n2h<MN2>(k).N, words, uniform ? nullptr : dplan + L.plan_off, L.seg_len, L.ncs, L.n_out, nxt);
+      launch((k_chunk_prod_words<MN2, Sh::RW2>), blocks(L.n_out), dim3(256), s, k->kd, n2h<MN2>(k).N, words,
+             uniform ? nullptr : dplan + L.plan_off, L.seg_len, L.ncs, L.n_out, nxt.as<uint32_t>());
     else
-      hipLaunchKernelGGL(k_chunk_prod<MN2>, blocks(L.n_out), dim3(256), 0, s, k->kd, n2h<MN2>(k).N, cur, L.n_in,
-                         uniform ? nullptr : dplan + L.plan_off, L.seg_len, L.ncs, L.n_out, nxt, L.raw ? 1 : 0);
-    HIPCHK(hipGetLastError());
-    if (cur) HIPCHK(hipFreeAsync(cur, s));
-    cur = nxt;
+      launch(k_chunk_prod<MN2>, blocks(L.n_out), dim3(256), s, k->kd, n2h<MN2>(k).N, cur.as<uint32_t>(), L.n_in,
+             uniform ? nullptr : dplan + L.plan_off, L.seg_len, L.ncs, L.n_out, nxt.as<uint32_t>(), L.raw ? 1 : 0);
+    cur = std::move(nxt);  // the level's input is freed here, in stream order
   }
-  if (dplan) HIPCHK(hipFreeAsync(dplan, s));
   return cur;
 }
 
@@ -1843,29 +1772,24 @@ void segprod_impl(const xhe_key* k, const uint32_t* c, const int32_t* d, int dma
                   const int64_t* seg_begin_host, int64_t nseg, uint32_t* out, hipStream_t s) {
   const int S4 = MN2::S4;
   auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
-  uint32_t *rows = nullptr, *sq = nullptr;
+  DevBuf rows, sq;
   // no alignment anywhere: the first level reads the ciphertext words itself
   // ($XHE_SUM_WORDS=0: the k_align_mont transpose first, A/B)
-  static const bool words_on = [] {
-    const char* e = getenv("XHE_SUM_WORDS");
-    return !(e && e[0] == '0');
-  }();
+  static const bool words_on = env_on("XHE_SUM_WORDS");
   const bool direct = count > 0 && (dmax == 0 || !d) && words_on;
   if (!direct) {
-    HIPCHK(hipMallocAsync((void**)&rows, (size_t)S4 * std::max<int64_t>(count, 1) * 4, s));
-    HIPCHK(hipMallocAsync((void**)&sq, (size_t)S4 * std::max<int64_t>(count, 1) * 4, s));
+    rows = DevBuf((size_t)S4 * std::max<int64_t>(count, 1) * 4, s, DevBuf::kAsync);
+    sq = DevBuf((size_t)S4 * std::max<int64_t>(count, 1) * 4, s, DevBuf::kAsync);
   }
   if (count > 0 && !direct) {
-    hipLaunchKernelGGL(k_align_mont<MN2>, blocks(count), dim3(256), 0, s, k->kd, n2h<MN2>(k).N, c, d, count, dmax,
-                       rows, sq);
-    HIPCHK(hipGetLastError());
+    launch(k_align_mont<MN2>, blocks(count), dim3(256), s, k->kd, n2h<MN2>(k).N, c, d, count, dmax,
+           rows.as<uint32_t>(), sq.as<uint32_t>());
   }
-  uint32_t* cur = reduce_segments<Sh, MN2>(
-      k, rows, count, std::vector<int64_t>(seg_begin_host, seg_begin_host + nseg + 1), s, true, direct ? c : nullptr);
-  hipLaunchKernelGGL(k_from_mont_rows<MN2>, blocks(nseg), dim3(256), 0, s, k->kd, n2h<MN2>(k).N, cur, nseg, out);
-  HIPCHK(hipGetLastError());
-  (void)hipFreeAsync(cur, s);  // stream-ordered: no host sync (the output is ready in stream order)
-  if (sq) (void)hipFreeAsync(sq, s);
+  // stream-ordered frees: no host sync (the output is ready in stream order)
+  const DevBuf cur = reduce_segments<Sh, MN2>(k, std::move(rows), count,
+                                              std::vector<int64_t>(seg_begin_host, seg_begin_host + nseg + 1), s, true,
+                                              direct ? c : nullptr);
+  launch(k_from_mont_rows<MN2>, blocks(nseg), dim3(256), s, k->kd, n2h<MN2>(k).N, cur.as<uint32_t>(), nseg, out);
 }
 
 // Window bits for a multi-exponentiation: minimise table products
@@ -1893,17 +1817,17 @@ void multiexp_impl(const xhe_key* k, const uint32_t* bases, int64_t nbases, cons
   const int S4 = MN2::S4;
   auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
   const int nwin = std::max(1, (kbits + c - 1) / c);
-  uint32_t *tab = nullptr, *rows = nullptr, *sq = nullptr;
-  HIPCHK(hipMallocAsync((void**)&tab, ((size_t)nbases << c) * S4 * 4, s));
+  // every buffer here: stream-ordered frees, no host sync
+  DevBuf sq, prod, tab;
+  tab = DevBuf(((size_t)nbases << c) * S4 * 4, s, DevBuf::kAsync);
   {
     ProfScope ps("k_mexp_tab", s);
     // by levels of entries (c + 1 dependent products per base); one launch
     // per level
     for (int lvl = 1; lvl <= c; ++lvl) {
       const int64_t per = lvl <= 1 ? 1 : lvl < c ? ((int64_t)1 << (lvl - 1)) : ((int64_t)1 << (lvl - 1)) - 1;
-      hipLaunchKernelGGL(k_mexp_tab_lvl<MN2>, blocks(nbases * per), dim3(256), 0, s, k->kd, n2h<MN2>(k).N, bases,
-                         nbases, c, lvl, tab);
-      HIPCHK(hipGetLastError());
+      launch(k_mexp_tab_lvl<MN2>, blocks(nbases * per), dim3(256), s, k->kd, n2h<MN2>(k).N, bases, nbases, c, lvl,
+             tab.as<uint32_t>());
     }
   }
   // enough lane groups to fill the chip, at least 2 terms per group
@@ -1912,56 +1836,46 @@ void multiexp_impl(const xhe_key* k, const uint32_t* bases, int64_t nbases, cons
   const int64_t chunk = std::max<int64_t>(2, std::min<int64_t>(64, (segs * nterms + target_groups - 1) / target_groups));
   const int64_t nchunks = (nterms + chunk - 1) / chunk;
   const int64_t n_out = segs * nchunks;
-  HIPCHK(hipMallocAsync((void**)&rows, (size_t)S4 * n_out * 4, s));
+  DevBuf rows((size_t)S4 * n_out * 4, s, DevBuf::kAsync);
   {
     ProfScope ps("k_mexp_gather", s);
-    hipLaunchKernelGGL(k_mexp_gather<MN2>, blocks(n_out), dim3(256), 0, s, k->kd, n2h<MN2>(k).N, tab, c, idx, kx, kw,
-                       nterms, nwin, nchunks, chunk, n_out, rows);
-    HIPCHK(hipGetLastError());
+    launch(k_mexp_gather<MN2>, blocks(n_out), dim3(256), s, k->kd, n2h<MN2>(k).N, tab.as<uint32_t>(), c, idx, kx, kw,
+           nterms, nwin, nchunks, chunk, n_out, rows.as<uint32_t>());
   }
   std::vector<int64_t> seg(segs + 1);
   for (int64_t i = 0; i <= segs; ++i) seg[i] = i * nchunks;
-  uint32_t* P = reduce_segments<Sh, MN2>(k, rows, n_out, std::move(seg), s);
-  HIPCHK(hipMallocAsync((void**)&sq, (size_t)S4 * ncols * 4, s));
+  prod = reduce_segments<Sh, MN2>(k, std::move(rows), n_out, std::move(seg), s);
+  const uint32_t* P = prod.as<uint32_t>();
+  sq = DevBuf((size_t)S4 * ncols * 4, s, DevBuf::kAsync);
   {
     ProfScope ps("k_mexp_horner", s);
     bool wave = false;
     if constexpr (Sh::K == 2048 && MN2::TPI == 16) {
       // small batches: one 16-wave block per column (latency; k_mexp_horner_wave)
-      static const bool on = [] {
-        const char* e = getenv("XHE_MEXP_WAVE");
-        return !(e && e[0] == '0');
-      }();
+      static const bool on = env_on("XHE_MEXP_WAVE");
       if (on && ncols <= 4096) {
-        hipLaunchKernelGGL((k_mexp_horner_wave<154, 16>), dim3((unsigned)ncols), dim3(1024), 0, s, k->kd, P, nwin, c,
-                           ncols, out);
+        launch((k_mexp_horner_wave<154, 16>), dim3((unsigned)ncols), dim3(1024), s, k->kd, P, nwin, c, ncols, out);
         wave = true;
       }
     }
     if (!wave)
-      hipLaunchKernelGGL(k_mexp_horner<MN2>, blocks(ncols), dim3(256), 0, s, k->kd, n2h<MN2>(k).N, P, nwin, c, ncols,
-                         sq, out);
-    HIPCHK(hipGetLastError());
+      launch(k_mexp_horner<MN2>, blocks(ncols), dim3(256), s, k->kd, n2h<MN2>(k).N, P, nwin, c, ncols,
+             sq.as<uint32_t>(), out);
   }
-  (void)hipFreeAsync(tab, s);  // stream-ordered frees: no host sync
-  (void)hipFreeAsync(P, s);
-  (void)hipFreeAsync(sq, s);
 }
 
 template <class Sh>
 void raw_encrypt_impl(const xhe_key* k, const uint32_t* m, int64_t count, uint32_t* ct, hipStream_t s) {
   using MP2 = typename Sh::MP2;
   int64_t chunk = std::min<int64_t>(count, kChunk);
-  uint32_t* ws = nullptr;
-  ws_alloc((void**)&ws, (size_t)2 * MP2::S4 * chunk * sizeof(uint32_t), s);
+  WsScope wsc(s);
+  uint32_t* ws = wsc.get<uint32_t>((size_t)2 * MP2::S4 * chunk * sizeof(uint32_t));
   for (int64_t off = 0; off < count; off += chunk) {
     int64_t n = std::min(chunk, count - off);
     int blocks = (int)((n * MP2::TPI + 255) / 256);
-    hipLaunchKernelGGL(k_raw_enc<MP2>, dim3(blocks), dim3(256), 0, s, k->kd, m + (size_t)off * k->nw, n, ws,
-                       ct + (size_t)off * k->n2w);
-    HIPCHK(hipGetLastError());
+    launch(k_raw_enc<MP2>, dim3(blocks), dim3(256), s, k->kd, m + (size_t)off * k->nw, n, ws,
+           ct + (size_t)off * k->n2w);
   }
-  ws_free(ws, s);
 }
 
 // Decrypt exponentiation shapes by batch size (latency- vs throughput-bound):
@@ -1971,20 +1885,17 @@ void raw_encrypt_impl(const xhe_key* k, const uint32_t* m, int64_t count, uint32
 // 11.3/11.8/11.9 ms for 4 lanes; 4 lanes 20-21 ms at 16 k vs 36 ms for 1
 // lane, 40 ms at 32 k vs 37 ms). $XHE_DEC_TPI (1, 4 or 16) pins one shape.
 constexpr int64_t kDecRowMax = 5120;
-// One 256-thread block per residue (k_dec_rns, 2048-bit keys) up to
-// kDecWaveMax elements (tools/dec_shapes.py, profiles/r6: 1,024 elements
+// One block of rns::NT = 384 threads (six waves; two blocks per CU by its
+// launch bounds) per residue (k_dec_rns, 2048-bit keys) up to kDecWaveMax
+// elements (tools/dec_shapes.py, profiles/r6: 1,024 elements
 // 5.68 ms vs 6.11 ms in 16 lanes, 1,536 8.34 vs 6.13 ms); $XHE_DEC_TPI=64
 // pins it.
 constexpr int64_t kDecWaveMax = 1024;
 constexpr int64_t kDecQuadMax = 28672;
 
 int dec_tpi_override() {
-  static const int v = [] {
-    const char* e = std::getenv("XHE_DEC_TPI");
-    int t = e ? std::atoi(e) : 0;
-    return (t == 1 || t == 4 || t == 16 || t == 64) ? t : 0;
-  }();
-  return v;
+  static const int t = (int)env_int("XHE_DEC_TPI", 0);
+  return (t == 1 || t == 4 || t == 16 || t == 64) ? t : 0;
 }
 
 template <class MP2S, int SHAPE, class MP2>
@@ -1992,54 +1903,40 @@ void dec_pow_launch(const xhe_key* k, const uint32_t* ct, int64_t n, int64_t chu
                     hipStream_t s) {
   int pow_blocks = (int)std::min<int64_t>((chunk * MP2S::TPI + 255) / 256, 512);
   int64_t groups = (int64_t)pow_blocks * 256 / MP2S::TPI;
-  uint32_t* ws = nullptr;
-  ws_alloc((void**)&ws, (size_t)2 * 17 * MP2S::S4 * groups * sizeof(uint32_t), s);
+  WsScope wsc(s);
+  uint32_t* ws = wsc.get<uint32_t>((size_t)2 * 17 * MP2S::S4 * groups * sizeof(uint32_t));
   const ModDev& mp = SHAPE == 2 ? k->kd.p2X : SHAPE == 1 ? k->kd.p2L : k->kd.p2;
   const ModDev& mq = SHAPE == 2 ? k->kd.q2X : SHAPE == 1 ? k->kd.q2L : k->kd.q2;
   {
     ProfScope ps("k_dec_pow", s);
-    hipLaunchKernelGGL((k_dec_pow<MP2S, SHAPE>), dim3(pow_blocks, 2), dim3(256), 0, s, k->kd, mp.N, mq.N, ct, n,
-                       (int)MP2::S4, xrows, ws);
-    HIPCHK(hipGetLastError());
+    launch((k_dec_pow<MP2S, SHAPE>), dim3(pow_blocks, 2), dim3(256), s, k->kd, mp.N, mq.N, ct, n, (int)MP2::S4, xrows,
+           ws);
   }
-  ws_free(ws, s);
 }
 
-#if XHE_PMD && XHE_LDS_ROWS
 // one lane per residue, exponentiation in Montgomery digits (2048-bit keys)
 template <class MP2>
 void dec_pmd_launch(const xhe_key* k, const uint32_t* ct, int64_t n, int64_t chunk, uint32_t* xrows, hipStream_t s) {
   constexpr int NQ = PMD<37>::NQ;
   const int pow_blocks = (int)std::min<int64_t>((chunk + 127) / 128, 1024);
   const int64_t lanes = (int64_t)pow_blocks * 128;
-  uint4 *ws = nullptr, *st = nullptr;
-  ws_alloc((void**)&ws, (size_t)2 * 16 * NQ * lanes * sizeof(uint4), s);
-  ws_alloc((void**)&st, (size_t)2 * NQ * chunk * sizeof(uint4), s);
+  WsScope wsc(s);
+  uint4* ws = wsc.get<uint4>((size_t)2 * 16 * NQ * lanes * sizeof(uint4));
+  uint4* st = wsc.get<uint4>((size_t)2 * NQ * chunk * sizeof(uint4));
   const dim3 g1((unsigned)((n + 127) / 128), 2);
-  hipLaunchKernelGGL((k_dec_pmd_in<MP2, 37>), g1, dim3(128), 0, s, k->kd, k->kd.p.N, k->kd.q.N, k->kd.p2.N,
-                     k->kd.q2.N, ct, k->n2w, n, st);
-  HIPCHK(hipGetLastError());
+  launch((k_dec_pmd_in<MP2, 37>), g1, dim3(128), s, k->kd, k->kd.p.N, k->kd.q.N, k->kd.p2.N, k->kd.q2.N, ct, k->n2w, n,
+         st);
   {
     ProfScope ps("k_dec_pow", s);
-    hipLaunchKernelGGL((k_dec_pmd_pow<37>), dim3(pow_blocks, 2), dim3(128), 0, s, k->kd, k->kd.p.N, k->kd.q.N, 0, n,
-                       st, ws);
-    HIPCHK(hipGetLastError());
+    launch((k_dec_pmd_pow<37>), dim3(pow_blocks, 2), dim3(128), s, k->kd, k->kd.p.N, k->kd.q.N, 0, n, st, ws);
   }
-  hipLaunchKernelGGL((k_dec_pmd_out<MP2, 37>), g1, dim3(128), 0, s, k->kd, k->kd.p.N, k->kd.q.N, k->kd.p2.N,
-                     k->kd.q2.N, n, st, (int)MP2::S4, xrows);
-  HIPCHK(hipGetLastError());
-  ws_free(ws, s);
-  ws_free(st, s);
+  launch((k_dec_pmd_out<MP2, 37>), g1, dim3(128), s, k->kd, k->kd.p.N, k->kd.q.N, k->kd.p2.N, k->kd.q2.N, n, st,
+         (int)MP2::S4, xrows);
 }
-#endif
 
-#if XHE_PMDX
 // $XHE_DEC_PMDX=0: the Montgomery decrypt shapes instead (A/B measurement)
 bool dec_pmdx_on() {
-  static const bool on = [] {
-    const char* e = getenv("XHE_DEC_PMDX");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("XHE_DEC_PMDX");
   return on;
 }
 
@@ -2057,43 +1954,28 @@ void dec_pmdx_launch(const xhe_key* k, const uint32_t* ct, int64_t n, int64_t ch
   constexpr int GPB = 128 / DP::TPI;
   const int pow_blocks = (int)std::min<int64_t>((chunk + GPB - 1) / GPB, 1024);
   const int64_t gs = (int64_t)pow_blocks * GPB;
-  uint32_t *words = nullptr, *scr = nullptr;
-  uint2 *st = nullptr, *tab = nullptr;
-  ws_alloc((void**)&words, (size_t)2 * chunk * RW * sizeof(uint32_t), s);
-  ws_alloc((void**)&scr, (size_t)2 * SCR * chunk * sizeof(uint32_t), s);
-  ws_alloc((void**)&st, (size_t)2 * DP::K * chunk * sizeof(uint2), s);
-  ws_alloc((void**)&tab, (size_t)2 * 16 * DP::K * gs * sizeof(uint2), s);
-  hipLaunchKernelGGL((k_p2_reduce_words<MP2L, RW>), dim3((unsigned)((n * MP2L::TPI + 255) / 256), 2), dim3(256), 0, s,
-                     k->kd, ct, n, scr, words);
-  HIPCHK(hipGetLastError());
+  WsScope wsc(s);
+  uint32_t* words = wsc.get<uint32_t>((size_t)2 * chunk * RW * sizeof(uint32_t));
+  uint32_t* scr = wsc.get<uint32_t>((size_t)2 * SCR * chunk * sizeof(uint32_t));
+  uint2* st = wsc.get<uint2>((size_t)2 * DP::K * chunk * sizeof(uint2));
+  uint2* tab = wsc.get<uint2>((size_t)2 * 16 * DP::K * gs * sizeof(uint2));
+  launch((k_p2_reduce_words<MP2L, RW>), dim3((unsigned)((n * MP2L::TPI + 255) / 256), 2), dim3(256), s, k->kd, ct, n,
+         scr, words);
   const dim3 go((unsigned)((n * DO::TPI + 127) / 128), 2);
-  hipLaunchKernelGGL((k_dec_pmdx_in<DO, RW>), go, dim3(128), 0, s, k->kd, words, n, st);
-  HIPCHK(hipGetLastError());
+  launch((k_dec_pmdx_in<DO, RW>), go, dim3(128), s, k->kd, words, n, st);
   {
     ProfScope ps("k_dec_pow", s);
     const int pb = (int)std::min<int64_t>((n + GPB - 1) / GPB, pow_blocks);
-    hipLaunchKernelGGL(k_dec_pmdx_pow<DP>, dim3(pb, 2), dim3(128), 0, s, k->kd, n, st, tab);
-    HIPCHK(hipGetLastError());
+    launch(k_dec_pmdx_pow<DP>, dim3(pb, 2), dim3(128), s, k->kd, n, st, tab);
   }
-  hipLaunchKernelGGL((k_dec_pmdx_out<DO, NWH>), go, dim3(128), 0, s, k->kd, n, st, scr, words);
-  HIPCHK(hipGetLastError());
-  hipLaunchKernelGGL(k_words_to_rows<MP>, dim3((unsigned)((n * MP::TPI + 255) / 256), 2), dim3(256), 0, s, words,
-                     NWH, n, mrows);
-  HIPCHK(hipGetLastError());
-  ws_free(words, s);
-  ws_free(scr, s);
-  ws_free(st, s);
-  ws_free(tab, s);
+  launch((k_dec_pmdx_out<DO, NWH>), go, dim3(128), s, k->kd, n, st, scr, words);
+  launch(k_words_to_rows<MP>, dim3((unsigned)((n * MP::TPI + 255) / 256), 2), dim3(256), s, words, NWH, n, mrows);
 }
-#endif
 
 // $XHE_DEC_RNS=0: the small-batch 2048-bit decrypt on k_dec_wave (the
 // WaveMont product) instead of k_dec_rns (A/B measurement)
 bool dec_rns_on() {
-  static const bool on = [] {
-    const char* e = getenv("XHE_DEC_RNS");
-    return !(e && e[0] == '0');
-  }();
+  static const bool on = env_on("XHE_DEC_RNS");
   return on;
 }
 
@@ -2112,55 +1994,41 @@ void decrypt_impl(const xhe_key* k, const uint32_t* ct, int64_t count, uint32_t*
                       : (count <= kDecQuadMax || MP2::TPI > 1) ? 4
                                                                    : 1;
   int64_t chunk = std::min<int64_t>(count, kChunk);
-  uint32_t *xrows = nullptr, *mrows = nullptr;
-  ws_alloc((void**)&xrows, (size_t)2 * MP2::S4 * chunk * sizeof(uint32_t), s);
-  ws_alloc((void**)&mrows, (size_t)2 * 2 * MP::S4 * chunk * sizeof(uint32_t), s);
+  WsScope wsc(s);
+  uint32_t* xrows = wsc.get<uint32_t>((size_t)2 * MP2::S4 * chunk * sizeof(uint32_t));
+  uint32_t* mrows = wsc.get<uint32_t>((size_t)2 * 2 * MP::S4 * chunk * sizeof(uint32_t));
   for (int64_t off = 0; off < count; off += chunk) {
     int64_t n = std::min(chunk, count - off);
     const uint32_t* cto = ct + (size_t)off * k->n2w;
-#if XHE_PMDX
     if constexpr (Sh::K == 3072 || Sh::K == 4096 || Sh::K == 8192) {
       if (k->kd.pmdx_dec && dec_pmdx_on() && (pin ? pin == 1 : tpi == 4)) {
         // batches: digits (the 16-lane shape keeps the small ones)
         dec_pmdx_launch<Sh>(k, cto, n, chunk, mrows, s);
         const int cblocks = (int)((n * MP::TPI + 255) / 256);
-        hipLaunchKernelGGL(k_crt_dec<MP>, dim3(cblocks), dim3(256), 0, s, k->kd, k->kd.p.N, n, mrows,
-                           m + (size_t)off * k->nw);
-        HIPCHK(hipGetLastError());
+        launch(k_crt_dec<MP>, dim3(cblocks), dim3(256), s, k->kd, k->kd.p.N, n, mrows, m + (size_t)off * k->nw);
         continue;
       }
     }
-#endif
     if (tpi == 64) {
       if constexpr (wave_ok) {
         static_assert(MP2::S == 74 && MP2::W == 28, "k_dec_wave / k_dec_rns share the MP2 limbs");
         if (k->kd.rns && dec_rns_on()) {
           ProfScope ps("k_dec_rns", s);
-          hipLaunchKernelGGL(k_dec_rns, dim3((unsigned)n, 2), dim3(rns::NT), 0, s, k->kd, cto, n, (int)MP2::S4, xrows);
-          HIPCHK(hipGetLastError());
+          launch(k_dec_rns, dim3((unsigned)n, 2), dim3(rns::NT), s, k->kd, cto, n, (int)MP2::S4, xrows);
         } else {
           ProfScope ps("k_dec_wave", s);
-          hipLaunchKernelGGL((k_dec_wave<74, XHE_DEC_NWV>), dim3((unsigned)n, 2), dim3(64 * XHE_DEC_NWV), 0, s, k->kd,
-                             cto, n, (int)MP2::S4, xrows);
-          HIPCHK(hipGetLastError());
+          launch((k_dec_wave<74, XHE_DEC_NWV>), dim3((unsigned)n, 2), dim3(64 * XHE_DEC_NWV), s, k->kd, cto, n,
+                 (int)MP2::S4, xrows);
         }
       }
     } else if (tpi == 16) dec_pow_launch<typename Sh::MP2X, 2, MP2>(k, cto, n, chunk, xrows, s);
     else if (tpi == 4) dec_pow_launch<typename Sh::MP2L, 1, MP2>(k, cto, n, chunk, xrows, s);
-#if XHE_PMD && XHE_LDS_ROWS
     else if constexpr (Sh::K == 2048) dec_pmd_launch<MP2>(k, cto, n, chunk, xrows, s);
-#endif
     else dec_pow_launch<MP2, 0, MP2>(k, cto, n, chunk, xrows, s);
     int blocks = (int)((n * MP::TPI + 255) / 256);
-    hipLaunchKernelGGL((k_dec_fin<MP2, MP>), dim3(blocks, 2), dim3(256), 0, s, k->kd, k->kd.p.N, k->kd.q.N, n,
-                       xrows, mrows);
-    HIPCHK(hipGetLastError());
-    hipLaunchKernelGGL(k_crt_dec<MP>, dim3(blocks), dim3(256), 0, s, k->kd, k->kd.p.N, n, mrows,
-                       m + (size_t)off * k->nw);
-    HIPCHK(hipGetLastError());
+    launch((k_dec_fin<MP2, MP>), dim3(blocks, 2), dim3(256), s, k->kd, k->kd.p.N, k->kd.q.N, n, xrows, mrows);
+    launch(k_crt_dec<MP>, dim3(blocks), dim3(256), s, k->kd, k->kd.p.N, n, mrows, m + (size_t)off * k->nw);
   }
-  ws_free(xrows, s);
-  ws_free(mrows, s);
 }
 
 template <class F>
@@ -2197,13 +2065,6 @@ int xhe_segprod(const xhe_key* key, const uint32_t* c_dev, const int32_t* d_dev,
 }
 
 namespace {
-struct DevBuf {
-  void* p = nullptr;
-  DevBuf(size_t bytes, hipStream_t s) { HIPCHK(hipMallocAsync(&p, std::max<size_t>(bytes, 4), s)); }
-  ~DevBuf() { (void)hipFree(p); }
-  template <class T>
-  T* as() const { return (T*)p; }
-};
 struct Stream {
   hipStream_t s = nullptr;
   Stream() { HIPCHK(hipStreamCreateWithFlags(&s, hipStreamNonBlocking)); }
@@ -2226,9 +2087,8 @@ int mulmod_gap_fix(const xhe_key* k, const uint32_t* a, const int32_t* ea, const
                    int64_t count, uint32_t* out, hipStream_t s) {
   const size_t cb = (size_t)k->n2w * 4;
   DevBuf x(count * cb, s), kx((size_t)count * k->nw * 4, s), z(count * cb, s), zi(count * cb, s), t(count * cb, s);
-  hipLaunchKernelGGL(k_gap_pick, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, s, k->kd, a, ea, b, eb, count,
-                     k->dneg, x.as<uint32_t>(), kx.as<uint32_t>());
-  HIPCHK(hipGetLastError());
+  launch(k_gap_pick, dim3((unsigned)((count + 255) / 256)), dim3(256), s, k->kd, a, ea, b, eb, count, k->dneg,
+         x.as<uint32_t>(), kx.as<uint32_t>());
   powmod_impl<Sh, MN2>(k, x.as<uint32_t>(), kx.as<uint32_t>(), k->nw, k->n_bits, count, z.as<uint32_t>(), s);
   const int rc = invert_impl<Sh, MN2>(k, z.as<uint32_t>(), count, zi.as<uint32_t>(), s);
   if (rc != XHE_OK) return rc;
@@ -2329,10 +2189,7 @@ struct HostPart {
 // Elements per chunk of the host-buffer pipelines for the encryption kernels
 // ($XHE_HOST_CHUNK overrides, for A/B runs).
 int64_t host_chunk(int64_t dflt) {
-  static const int64_t v = [] {
-    const char* e = getenv("XHE_HOST_CHUNK");
-    return e ? std::max<int64_t>(1024, atoll(e)) : (int64_t)0;
-  }();
+  static const int64_t v = env_str("XHE_HOST_CHUNK") ? std::max<int64_t>(1024, env_int("XHE_HOST_CHUNK", 0)) : 0;
   return v ? v : dflt;
 }
 
@@ -2361,12 +2218,12 @@ template <class Run>
 int host_pipeline(const xhe_key* key, int64_t count, int64_t chunk, const std::vector<HostPart>& in,
                   const std::vector<HostPart>& out, Run&& run) {
   if (count <= 0) return XHE_OK;
-  static const bool trace = getenv("XHE_HOST_TRACE") != nullptr;  // per-chunk timings to stderr
+  static const bool trace = env_str("XHE_HOST_TRACE") != nullptr;  // per-chunk timings to stderr
   // Kernels of consecutive chunks run one after another ($XHE_HOST_OVERLAP
   // lets them overlap instead: then the three streams' chunks advance in
   // lockstep - each one's small kernels wait for CU slots behind the others'
   // big ones - and the copy-out comes in bursts; 17.6-18.8 vs 19.5-20.4 M/s).
-  static const bool serial = getenv("XHE_HOST_OVERLAP") == nullptr;
+  static const bool serial = env_str("XHE_HOST_OVERLAP") == nullptr;
   chunk = std::max<int64_t>(1, std::min(chunk, count));
   const int64_t nch = (count + chunk - 1) / chunk;
   const int D = (int)std::min<int64_t>(nch, 3);
@@ -2406,9 +2263,8 @@ int host_pipeline(const xhe_key* key, int64_t count, int64_t chunk, const std::v
   // test hook: run() of this chunk fails (error-path tests). Armed only when
   // XHE_TEST_HOOKS=1 is set as well, so a stray variable cannot fail a call.
   static const int64_t fail_chunk = [] {
-    const char* on = getenv("XHE_TEST_HOOKS");
-    const char* e = getenv("XHE_TEST_FAIL_CHUNK");
-    return (on && on[0] == '1' && e) ? (int64_t)atoll(e) : (int64_t)-1;
+    const char* on = env_str("XHE_TEST_HOOKS");
+    return (on && on[0] == '1') ? env_int("XHE_TEST_FAIL_CHUNK", -1) : (int64_t)-1;
   }();
   auto dptr = [&](int b, int k) { return dev[(size_t)b * parts.size() + k]->p; };
   auto enqueue = [&](int64_t c) -> int {
@@ -2502,14 +2358,13 @@ void rand_impl(const xhe_key* key, const uint8_t* seed32, uint64_t nonce, int64_
     int tpe = 1;
     while (tpe < (key->rand_words + 15) / 16) tpe <<= 1;
     int blocks = (int)((count * tpe + 255) / 256);
-    hipLaunchKernelGGL(k_rand_djn, dim3(blocks), dim3(256), 0, s, ck, base, count, key->rand_words, key->rand_bits,
-                       tpe, rand_dev, status_dev);
+    launch(k_rand_djn, dim3(blocks), dim3(256), s, ck, base, count, key->rand_words, key->rand_bits, tpe, rand_dev,
+           status_dev);
   } else {
     int blocks = (int)((count + 255) / 256);
-    hipLaunchKernelGGL(k_rand_below, dim3(blocks), dim3(256), 0, s, ck, base, count, key->rand_words,
-                       key->rand_bits, key->kd.n_words, rand_dev, status_dev);
+    launch(k_rand_below, dim3(blocks), dim3(256), s, ck, base, count, key->rand_words, key->rand_bits, key->kd.n_words,
+           rand_dev, status_dev);
   }
-  HIPCHK(hipGetLastError());
 }
 }  // namespace
 
@@ -2570,9 +2425,8 @@ int xhe_row_bits(const uint32_t* words_dev, int64_t count, int n2w, int16_t* bit
     if (count < 0 || n2w <= 0 || n2w > 1023) return fail(XHE_EINVAL, "xhe_row_bits: bad size");
     if (count == 0) return XHE_OK;
     if (!words_dev || !bits_dev) return fail(XHE_EINVAL, "xhe_row_bits: null argument");
-    hipLaunchKernelGGL(k_row_bits, dim3((unsigned)((count + 255) / 256)), dim3(256), 0, (hipStream_t)stream,
-                       words_dev, count, n2w, bits_dev);
-    HIPCHK(hipGetLastError());
+    launch(k_row_bits, dim3((unsigned)((count + 255) / 256)), dim3(256), (hipStream_t)stream, words_dev, count, n2w,
+           bits_dev);
     return XHE_OK;
   });
 }
@@ -2586,7 +2440,7 @@ int xhe_key_create(int device, int key_bits, const uint32_t* n_words, const uint
       return fail(XHE_ENOTSUP, "xhe_key_create: key_bits must be 2048, 3072, 4096 or 8192");
     if ((p_words == nullptr) != (q_words == nullptr)) return fail(XHE_EINVAL, "xhe_key_create: need both p and q");
     if (win_bits == 0) {
-      const char* ev = getenv("XHE_WIN_BITS");  // "23" or "23s" (split layout), as _native.parse_win
+      const char* ev = env_str("XHE_WIN_BITS");  // "23" or "23s" (split layout), as _native.parse_win
       win_bits = ev ? atoi(ev) : 16;
       if (ev && win_bits > 0 && ev[strlen(ev) - 1] == 's') win_bits |= XHE_WIN_SPLIT;
     }
@@ -2671,9 +2525,8 @@ int xhe_encode_f64(const xhe_key* key, const double* x_dev, int64_t count, int p
     // -ceil(log2(10) * precision) (encoder.py:39), computed exactly as Python does in float64
     int e0 = precision < 0 ? 0 : -(int)std::ceil(std::log2(10.0) * (double)precision);
     int blocks = (int)((count * (key->nw / 4) + 255) / 256);  // one thread per 16-byte quad of m
-    hipLaunchKernelGGL(k_encode_f64, dim3(blocks), dim3(256), 0, (hipStream_t)stream, x_dev, count, mode, e0,
-                       has_max, max_exponent, key->kd.n_words, key->nw, m_dev, exp_dev, status_dev);
-    HIPCHK(hipGetLastError());
+    launch(k_encode_f64, dim3(blocks), dim3(256), (hipStream_t)stream, x_dev, count, mode, e0, has_max, max_exponent,
+           key->kd.n_words, key->nw, m_dev, exp_dev, status_dev);
     return XHE_OK;
   });
 }
@@ -2730,9 +2583,8 @@ int xhe_decode(const xhe_key* key, const uint32_t* m_dev, const int32_t* exp_dev
     if (count <= 0) return XHE_OK;
     DevGuard dg(key->device);
     int blocks = (int)((count + 255) / 256);
-    hipLaunchKernelGGL(k_decode, dim3(blocks), dim3(256), 0, (hipStream_t)stream, m_dev, exp_dev, count, key->kd,
-                       f64_dev, f32_dev, status_dev);
-    HIPCHK(hipGetLastError());
+    launch(k_decode, dim3(blocks), dim3(256), (hipStream_t)stream, m_dev, exp_dev, count, key->kd, f64_dev, f32_dev,
+           status_dev);
     return XHE_OK;
   });
 }
@@ -2751,17 +2603,15 @@ bool pack_geometry_ok(const xhe_key* key, int slots, int interval_bits, int prec
 void embed_launch(const xhe_key* key, const double* cols_dev, int64_t cstride, int ncols, int64_t count,
                   int interval_bits, int precision, uint32_t* m_dev, int32_t* status_dev, hipStream_t s) {
   int blocks = (int)((count * (key->nw / 4) + 255) / 256);  // one thread per 16-byte quad of m
-  hipLaunchKernelGGL(k_embed_f64, dim3(blocks), dim3(256), 0, s, cols_dev, cstride, ncols, count, interval_bits,
-                     precision, key->kd.n_words, key->nw, m_dev, status_dev);
-  HIPCHK(hipGetLastError());
+  launch(k_embed_f64, dim3(blocks), dim3(256), s, cols_dev, cstride, ncols, count, interval_bits, precision,
+         key->kd.n_words, key->nw, m_dev, status_dev);
 }
 
 void umbed_launch(const xhe_key* key, const uint32_t* m_dev, int64_t count, int num, int interval_bits, int precision,
                   double* f64_dev, float* f32_dev, int64_t ostride, int32_t* status_dev, hipStream_t s) {
   int blocks = (int)((count + 255) / 256);
-  hipLaunchKernelGGL(k_umbed, dim3(blocks), dim3(256), 0, s, m_dev, count, num, interval_bits, precision, key->kd,
-                     f64_dev, f32_dev, ostride, status_dev);
-  HIPCHK(hipGetLastError());
+  launch(k_umbed, dim3(blocks), dim3(256), s, m_dev, count, num, interval_bits, precision, key->kd, f64_dev, f32_dev,
+         ostride, status_dev);
 }
 }  // namespace
 
@@ -3153,9 +3003,7 @@ int xhe_gather_rows(const uint32_t* src_dev, const int64_t* idx_dev, int64_t cou
     if (!src_dev || !idx_dev || !dst_dev) return fail(XHE_EINVAL, "xhe_gather_rows: null argument");
     const int64_t tot = count * words;
     const unsigned blocks = (unsigned)std::min<int64_t>((tot + 255) / 256, 65536);
-    hipLaunchKernelGGL(k_move_rows<false>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src_dev, idx_dev, count,
-                       words, dst_dev);
-    HIPCHK(hipGetLastError());
+    launch(k_move_rows<false>, dim3(blocks), dim3(256), (hipStream_t)stream, src_dev, idx_dev, count, words, dst_dev);
     return XHE_OK;
   });
 }
@@ -3168,9 +3016,7 @@ int xhe_scatter_rows(const uint32_t* src_dev, const int64_t* idx_dev, int64_t co
     if (!src_dev || !idx_dev || !dst_dev) return fail(XHE_EINVAL, "xhe_scatter_rows: null argument");
     const int64_t tot = count * words;
     const unsigned blocks = (unsigned)std::min<int64_t>((tot + 255) / 256, 65536);
-    hipLaunchKernelGGL(k_move_rows<true>, dim3(blocks), dim3(256), 0, (hipStream_t)stream, src_dev, idx_dev, count,
-                       words, dst_dev);
-    HIPCHK(hipGetLastError());
+    launch(k_move_rows<true>, dim3(blocks), dim3(256), (hipStream_t)stream, src_dev, idx_dev, count, words, dst_dev);
     return XHE_OK;
   });
 }

@@ -621,7 +621,6 @@ __global__ void __launch_bounds__(256, 2) k_djn_pow_x(KeyDev key, const uint32_t
   M.store_strided_n(b, ws + (size_t)prime * 2 * RS4 * count + e, (int)count, RS4);
 }
 
-#if XHE_LDS_ROWS
 // Variant of k_djn_pow (TPI == 1) with each product's table row moved into
 // LDS in one burst of LDS-DMA instructions (global_load_lds_dwordx4:
 // instruction k moves quad k of every lane's row; image [quad][lane][4
@@ -637,7 +636,7 @@ struct ALdsQ {
 
 // c_P = (1 + n m) h^a mod P^2 for one element and one prime, table rows
 // through the wave's LDS image; written as row `prime` of ws.
-// XHE_DJN_FOLD: the product starts from the first window's row (h_0 R) and
+// The product starts from the first window's row (h_0 R) and
 // (1 + n m) enters once, in plain form, as the last multiplier, so the
 // conversion out of Montgomery form is that same product: nwin + 1 products
 // instead of nwin + 2 ((1 + n m) R first, a final multiply by 1).
@@ -662,7 +661,6 @@ XHE_DEV void djn_prime_lds(const KeyDev& key, const uint32_t* __restrict__ Np, c
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     unpack_limbs_lds<MP2, RW>(img + (threadIdx.x & 63) * 4);
   };
-#if XHE_DJN_FOLD
   (void)nR2;
   stage(0);
 #pragma unroll
@@ -683,17 +681,6 @@ XHE_DEV void djn_prime_lds(const KeyDev& key, const uint32_t* __restrict__ Np, c
   M.mul(b, ARow{nR});  // n m mod P^2 (< 2 P^2), plain
   b[0] += 1u;          // 1 + n m: one limb may reach 2^W, inside the lazy-carry bound
   M.mul(b, ALdsQ{mine});  // (1 + n m) h^a mod P^2
-#else
-  (void)nR;
-  M.load_words(b, m_words + (size_t)e * key.nw, key.nw);
-  M.mul(b, ARow{nR2});     // n m R mod P^2
-  M.add_row(b, md.R1);     // (1 + n m) R
-  for (int w = 0; w < key.nwin; ++w) {
-    stage(w);
-    M.mul(b, ALdsQ{mine});
-  }
-  M.mul(b, AOne{});
-#endif
   M.reduce_once(b);
   M.store_strided(b, ws + (size_t)prime * 2 * MP2::S4 * count + e, (int)count);
 }
@@ -715,9 +702,6 @@ __global__ void __launch_bounds__(128, 2) k_djn_pow_lds(KeyDev key, const uint32
                      prime, img, img + (threadIdx.x & 63) * 4, ws);
 }
 
-#endif
-
-#if XHE_PMD && XHE_LDS_ROWS
 // ---------------------------------------------------------------------------
 // DJN encryption in Montgomery digits (pdigit_dev.hpp PMD; 2048-bit keys,
 // K = 37 limbs of P): c_P = (1 + n m) h^a mod P^2 as k_djn_pow_lds computes
@@ -1487,7 +1471,6 @@ __global__ void __launch_bounds__(256, 2) k_tab_to_pmd(const uint32_t* __restric
         make_uint4(word(f, 4 * q), word(f, 4 * q + 1), word(f, 4 * q + 2), word(f, 4 * q + 3));
   }
 }
-#endif
 
 // c = c_q + q^2 ((c_p + 4p^2 - c_q) (q^2)^-1 mod p^2) for element e (utils.py:38-43)
 // out == nullptr: the 2S result limbs are left in element e's q row of ws
@@ -1719,12 +1702,9 @@ __global__ void __launch_bounds__(256, 2) k_dec_pow(KeyDev key, const uint32_t* 
   uint32_t* tab = ws + (size_t)prime * 17 * rs + gid0;  // rows 0..15
   uint32_t* sq = tab + 16 * rs;
   const int n2w = key.n2w;
-#if XHE_SQ_LDS
+  // the squaring operand of the exponentiation goes through LDS (SqLds)
   __shared__ __attribute__((aligned(16))) uint32_t sq_img[4][SqLds<MP2>::WORDS_PER_WAVE];  // 256-thread blocks
   uint32_t* sq_lds = sq_img[(threadIdx.x >> 6) & 3];
-#else
-  uint32_t* sq_lds = nullptr;
-#endif
   for (int64_t e = gid0; e < count; e += G_total) {
     const uint32_t* cw = c_words + (size_t)e * n2w;
     MP2 M;
@@ -1825,20 +1805,12 @@ __global__ void __launch_bounds__(256, 2) k_crt_dec(KeyDev key, const uint32_t* 
 
 // ============================================================== mod n^2
 // Helpers shared by the n^2 kernels (shape MN2, usually TPI = 4).
-#ifndef XHE_STORE_DIRECT
-#define XHE_STORE_DIRECT 1  // store_packed straight from the registers (Mont::store_words); 0: via the strided row
-#endif
 template <class M_>
 XHE_DEV void store_packed(const M_& M, const uint32_t (&b)[M_::L], uint32_t* row, int st, uint32_t* out, int nwords) {
-#if XHE_STORE_DIRECT
+  // straight from the registers (Mont::store_words), not via the strided row
   (void)row;
   (void)st;
   M.store_words(b, out, nwords);
-#else
-  M.store_strided(b, row, st);
-  wave_sync_mem_();
-  pack_words_<M_::W, M_::TPI>(row, st, M_::S, out, nwords);
-#endif
 }
 
 // 4-bit fixed-window power of the Montgomery residue in b. Digits come from
@@ -1973,12 +1945,9 @@ __global__ void __launch_bounds__(256, 2) k_powmod_n2(KeyDev key, const uint32_t
   uint32_t* tab = ws + gid0;
   uint32_t* sq = tab + 16 * rs;
   const int nwin = kbits <= 0 ? 1 : (kbits + 3) / 4;
-#if XHE_SQ_LDS
+  // the squaring operand of the exponentiation goes through LDS (SqLds)
   __shared__ __attribute__((aligned(16))) uint32_t sq_img[4][SqLds<MN2>::WORDS_PER_WAVE];  // 256-thread blocks
   uint32_t* sq_lds = sq_img[(threadIdx.x >> 6) & 3];
-#else
-  uint32_t* sq_lds = nullptr;
-#endif
   for (int64_t e = gid0; e < count; e += G_total) {
     MN2 M;
     M.init(Nn2, n2dev<MN2>(key).n0inv);
@@ -2019,7 +1988,6 @@ __global__ void __launch_bounds__(256, 2) k_djn_pub(KeyDev key, const uint32_t* 
   store_packed(M, b, ws + e, (int)count, out + (size_t)e * key.n2w, key.n2w);
 }
 
-#if XHE_NDIG
 // Public-key DJN encryption in Montgomery digits of n (2048 bits; the tables
 // rewritten as canonical digit pairs by k_tab_to_pmdx at key creation): the
 // first window's row is the start state, every further row is unpacked into
@@ -2060,7 +2028,6 @@ __global__ void __launch_bounds__(128, 2) k_djn_pub_nd(KeyDev key, const uint32_
   }
   ndig_st_store<D>(a, c, st, count, e);
 }
-#endif
 
 // Non-DJN obfuscation, variable base r with a uniform exponent:
 //   public  (paillier.py:228-230): (1 + n m) r^n mod n^2          -> out words
@@ -2098,12 +2065,9 @@ __global__ void __launch_bounds__(256, 2) k_nodjn_pub(KeyDev key, const uint32_t
   const int st = (int)G_total;
   const size_t rs = (size_t)MN2::S4 * st;
   uint32_t* tab = ws + gid0;
-#if XHE_SQ_LDS
+  // the squaring operand of the exponentiation goes through LDS (SqLds)
   __shared__ __attribute__((aligned(16))) uint32_t sq_img[4][SqLds<MN2>::WORDS_PER_WAVE];  // 256-thread blocks
   uint32_t* sq_lds = sq_img[(threadIdx.x >> 6) & 3];
-#else
-  uint32_t* sq_lds = nullptr;
-#endif
   for (int64_t e = gid0; e < count; e += G_total) {
     MN2 M;
     M.init(Nn2, key.n2.n0inv);
@@ -2114,7 +2078,6 @@ __global__ void __launch_bounds__(256, 2) k_nodjn_pub(KeyDev key, const uint32_t
   }
 }
 
-#if XHE_NDIG
 // ---------------------------------------------------------------------------
 // Variable-base exponentiations mod n^2 in Montgomery digits (PMDX, 4 lanes
 // per element, 2048-bit keys): 4 K^2 mads per squaring and 5 K^2 per product
@@ -2248,7 +2211,6 @@ __global__ void __launch_bounds__(128, 2) k_ndig_out(KeyDev key, const uint2* __
   wave_sync_mem_();
   X.M.wide_mul_add_store(y1, ARow{key.nd.N}, rows, cnt, out + (size_t)e * key.n2w, key.n2w);
 }
-#endif
 
 // SHAPE 0: the batch shape (key.p2/q2); 1: the 4-lane shape (key.p2L/q2L),
 // for key sizes whose batch shape spills in this exponentiation (3072 bits:
@@ -2267,12 +2229,9 @@ __global__ void __launch_bounds__(256, 2) k_nodjn_crt(KeyDev key, const uint32_t
   const int st = (int)G_total;
   const size_t rs = (size_t)MP2::S4 * st;
   uint32_t* tab = ws + (size_t)prime * 18 * rs + gid0;
-#if XHE_SQ_LDS
+  // the squaring operand of the exponentiation goes through LDS (SqLds)
   __shared__ __attribute__((aligned(16))) uint32_t sq_img[4][SqLds<MP2>::WORDS_PER_WAVE];  // 256-thread blocks
   uint32_t* sq_lds = sq_img[(threadIdx.x >> 6) & 3];
-#else
-  uint32_t* sq_lds = nullptr;
-#endif
   for (int64_t e = gid0; e < count; e += G_total) {
     MP2 M;
     M.init(prime ? Nq2 : Np2, md.n0inv);
