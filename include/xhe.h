@@ -63,7 +63,13 @@ int xhe_rand(const xhe_key* key, const uint8_t* seed32, uint64_t nonce, int64_t 
              int32_t* status_dev, void* stream);
 
 /* Paillier._encrypt_single + PaillierCiphertext.obfuscate (paillier.py:273-287,
- * 189-232): ct = (1 + n*m) * X mod n^2 with X from rand (NULL = no obfuscation). */
+ * 189-232): ct = (1 + n*m) * X mod n^2 with X from rand (NULL = no obfuscation).
+ * The kernel shape follows the key and the batch size. A public non-DJN
+ * 2048-bit key (X = r^n mod n^2, the obfuscator of a party that received the
+ * key: linear_regression/trainer.py:145-154,197-200) runs one 1,024-thread
+ * block per element up to 2,048 elements (6.7 ms for up to 256 elements) and
+ * the 4-lane Montgomery-digit kernels beyond (48 ms for any batch up to 8 k);
+ * $XHE_PUB_TPI = 64 or 4 pins one of the two. */
 int xhe_encrypt(const xhe_key* key, const uint32_t* m_dev, const uint32_t* rand_dev, int64_t count,
                 uint32_t* ct_dev, void* stream);
 

@@ -646,6 +646,111 @@ XHE_DEV void wave_words_out(uint32_t* x, const uint32_t* zn, int nwords, uint32_
   }
 }
 
+// ---------------------------------------------------------------------------
+// Public non-DJN encryption of a few elements (2048-bit keys; the regression
+// operators' Paillier.encrypt(public_context, ...) of B, 1 or D elements):
+// ct = (1 + n m) r^n mod n^2, one element per block of NWV waves. The 4-lane
+// digit kernels (k_ndig_pow_n) give a small batch the latency of a full one;
+// here r^n is a chain of ~2,400 WaveMont products mod n^2 (154 limbs of 27
+// bits, as k_mexp_horner_wave), k_dec_wave's schedule: 16 odd powers in LDS,
+// a wave-uniform 5-bit sliding window over n from its top set bit, one
+// product site.
+//   c0 = 1 + n m      plain column product (76 x 76 limbs, < n^2: no
+//                     reduction), normalised to limbs <= MASK + 2
+//   x  = MontW(r, R_w^2) = r R_w, then x^n in wave form
+//   ct = MontW(x^n R_w, c0) = r^n (1 + n m)   out of Montgomery form and the
+//        plaintext folded in by the same product (as k_nodjn_pmd_out), < 2 n^2
+// normalised, reduced once and packed to n2w words by one thread. r: rw words
+// (< n), m: nw words (< n) per element.
+template <int K, int NWV>
+__global__ void __launch_bounds__(64 * NWV) k_nodjn_pub_wave(KeyDev key, const uint32_t* __restrict__ m_words,
+                                                             const uint32_t* __restrict__ r_words, int rw,
+                                                             int64_t count, uint32_t* __restrict__ out) {
+  using WM = WaveMont<K, NWV, 27>;
+  __shared__ __attribute__((aligned(16))) typename WM::Lds s;
+  const int64_t e = blockIdx.x;
+  if (e >= count) return;
+  const uint32_t* ex = key.n_words;
+  const int ebits = key.n_bits;
+  wave_init_n2<WM>(s, key);  // everything zero, then n^2 and -n^-2
+  // c0: n's limbs as the multiplicand (zb is free until r R_w), m's as the
+  // a-operand, the 1 already in column 0 of the zeroed columns
+  wave_limbs_in<WM>(m_words + (size_t)e * key.nw, key.nw, s.mq);
+  wave_limbs_in<WM>(ex, key.nw, s.zb + WM::ZO);
+  wave_limbs_in<WM>(r_words + (size_t)e * rw, rw, s.tl);
+  for (int j = WM::tid(); j < (ebits + 31) / 32 && j < 64; j += WM::NT) s.exw[j] = ex[j];
+  if (WM::tid() == 0) s.col[0][WM::G] = 1ull;
+  WM::sync();
+  WM::template prodq<false>(s.mq, s.zb, s.col[0]);
+  WM::norm_low(s.col[0], s.r3);  // c0 < n^2 < R_w: nothing crosses limb K - 1
+  for (int j = WM::tid(); j < K; j += WM::NT) s.zb[WM::ZO + j] = key.n2w_R2[j];
+  WM::sync();
+  int cur = 0;  // the first product writes col[1] (still zero) and zeroes col[0]
+  WM::mul(s, cur, s.tl, s.x, true);  // r R_w
+
+  // exponent bits k in (32 (wi - 1), 32 wi + 31] from two words (wi = i >> 5)
+  auto bits64 = [&](int i, int& base) {
+    const int wi = i >> 5;
+    base = (wi - 1) * 32;
+    return ((uint64_t)s.exw[wi] << 32) | (wi > 0 ? s.exw[wi - 1] : 0u);
+  };
+  int i = ebits - 1;
+  while (i >= 0 && !((ex[i >> 5] >> (i & 31)) & 1u)) --i;
+  int step = 1, pend_sq = 0, pend_mul = -1;
+#pragma unroll 1
+  while (true) {
+    const uint32_t* a;
+    uint32_t* dst = s.x;
+    bool zbw = true;
+    if (step == 1) {  // tab[0] = x; x = zb = x^2
+      WM::copy_in(s.tab[0], s.x, K);
+      WM::sync();
+      a = s.x;
+      step = 2;
+    } else if (step < 17) {  // tab[t] = tab[t-1] x^2 (x^2 stays in zb)
+      a = s.tab[step - 2];
+      dst = s.tab[step - 1];
+      zbw = false;
+      ++step;
+    } else if (pend_sq > 0) {
+      a = s.x;
+      --pend_sq;
+    } else if (pend_mul >= 0) {
+      a = s.tab[pend_mul];
+      pend_mul = -1;
+    } else if (i >= 0) {
+      int base;
+      const uint64_t v = bits64(i, base);
+      auto bit = [&](int k) { return (uint32_t)(v >> (k - base)) & 1u; };
+      if (step == 17 || bit(i)) {  // a window [i..j] ending in a set bit
+        int j = i - 4 < 0 ? 0 : i - 4;
+        while (!bit(j)) ++j;
+        uint32_t val = 0;
+        for (int k = i; k >= j; --k) val = (val << 1) | bit(k);
+        if (step == 17) {  // the first window's odd power is the start value
+          WM::copy_in(s.x, s.tab[val >> 1], K);
+          WM::copy_in(s.zb + WM::ZO, s.tab[val >> 1], K);
+          WM::sync();
+          step = 18;
+        } else {
+          pend_sq = i - j + 1;
+          pend_mul = (int)(val >> 1);
+        }
+        i = j - 1;
+      } else {
+        pend_sq = 1;
+        --i;
+      }
+      continue;
+    } else {
+      break;
+    }
+    WM::mul(s, cur, a, dst, zbw);
+  }
+  WM::mul(s, cur, s.r3, s.x, false);  // (zb = x^n R_w) c0 / R_w: plain, < 2 n^2
+  wave_words_out<WM>(s.x, s.zn, key.n2w, out + (size_t)e * key.n2w);
+}
+
 // mode 0: node[e] = words[e] R_w (MontW(x, R_w^2)); mode 1: root words
 // (plain inverse from the host) -> inv node, the same conversion
 template <int K, int NWV>

@@ -1372,12 +1372,32 @@ void encrypt_nodjn_pmd(const xhe_key* k, const uint32_t* m, const uint32_t* r, i
   }
 }
 
+// Public non-DJN encryption of 2048-bit keys by batch size: one 16-wave block
+// per element (k_nodjn_pub_wave) up to kPubWaveMax elements - the 4-lane digit
+// kernels take the same time for 1 element as for 8 k (one wave's chain of
+// products: 47.4 ms at 15, 48.9 ms at 8 k) - and the digit kernels beyond
+// (tools/dec_shapes.py --pub, profiles/r9/pub_small/: 6.7 ms up to 256
+// elements, one block a CU; 20.8 ms at 1 k, 40.4 vs 48.7 ms at 2 k, 79.6 vs
+// 48.9 ms at 4 k). $XHE_PUB_TPI (64 or 4) pins one path (A/B measurement).
+// Mirrored as xfl_amd._native.PUB_WAVE_MAX.
+constexpr int64_t kPubWaveMax = 2048;
+bool pub_wave(int64_t count) {
+  static const int pin = (int)env_int("XHE_PUB_TPI", 0);
+  return pin == 4 || pin == 64 ? pin == 64 : count <= kPubWaveMax;
+}
+
 template <class Sh>
 void encrypt_nodjn_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r, int64_t count, uint32_t* ct,
                         hipStream_t s) {
   if constexpr (Sh::K == 2048) {
     if (k->priv && nodjn_pmd_on()) {
       encrypt_nodjn_pmd<Sh>(k, m, r, count, ct, s);
+      return;
+    }
+    if (!k->priv && pub_wave(count)) {
+      // (a pinned large batch: grid.x holds it, a block per element)
+      ProfScope ps("k_nodjn_pub_wave", s);
+      launch((k_nodjn_pub_wave<154, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, m, r, k->rand_words, count, ct);
       return;
     }
   }

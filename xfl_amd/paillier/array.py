@@ -1223,71 +1223,112 @@ def _f_transpose(a, axes=None):
 
 # ------------------------------------------------------------ matmul
 def _matmul(a, b):
-    """enc[B] @ X[B, D] (logistic_regression/trainer.py:166) and X[D, B] @
-    enc[B]: per output j the multi-exponentiation prod_i base_i^(k'_ij *
-    2^(d_ij)) with base_i = c_i or c_i^-1 (negative scalars) and d_ij aligning
-    e_i + e_kij to the column minimum = the reference's object-dtype dot
-    product (a fold of __mul__ + __add__) bit for bit."""
+    """enc @ X and X @ enc for one ciphertext operand of one or two
+    dimensions: enc[B] @ X[B, D] (logistic_regression/trainer.py:166), X[D, B]
+    @ enc[B], enc[M, B] @ X[B, D] (the regression operators' enc_d.reshape(1,
+    B) @ X, linear_regression/trainer.py:207) and X[M, B] @ enc[B, D]. Per
+    output (m, j) the multi-exponentiation prod_i base_i^(k'_i * 2^(d_i)) with
+    base_i = c_i or c_i^-1 (negative scalars) and d_i aligning e_i + e_ki to
+    the output's minimum = the reference's object-dtype dot product (a fold
+    of __mul__ + __add__) bit for bit; every output in one xhe_multiexp call."""
     ca, cb = _as_cipher(a), _as_cipher(b)
     if ca is not None and cb is not None:
         raise TypeError("Cannot multiply one ciphertext with another ciphertext, try multiply a scalar.")
-    if ca is not None:
-        X = _as_plain(b)
-        if X is None or ca.ndim != 1 or np.ndim(X) != 2 or X.shape[0] != ca.shape[0] or ca.size == 0:
-            raise _Fallback()
-        return _matvec(ca, X)
-    if cb is not None:
-        X = _as_plain(a)
-        if X is None or cb.ndim != 1 or np.ndim(X) != 2 or X.shape[1] != cb.shape[0] or cb.size == 0:
-            raise _Fallback()
-        return _matvec(cb, np.asarray(X).T)
-    raise _Fallback()
+    if ca is None and cb is None:
+        raise _Fallback()
+    C, left = (ca, True) if ca is not None else (cb, False)
+    X = _as_plain(b if left else a)
+    if X is None or C.size == 0:
+        raise _Fallback()
+    X = np.asarray(X)
+    cs, xs = C.shape, X.shape
+    if not (1 <= len(cs) <= 2 and 1 <= len(xs) <= 2 and len(cs) + len(xs) >= 3):
+        raise _Fallback()  # (1-D @ 1-D gives a scalar, stacks of matrices: the object loop)
+    # as numpy: a 1-D operand is a row on the left, a column on the right,
+    # and its axis leaves the result
+    if left:
+        cs2, xs2 = (cs if len(cs) == 2 else (1, cs[0])), (xs if len(xs) == 2 else (xs[0], 1))
+        out_shape = (cs[:-1] if len(cs) == 2 else ()) + (xs[1:] if len(xs) == 2 else ())
+    else:
+        xs2, cs2 = (xs if len(xs) == 2 else (1, xs[0])), (cs if len(cs) == 2 else (cs[0], 1))
+        out_shape = (xs[:-1] if len(xs) == 2 else ()) + (cs[1:] if len(cs) == 2 else ())
+    if ((cs2[1] != xs2[0]) if left else (xs2[1] != cs2[0])) or X.size == 0:
+        raise _Fallback()  # numpy's own shape error / empty result
+    return _matmul_run(C, X, cs2, xs2, left, out_shape)
 
 
-def _matvec(A, X):
+def _matmul_terms(cshape, xshape, left):
+    """(bidx, sidx), both [M * D, B]: the flat ciphertext and scalar index of
+    term i of output (m, j) of enc[M, B] @ X[B, D] (left) or X[M, B] @ enc[B,
+    D], outputs in C order."""
+    if left:
+        (M, Bn), D = cshape, xshape[1]
+    else:
+        (M, Bn), D = xshape, cshape[1]
+    m, j, i = np.meshgrid(np.arange(M, dtype=np.int64), np.arange(D, dtype=np.int64),
+                          np.arange(Bn, dtype=np.int64), indexing="ij")
+    row, col = (m * Bn + i).reshape(M * D, Bn), (i * D + j).reshape(M * D, Bn)
+    return (row, col) if left else (col, row)
+
+
+def _matmul_plan(cexp, neg, e_k, bidx, sidx):
+    """The multi-exponentiation of a ciphertext matmul, in numpy alone (no
+    device): cexp[nb] the ciphertexts' exponents, neg[ns] / e_k[ns] the sign
+    and exponent of every encoded scalar, bidx / sidx [ncols, nterms] as
+    _matmul_terms gives them. Returns
+      need_inv  the ciphertexts (ascending) some negative scalar multiplies:
+                base nb + t is the inverse of ciphertext need_inv[t]
+      idx       int32 [ncols, nterms]: the base of every term
+      shift     int64 [ncols, nterms]: e_i + e_k - emin, the term's exponent is
+                |k| << shift
+      emin      int64 [ncols]: the outputs' exponents
+    """
+    cexp = np.asarray(cexp, dtype=np.int64)
+    nb = cexp.shape[0]
+    ex = cexp[bidx] + np.asarray(e_k, dtype=np.int64)[sidx]
+    emin = ex.min(axis=1)
+    negt = np.asarray(neg, dtype=bool)[sidx]
+    used = np.zeros(nb, dtype=bool)
+    used[bidx[negt]] = True
+    need_inv = np.nonzero(used)[0]
+    inv_slot = np.full(nb, -1, dtype=np.int64)
+    inv_slot[need_inv] = nb + np.arange(need_inv.size)
+    idx = np.where(negt, inv_slot[bidx], bidx).astype(np.int32)
+    return need_inv, idx, ex - emin[:, None], emin
+
+
+def _matmul_run(A, X, cshape, xshape, left, out_shape):
     ctx = _ctx_of(A)
     _check_no_na(A)
     A = A._aligned_words(ops.n2w_of(ctx))
-    Bn, D = X.shape
-    cexp = A._e.astype(np.int64)
-    kw_, neg, e_k = _encode_scalars(ctx, np.asarray(X))
+    kw_, neg, e_k = _encode_scalars(ctx, X)
     kvec = kw_.ndim == 1  # int64 |k| from the vectorised encoder
-    ks = None if kvec else nat.words_to_ints(kw_)  # |k_ij|, row-major [B, D]
-    neg = neg.reshape(Bn, D)
-    ex = cexp[:, None] + e_k.reshape(Bn, D)
-    emin = ex.min(axis=0)
-    need_inv = np.nonzero(neg.any(axis=1))[0]
+    bidx, sidx = _matmul_terms(cshape, xshape, left)
+    need_inv, idx, shift, emin = _matmul_plan(A._e, neg, e_k, bidx, sidx)
     dev = _res_dev(ctx, A)
-    inv_slot = np.full(Bn, -1, dtype=np.int64)
     if dev is not None:
         dk = ctx.device_key(dev)
         bases = A._dw(dev)
         if need_inv.size:
-            inv = resident.invert(dk, resident.take(bases, need_inv))
-            inv_slot[need_inv] = Bn + np.arange(need_inv.size)
-            bases = resident.cat([bases, inv])
+            bases = resident.cat([bases, resident.invert(dk, resident.take(bases, need_inv))])
     else:
         bases = A._w
         if need_inv.size:
             one = np.zeros((need_inv.size, 1), dtype=np.uint32)
             one[:, 0] = 1
-            inv = ops.powmod_words(ctx, A._w[need_inv], one, 1, invert_first=True)
-            inv_slot[need_inv] = Bn + np.arange(need_inv.size)
-            bases = np.concatenate([A._w, inv])
-    rows = np.arange(Bn, dtype=np.int64)
-    idx = np.where(neg, inv_slot[:, None], rows[:, None]).T.astype(np.int32)  # [D, B]
-    shift = (ex - emin[None, :]).T  # [D, B]
+            bases = np.concatenate([A._w, ops.powmod_words(ctx, A._w[need_inv], one, 1, invert_first=True)])
     if kvec:
-        kwords, kbits = _shifted_words(np.ascontiguousarray(kw_.reshape(Bn, D).T), shift)
+        kwords, kbits = _shifted_words(kw_[sidx], shift)
     else:
-        exps = [ks[i * D + j] << int(shift[j, i]) for j in range(D) for i in range(Bn)]
+        ks = nat.words_to_ints(kw_)  # |k|, flat over X
+        exps = [ks[t] << int(d) for t, d in zip(sidx.reshape(-1), shift.reshape(-1))]
         kbits = max(1, max(k.bit_length() for k in exps))
         kwords = nat.ints_to_words(exps, (kbits + 31) // 32)
     if dev is not None:
         r = resident.multiexp(dk, bases, idx, kwords, kbits)
-        return PaillierArray.from_device(ctx, r, emin.astype(np.int32), (D,))
+        return PaillierArray.from_device(ctx, r, emin.astype(np.int32), out_shape)
     r = ops.multiexp_words(ctx, bases, idx, kwords, kbits)
-    return _result(ctx, r, emin.astype(np.int32), (D,))
+    return _result(ctx, r, emin.astype(np.int32), out_shape)
 
 
 def _shifted_words(k, shift):
