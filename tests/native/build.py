@@ -3,7 +3,9 @@ not the product): mont_selftest (Mont<S, W, TPI> products against host big
 integers for every limb shape) and pdigit_selftest (base-P digit arithmetic
 mod P^2). hipcc cross-compiles for gfx950 without a GPU; the
 binaries land in tests/native/_build (git-ignored, shipped to the GPU box with
-the tree) and are run by tests/test_gpu_native_selftests.py.
+the tree) and are run by tests/test_gpu_native_selftests.py. The host-only
+programs of this folder (host_fuzz.cpp, modinv_host.cpp, keyconst_check.cpp)
+are compiled with g++ by the CPU tests that run them.
 
     python tests/native/build.py
 """

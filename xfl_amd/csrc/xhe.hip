@@ -20,6 +20,7 @@
 #include "../../include/xhe.h"
 #include "abi_common.hpp"
 #include "hostbn.hpp"
+#include "keyconst.hpp"
 #include "xhe_kernels.hpp"
 #include "dec_wave.hpp"
 #include "barrett_dev.hpp"
@@ -152,256 +153,14 @@ decltype(auto) with_shape(int K, F&& f) {
 }
 #endif
 
+// Shapes that only 2048-bit keys have:
+using ND2048 = PMDX<80, 4>;           // Montgomery digits mod n^2 (k_ndig_*, k_djn_pub_nd)
+using WaveN2 = WaveMont<154, 16, 27>;  // one-block products mod n^2 (k_*_wave<WaveN2::K_, 16>)
+
 // $XHE_NDIG_PUB=0: public DJN keys keep Montgomery n^2 tables (k_djn_pub; A/B)
 bool ndig_pub_on() {
   static const bool on = env_on("XHE_NDIG_PUB");
   return on;
-}
-
-struct ModSpec {
-  int S, W;
-  int S4() const { return (S + 3) & ~3; }
-};
-
-// ------------------------------------------------------------------ blob
-struct Blob {
-  std::vector<uint32_t> h;
-  size_t put(const std::vector<uint32_t>& v, size_t min_words = 0) {
-    size_t off = h.size();
-    size_t len = std::max(v.size(), min_words);
-    len = (len + 3) & ~(size_t)3;
-    h.resize(off + len, 0u);
-    std::copy(v.begin(), v.end(), h.begin() + off);
-    return off;
-  }
-  size_t put_limbs(const BigU& x, const ModSpec& s) { return put(x.to_limbs(s.W, s.S), s.S4()); }
-  size_t put_words(const BigU& x, int nw) {
-    std::vector<uint32_t> v(nw);
-    x.to_words(v.data(), nw);
-    return put(v);
-  }
-};
-
-// ---- RNS small-batch decrypt constants (rns_dev.hpp k_dec_rns; checked
-// against tools/rns_model.py, which builds the same bases)
-namespace rnsh {
-inline bool prime32(uint32_t n) {  // deterministic Miller-Rabin for n < 2^32
-  if (n < 2) return false;
-  for (uint32_t p : {2u, 3u, 5u, 7u})
-    if (n % p == 0) return n == p;
-  uint32_t d = n - 1;
-  int r = 0;
-  while (!(d & 1)) d >>= 1, ++r;
-  for (uint64_t a : {2ull, 3ull, 5ull, 7ull}) {
-    uint64_t x = 1, b = a, e = d;
-    while (e) {
-      if (e & 1) x = x * b % n;
-      b = b * b % n;
-      e >>= 1;
-    }
-    if (x == 1 || x == n - 1) continue;
-    bool ok = false;
-    for (int i = 1; i < r && !ok; ++i) {
-      x = x * x % n;
-      ok = x == n - 1;
-    }
-    if (!ok) return false;
-  }
-  return true;
-}
-inline uint32_t inv_mod(uint32_t a, uint32_t m) {  // a^-1 mod m (gcd = 1)
-  int64_t t0 = 0, t1 = 1, r0 = m, r1 = a % m;
-  while (r1) {
-    const int64_t q = r0 / r1;
-    std::swap(r0, r1);
-    r1 -= q * r0;
-    std::swap(t0, t1);
-    t1 -= q * t0;
-  }
-  return (uint32_t)((t0 % (int64_t)m + m) % m);
-}
-inline uint32_t inv_2_32(uint32_t a) {  // odd a
-  uint32_t x = a;
-  for (int i = 0; i < 5; ++i) x *= 2u - a * x;
-  return x;
-}
-inline uint32_t shoup_const(uint32_t w, uint32_t m) {  // floor(w 2^32 / m), w < m
-  return (uint32_t)(((uint64_t)w << 32) / m);
-}
-inline uint32_t mod_small(const BigU& x, uint32_t m) {  // m = 0: mod 2^32
-  if (m == 0) return x.word(0);
-  uint64_t r = 0;
-  for (size_t k = x.w.size(); k-- > 0;) r = ((r << 32) | x.w[k]) % m;
-  return (uint32_t)r;
-}
-struct Bases {
-  std::vector<uint32_t> b, b2;  // B and B' (the 2 RK largest primes below 2^28, interleaved)
-  BigU M, M2;
-  std::vector<BigU> Mi, M2j;
-  std::vector<uint32_t> shared;  // the S_* block
-};
-inline const Bases& bases() {
-  static const Bases B = [] {
-    using namespace rns;
-    Bases r;
-    std::vector<uint32_t> pr;
-    for (uint32_t c = (1u << 28) - 1; (int)pr.size() < 2 * RK; c -= 2)
-      if (prime32(c)) pr.push_back(c);
-    for (int i = 0; i < 2 * RK; ++i) (i % 2 ? r.b2 : r.b).push_back(pr[i]);
-    r.M = BigU(1);
-    r.M2 = BigU(1);
-    for (int i = 0; i < RK; ++i) {
-      r.M = mul(r.M, BigU(r.b[i]));
-      r.M2 = mul(r.M2, BigU(r.b2[i]));
-    }
-    for (int i = 0; i < RK; ++i) {
-      BigU q;
-      divmod(r.M, BigU(r.b[i]), &q, nullptr);
-      r.Mi.push_back(q);
-      divmod(r.M2, BigU(r.b2[i]), &q, nullptr);
-      r.M2j.push_back(q);
-    }
-    std::vector<uint32_t>& s = r.shared;
-    s.assign(S_WORDS, 0u);
-    for (int slot = 0; slot < NSLOT; ++slot) {  // slot = 80 base + channel; B' channel RCH is r
-      const bool gB = slot < 80;
-      const int ch = gB ? slot : slot - 80;
-      const bool isr = !gB && ch == RCH;
-      if (!(ch < RK || isr)) continue;
-      const uint32_t m = isr ? 0u : (gB ? r.b[ch] : r.b2[ch]);
-      if (m) {
-        s[S_M + slot] = m;
-        s[S_MU + slot] = (uint32_t)((1ull << 59) / m);
-        s[S_T32 + slot] = (uint32_t)((1ull << 32) % m);
-      }
-      for (int i = 0; i < RK; ++i)  // B: |M'_j|_(m_i); B': |M_i|_(m'_j); 2^32: |M_i|_(2^32)
-        s[S_ROWS + i * NSLOT + slot] = gB ? mod_small(r.M2j[i], m) : mod_small(r.Mi[i], m);
-      if (gB) {
-        s[S_B + slot] = mod_small(r.M2, m);                       // |M'|_(m_i)
-        s[S_C + slot] = inv_mod(mod_small(r.Mi[ch], m), m);        // |M_i^-1|_(m_i)
-      } else if (!isr) {
-        const uint64_t minv = inv_mod(mod_small(r.M, m), m);
-        s[S_B + slot] = (uint32_t)minv;                                               // |M^-1|_(m'_j)
-        s[S_C + slot] = (uint32_t)(minv * inv_mod(mod_small(r.M2j[ch], m), m) % m);  // |M^-1 M'_j^-1|_(m'_j)
-        s[S_D + slot] = r.M2j[ch].word(0);                                            // |M'_j|_(2^32)
-      } else {
-        s[S_B + slot] = inv_2_32(r.M.word(0));  // M^-1 mod 2^32
-      }
-      if (m) {
-        s[S_BS + slot] = shoup_const(s[S_B + slot], m);
-        s[S_CS + slot] = shoup_const(s[S_C + slot], m);
-      }
-    }
-    for (int i = 0; i < RK; ++i) {
-      const std::vector<uint32_t> l = r.Mi[i].to_limbs(28, RKP);
-      for (int c = 0; c < RKP; ++c) s[S_MPOS + i * RKP + c] = l[c];
-    }
-    const std::vector<uint32_t> lm = r.M.to_limbs(28, RKP);
-    for (int c = 0; c < RKP; ++c) s[S_MFULL + c] = lm[c];
-    s[S_M2RINV] = inv_2_32(r.M2.word(0));
-    return r;
-  }();
-  return B;
-}
-// the per-prime block for N = P^2: |-N^-1 M_i^-1| (B), |N M^-1| and |N M^-1
-// M'_j^-1| (B'), N mod 2^32; M^3 mod N in every channel; and the exponent P - 1
-// as the kernel's sliding-window schedule (5-bit windows, the rule of
-// pow_uniform_exp: each window ends in a set bit)
-inline std::vector<uint32_t> prime_block(const BigU& P) {
-  using namespace rns;
-  const Bases& b = bases();
-  const BigU N = mul(P, P);
-  std::vector<uint32_t> v(P_WORDS, 0u);
-  const BigU MN = mod(b.M, N);
-  const BigU M3 = mulmod(mulmod(MN, MN, N), MN, N);
-  for (int slot = 0; slot < NSLOT; ++slot) {
-    const bool gB = slot < 80;
-    const int ch = gB ? slot : slot - 80;
-    const bool isr = !gB && ch == RCH;
-    if (!(ch < RK || isr)) continue;
-    const uint32_t m = isr ? 0u : (gB ? b.b[ch] : b.b2[ch]);
-    if (gB) {
-      const uint64_t ni = inv_mod(mod_small(N, m), m), mi = inv_mod(mod_small(b.Mi[ch], m), m);
-      v[P_A + slot] = (uint32_t)((m - ni * mi % m) % m);
-    } else if (!isr) {
-      const uint64_t nm = (uint64_t)mod_small(N, m) * inv_mod(mod_small(b.M, m), m) % m;
-      v[P_A + slot] = (uint32_t)nm;
-      v[P_A2 + slot] = (uint32_t)(nm * inv_mod(mod_small(b.M2j[ch], m), m) % m);
-      v[P_A2S + slot] = shoup_const(v[P_A2 + slot], m);
-    } else {
-      v[P_A + slot] = N.word(0);
-    }
-    if (m) v[P_AS + slot] = shoup_const(v[P_A + slot], m);
-    v[P_M3 + slot] = mod_small(M3, m);
-  }
-  // schedule over e = P - 1 (bits high to low)
-  const BigU e = sub(P, BigU(1));
-  const int nb = (int)e.bits();
-  auto bit = [&](int i) { return (e.word((size_t)i / 32) >> (i % 32)) & 1u; };  // i: from the bottom
-  auto window = [&](int hi, int* lo_out) {  // the window from bit hi down (at most 5 bits, ends in a set bit)
-    int lo = std::max(hi - 4, 0);
-    while (!bit(lo)) ++lo;
-    uint32_t val = 0;
-    for (int i = hi; i >= lo; --i) val = val << 1 | bit(i);
-    *lo_out = lo;
-    return val;
-  };
-  int ns = 0, lo;
-  const uint32_t first = window(nb - 1, &lo);
-  v[P_SCHED + ns++] = (first - 1) / 2;
-  int i = lo - 1;
-  uint32_t sq = 0;
-  while (i >= 0) {
-    if (!bit(i)) {
-      ++sq;
-      --i;
-      continue;
-    }
-    const uint32_t w = window(i, &lo);
-    sq += (uint32_t)(i - lo + 1);
-    if (ns >= P_SCHED_MAX) throw std::runtime_error("rns schedule overflow");
-    v[P_SCHED + ns++] = sq << 8 | ((w - 1) / 2 + 1);
-    sq = 0;
-    i = lo - 1;
-  }
-  if (sq) {
-    if (ns >= P_SCHED_MAX) throw std::runtime_error("rns schedule overflow");
-    v[P_SCHED + ns++] = sq << 8;
-  }
-  v[P_NS] = (uint32_t)ns;
-  return v;
-}
-}  // namespace rnsh
-
-struct ModOff {
-  size_t N, R1, R2, R3, Rpow = 0;
-  uint32_t n0inv;
-  int npow = 0;
-};
-
-// npow > 0 also stores R^j mod M for j < npow (consecutive rows of S4 limbs):
-// the fix-up factors of chains over plain residues (k_chunk_prod, raw inputs)
-ModOff put_mod(Blob& bl, const BigU& M, const ModSpec& s, int npow = 0) {
-  ModOff o;
-  BigU R = pow2((size_t)s.W * s.S);
-  BigU R1 = mod(R, M);
-  BigU R2 = mulmod(R1, R1, M);
-  BigU R3 = mulmod(R2, R1, M);
-  o.N = bl.put_limbs(M, s);
-  o.R1 = bl.put_limbs(R1, s);
-  o.R2 = bl.put_limbs(R2, s);
-  o.R3 = bl.put_limbs(R3, s);
-  o.n0inv = mont_ninv(M.word(0), s.W);
-  if (npow > 0) {
-    BigU x = mod(BigU(1), M);
-    for (int j = 0; j < npow; ++j) {
-      const size_t off = bl.put_limbs(x, s);
-      if (j == 0) o.Rpow = off;
-      x = mulmod(x, R1, M);
-    }
-    o.npow = npow;
-  }
-  return o;
 }
 
 }  // namespace
@@ -411,7 +170,6 @@ struct xhe_key {
   int K = 0, nw = 0, n2w = 0;
   bool priv = false, djn = false;
   int rand_bits = 0, rand_words = 0;
-  ModSpec mp2{}, mp{}, mn2{}, mp2L{}, mp2X{}, mn2X{};
   uint32_t* d_blob = nullptr;
   uint32_t* d_tab = nullptr;
   KeyDev kd{};
@@ -438,18 +196,6 @@ struct DevGuard {
 template <class MP2, int RW>
 void build_tables_m(xhe_key* k, const ModDev& md, const uint32_t* d_hM, uint32_t* d_tab, uint32_t* d_chain,
                     uint32_t* d_ws, hipStream_t s);
-
-// Window layout of a fixed-base table over rand_bits exponent bits: uniform
-// ceil(rand_bits/win) windows, or (split) floor(rand_bits/win) windows of
-// which the first rand_bits mod win are win+1 bits wide (KeyDev::nhi).
-void win_layout(int rand_bits, int win, bool split, int* nwin, int* nhi) {
-  *nwin = (rand_bits + win - 1) / win;
-  *nhi = 0;
-  if (split && rand_bits % win != 0 && rand_bits % win <= rand_bits / win) {
-    *nwin = rand_bits / win;
-    *nhi = rand_bits % win;
-  }
-}
 
 int64_t chain_rows_h(int win) { return ((int64_t)1 << (win / 2)) + ((int64_t)1 << (win - win / 2)); }
 
@@ -522,426 +268,120 @@ void build_tables_m(xhe_key* k, const ModDev& md, const uint32_t* d_hM, uint32_t
                             d_chain, d_ws, s);
 }
 
-ModDev moddev(uint32_t* base, const ModOff& o) {
-  return ModDev{base + o.N, base + o.R1, base + o.R2, base + o.R3, o.n0inv, o.npow ? base + o.Rpow : nullptr};
+// The shapes keyconst.hpp derives a key's constants for, read from the types
+// of the kernels that use them.
+template <class Sh>
+KeySpec key_spec(const xhe_key* k, int win) {
+  KeySpec s{};
+  s.K = Sh::K;
+  s.priv = k->priv;
+  s.djn = k->djn;
+  s.win = win & 0xff;
+  s.split = (win & XHE_WIN_SPLIT) != 0;
+  s.mp2 = {Sh::MP2::S, Sh::MP2::W};
+  s.mp2L = {Sh::MP2L::S, Sh::MP2L::W};
+  s.mp2X = {Sh::MP2X::S, Sh::MP2X::W};
+  s.mp = {Sh::MP::S, Sh::MP::W};
+  s.mn2 = {Sh::MN2::S, Sh::MN2::W};
+  s.mn2X = {Sh::MN2X::S, Sh::MN2X::W};
+  if constexpr (Sh::K == 2048) {
+    s.nd = {ND2048::K, ND2048::W};
+    // the one-lane digit kernels are instantiated on 37 limbs (k_djn_pmd<MP2, 37>,
+    // k_dec_pmd_*<37>): the mod-p limbs, whose R mod P they read as kd.p.R1
+    static_assert(Sh::MP::S == 37 && Sh::MP::W == 28, "k_*_pmd<37> run on the mod-p limbs");
+    s.pmd = s.mp;
+    s.wave = {WaveN2::K_, WaveN2::W};
+    static_assert(bar::S == Sh::MN2::S && bar::W == Sh::MN2::W, "Barrett constants are for 2048-bit keys");
+    s.bar = {bar::S, bar::W};
+  } else {
+    using D = typename Sh::PDX;  // products, conversions and the decrypt share the digits
+    static_assert(D::K == Sh::PDXO::K && D::K == Sh::PDXP::K, "one digit modulus per key size");
+    s.pd = {D::K, D::W};
+  }
+  return s;
 }
 
-void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, const BigU* h, int win) {
-  Blob bl;
-  const int K = k->K;
-  BigU n2 = mul(n, n);
-  size_t o_n = bl.put_words(n, k->nw);
-  size_t o_n2 = bl.put_words(n2, k->n2w);
-  BigU maxpos, minneg;
-  divmod(n, BigU(3), &maxpos, nullptr);
-  minneg = sub(n, maxpos);
-  size_t o_maxpos = bl.put_words(maxpos, k->nw);
-  size_t o_minneg = bl.put_words(minneg, k->nw);
-  size_t o_nlim = bl.put_limbs(n, k->mp2);
-  ModOff o_n2m = put_mod(bl, n2, k->mn2, kRpowRows);
-  ModOff o_n2X = put_mod(bl, n2, k->mn2X, kRpowRows);
-  size_t o_n2wN = 0, o_n2wnp = 0, o_n2wC = 0, o_n2wR2 = 0, o_n2mu = 0;
-  if (K == 2048) {  // k_add_barrett: mu = floor(beta^(2S) / n^2), beta = 2^27, S = 152
-    static_assert(bar::S == 152, "Barrett constants are for 2048-bit keys");
-    BigU mu;
-    divmod(pow2((size_t)27 * 2 * bar::S), n2, &mu, nullptr);
-    o_n2mu = bl.put_limbs(mu, ModSpec{bar::S + 1, 27});
-  }
-  if (K == 2048) {  // k_mexp_horner_wave
-    const ModSpec sw{154, 27};
-    const BigU Rw = pow2((size_t)27 * 154), RX = pow2((size_t)k->mn2X.W * k->mn2X.S);
-    o_n2wN = bl.put_limbs(n2, sw);
-    o_n2wnp = bl.put_limbs(sub(Rw, modinv(n2, Rw)), sw);
-    const BigU Rwn = mod(Rw, n2);
-    o_n2wC = bl.put_limbs(mulmod(mulmod(Rwn, Rwn, n2), modinv(mod(RX, n2), n2), n2), sw);
-    o_n2wR2 = bl.put_limbs(mulmod(Rwn, Rwn, n2), sw);
-  }
-  size_t o_nR2n2, o_hMn2 = 0;
-  {
-    BigU Rn2 = mod(pow2((size_t)k->mn2.W * k->mn2.S), n2);
-    o_nR2n2 = bl.put_limbs(mulmod(n, mulmod(Rn2, Rn2, n2), n2), k->mn2);
-    if (h && !p) o_hMn2 = bl.put_limbs(mulmod(mod(*h, n2), Rn2, n2), k->mn2);  // public DJN table base
-  }
-  // Montgomery digits mod n^2 (PMDX<80, 4>, pdigit_dev.hpp): n in 80 limbs of
-  // 27 bits, R = 2^2160; ceil(R/n) n^2 (the input conversion's offset), R - n,
-  // the digits (e, f) of R^2 mod n^2 and of 1 (R e + n f = X R^2 mod n^2),
-  // MASK + E_i with E = (1 - R) mod n
-  struct {
-    ModOff nd;
-    size_t kn2 = 0, rmn = 0, dw = 0, d1 = 0, topc = 0, dwt = 0;
-  } on;
-  if (K == 2048) {
-    const ModSpec sn{80, 27};
-    on.nd = put_mod(bl, n, sn);
-    const BigU R = pow2((size_t)27 * 80);
-    BigU q;
-    divmod(sub(add(R, n), BigU(1)), n, &q, nullptr);  // ceil(R / n)
-    on.kn2 = bl.put_limbs(mul(q, n2), ModSpec{160, 27});
-    on.rmn = bl.put_limbs(sub(R, n), sn);
-    const BigU Rn = mod(R, n), Rinv = modinv(Rn, n);
-    auto digits = [&](const BigU& X) {
-      const BigU e = mulmod(mod(X, n), Rinv, n);
-      BigU Q;
-      divmod(add(X, mul(R, sub(n, e))), n, &Q, nullptr);  // (X - R e) / n + R
-      const BigU f = submod(mod(Q, n), Rn, n);
-      const std::vector<uint32_t> el = e.to_limbs(27, 80), fl = f.to_limbs(27, 80);
-      std::vector<uint32_t> v(160);
-      for (int i = 0; i < 80; ++i) {
-        v[2 * i] = el[i];
-        v[2 * i + 1] = fl[i];
-      }
-      return bl.put(v);
-    };
-    const BigU R2 = mulmod(mod(R, n2), mod(R, n2), n2);  // R^2 mod n^2
-    on.d1 = digits(R2);                                   // 1 R^2
-    on.dw = digits(mulmod(R2, R2, n2));                   // R^2 R^2
-    // R^2 R_MN2^-1 (R_MN2 = 2^(27*152), the public DJN tables' Montgomery
-    // factor): converts their rows to canonical digits (k_tab_to_pmdx, n)
-    const BigU RM = mod(pow2((size_t)k->mn2.W * k->mn2.S), n2);
-    on.dwt = digits(mulmod(mulmod(R2, R2, n2), modinv(RM, n2), n2));  // X = w R^2, w = R^2 R_MN2^-1
-    std::vector<uint32_t> tc = submod(BigU(1), Rn, n).to_limbs(27, 80);
-    for (auto& x : tc) x += (1u << 27) - 1u;
-    on.topc = bl.put(tc);
-  }
-  // randomness bound (paillier.py:195 djn_exp_bound = 2^(bitlen(n)//2); :215 r < n)
-  k->rand_bits = k->djn ? (int)(n.bits() / 2) : (int)n.bits();
-  k->rand_words = (k->rand_bits + 31) / 32;
+int64_t table_rows(const KeyDev& kd) { return (int64_t)(kd.nwin + kd.nhi) << kd.win; }
 
-  struct {
-    ModOff p2, q2, p, q, p2L, q2L, p2X, q2X;
-    size_t nR2C_p2X = 0, nR2C_q2X = 0, R1C_p2X = 0, R1C_q2X = 0;
-    size_t nR_p2 = 0, nR_q2 = 0;
-    size_t nR2_p2L = 0, nR2_q2L = 0;
-    size_t nR2_p2 = 0, nR2_q2 = 0, q2invR = 0, q2_lim = 0, p2x4 = 0, hM_p2 = 0, hM_q2 = 0;
-    size_t pm1 = 0, qm1 = 0, pinv = 0, qinv = 0, hpR = 0, hqR = 0, qinvpR = 0, q_lim = 0, p2x = 0, p_lim = 0;
-    size_t ep = 0, eq = 0;
-    size_t topc_p = 0, topc_q = 0;
-    size_t nprime_p2 = 0, nprime_q2 = 0;
-    size_t rns = 0, rns_p = 0, rns_q = 0;
-    ModOff xd[2];
-    size_t xkn2[2] = {0, 0}, xrmn[2] = {0, 0}, xtopc[2] = {0, 0}, xfold[2] = {0, 0}, xdwt[2] = {0, 0};
-    size_t xdw[2] = {0, 0}, xhpR[2] = {0, 0};
-  } o;
-  int pm1_bits = 0, qm1_bits = 0, ep_bits = 0, eq_bits = 0;
-  if (k->priv) {
-    const BigU &P = *p, &Q = *q;
-    BigU p2 = mul(P, P), q2 = mul(Q, Q);
-    const ModSpec& s2 = k->mp2;
-    const ModSpec& s1 = k->mp;
-    o.p2 = put_mod(bl, p2, s2);
-    o.p2L = put_mod(bl, p2, k->mp2L);
-    o.q2L = put_mod(bl, q2, k->mp2L);
-    o.p2X = put_mod(bl, p2, k->mp2X);
-    o.q2X = put_mod(bl, q2, k->mp2X);
-    o.q2 = put_mod(bl, q2, s2);
-    if (K == 2048) {  // -P^-2 mod R for k_dec_wave's parallel REDC
-      const BigU R = pow2((size_t)s2.W * s2.S);
-      o.nprime_p2 = bl.put_limbs(sub(R, modinv(p2, R)), s2);
-      o.nprime_q2 = bl.put_limbs(sub(R, modinv(q2, R)), s2);
-      // the RNS decrypt's bases (shared by every key) and per-prime constants
-      o.rns = bl.put(rnsh::bases().shared);
-      o.rns_p = bl.put(rnsh::prime_block(P));
-      o.rns_q = bl.put(rnsh::prime_block(Q));
-    }
-    BigU R2p = pow2((size_t)s2.W * s2.S);
-    BigU Rp2 = mod(R2p, p2), Rq2 = mod(R2p, q2);
-    // n R^2 mod P^2
-    o.nR2_p2 = bl.put_limbs(mulmod(mod(n, p2), mulmod(Rp2, Rp2, p2), p2), s2);
-    o.nR2_q2 = bl.put_limbs(mulmod(mod(n, q2), mulmod(Rq2, Rq2, q2), q2), s2);
-    {  // n R_L^2 mod P^2 for the 4-lane shape (k_nodjn_crt<MP2L, 1>)
-      const ModSpec& sL = k->mp2L;
-      BigU RL = pow2((size_t)sL.W * sL.S);
-      BigU RLp = mod(RL, p2), RLq = mod(RL, q2);
-      o.nR2_p2L = bl.put_limbs(mulmod(mod(n, p2), mulmod(RLp, RLp, p2), p2), sL);
-      o.nR2_q2L = bl.put_limbs(mulmod(mod(n, q2), mulmod(RLq, RLq, q2), q2), sL);
-    }
-    o.nR_p2 = bl.put_limbs(mulmod(mod(n, p2), Rp2, p2), s2);  // n R mod P^2
-    o.nR_q2 = bl.put_limbs(mulmod(mod(n, q2), Rq2, q2), s2);
-    // CRT constants (context.py:46)
-    BigU q2inv = modinv(q2, p2);
-    o.q2invR = bl.put_limbs(mulmod(q2inv, Rp2, p2), s2);
-    o.q2_lim = bl.put_limbs(q2, s2);
-    o.p2x4 = bl.put_limbs(shl(p2, 2), s2);
-    if (k->djn) {
-      o.hM_p2 = bl.put_limbs(mulmod(mod(*h, p2), Rp2, p2), s2);  // h_pow_n mod p^2 (context.py:63)
-      o.hM_q2 = bl.put_limbs(mulmod(mod(*h, q2), Rq2, q2), s2);
-      // 16-lane small-batch shape on the same tables (k_djn_pow_x)
-      int nwin, nhi;
-      win_layout(k->rand_bits, win & 0xff, (win & XHE_WIN_SPLIT) != 0, &nwin, &nhi);
-      const ModSpec& sx = k->mp2X;
-      BigU Rx = pow2((size_t)sx.W * sx.S);
-      BigU Cexp = pow2((size_t)(sx.S - s2.S) * s2.W * nwin);  // (R'/R)^nwin
-      auto put_x = [&](const BigU& P2, size_t* nr2c, size_t* r1c) {
-        BigU C = mod(Cexp, P2), RxP = mod(Rx, P2);
-        BigU CR = mulmod(C, RxP, P2);
-        *r1c = bl.put_limbs(CR, sx);
-        *nr2c = bl.put_limbs(mulmod(mod(n, P2), mulmod(CR, RxP, P2), P2), sx);
-      };
-      put_x(p2, &o.nR2C_p2X, &o.R1C_p2X);
-      put_x(q2, &o.nR2C_q2X, &o.R1C_q2X);
-    }
-    // mod p / q (decrypt)
-    o.p = put_mod(bl, P, s1);
-    o.q = put_mod(bl, Q, s1);
-    BigU pm1 = sub(P, BigU(1)), qm1 = sub(Q, BigU(1));
-    pm1_bits = (int)pm1.bits();
-    qm1_bits = (int)qm1.bits();
-    o.pm1 = bl.put_words(pm1, k->nw / 2 + 1);
-    o.qm1 = bl.put_words(qm1, k->nw / 2 + 1);
-    BigU T = pow2((size_t)s1.W * s1.S);
-    o.pinv = bl.put_limbs(modinv(P, T), s1);
-    o.qinv = bl.put_limbs(modinv(Q, T), s1);
-    // hp = L_p((n+1)^(p-1) mod p^2)^-1 mod p (context.py:47,193-194). By the
-    // binomial theorem (n+1)^(p-1) = 1 + (p-1) n (mod n^2, hence mod p^2).
-    auto hfun = [&](const BigU& X, const BigU& X2) {
-      BigU x = mod(add(BigU(1), mul(sub(X, BigU(1)), n)), X2);
-      BigU L;
-      divmod(sub(x, BigU(1)), X, &L, nullptr);
-      return modinv(L, X);
-    };
-    BigU hp = hfun(P, p2), hq = hfun(Q, q2);
-    BigU Rp = mod(T, P), Rq = mod(T, Q);
-    o.hpR = bl.put_limbs(mulmod(hp, Rp, P), s1);
-    o.hqR = bl.put_limbs(mulmod(hq, Rq, Q), s1);
-    o.qinvpR = bl.put_limbs(mulmod(modinv(Q, P), Rp, P), s1);  // context.py:43
-    o.q_lim = bl.put_limbs(Q, s1);
-    if (K == 2048) {
-      // Montgomery-digit kernels (k_djn_pmd, k_dec_pmd): MASK + E_i, E = (1 - R) mod P,
-      // R = 2^(28*37) (= the mod-p shape's R, so R mod P is kd.p.R1)
-      auto topc = [&](const BigU& X) {
-        std::vector<uint32_t> v = submod(BigU(1), mod(T, X), X).to_limbs(28, 37);
-        for (auto& x : v) x += (1u << 28) - 1u;
-        return bl.put(v);
-      };
-      o.topc_p = topc(P);
-      o.topc_q = topc(Q);
-    }
-    if (K == 3072 || K == 4096 || K == 8192) {
-      // Montgomery digits mod P^2 over 4 lanes (k_djn_pmdx, k_dec_pmdx_*): per
-      // prime the modulus P in K limbs of 27 bits (R = 2^(27 K)), ceil(R/P)
-      // P^2, R - P, MASK + E_i, the fold constant Q R^3 mod P, the digits of
-      // R^2 R_MP2^-1 mod P^2 (R_MP2: the MP2 shape's R, the tables' factor)
-      // and of R^2 mod P^2 (plain conversion), and hp R mod P (decrypt)
-      const int KD = K == 3072 ? 60 : K == 4096 ? 80 : 160;
-      const ModSpec sd{KD, 27};
-      const BigU Rd = pow2((size_t)27 * KD), RM = pow2((size_t)s2.W * s2.S);
-      for (int i = 0; i < 2; ++i) {
-        const BigU& X = i ? Q : P;
-        const BigU& Y = i ? P : Q;
-        const BigU X2 = i ? q2 : p2;
-        o.xd[i] = put_mod(bl, X, sd);
-        BigU cq;
-        divmod(sub(add(Rd, X), BigU(1)), X, &cq, nullptr);
-        o.xkn2[i] = bl.put_limbs(mul(cq, X2), ModSpec{2 * KD, 27});
-        o.xrmn[i] = bl.put_limbs(sub(Rd, X), sd);
-        const BigU RdX = mod(Rd, X);
-        std::vector<uint32_t> tc = submod(BigU(1), RdX, X).to_limbs(27, KD);
-        for (auto& x : tc) x += (1u << 27) - 1u;
-        o.xtopc[i] = bl.put(tc);
-        o.xfold[i] = bl.put_limbs(mulmod(mod(Y, X), mulmod(mulmod(RdX, RdX, X), RdX, X), X), sd);
-        // digits (e, f) of w: R e + X f = w R^2 (mod X^2), as K interleaved pairs;
-        // Xw = w R^2 mod X^2
-        auto put_digits = [&](const BigU& Xw) {
-          const BigU e = mulmod(mod(Xw, X), modinv(RdX, X), X);
-          BigU Qd;
-          divmod(add(Xw, mul(Rd, sub(X, e))), X, &Qd, nullptr);
-          const BigU f = submod(mod(Qd, X), RdX, X);
-          const std::vector<uint32_t> el = e.to_limbs(27, KD), fl = f.to_limbs(27, KD);
-          std::vector<uint32_t> v(2 * KD);
-          for (int j = 0; j < KD; ++j) {
-            v[2 * j] = el[j];
-            v[2 * j + 1] = fl[j];
-          }
-          return bl.put(v);
-        };
-        const BigU Rd2 = mulmod(mod(Rd, X2), mod(Rd, X2), X2);
-        const BigU Rd4 = mulmod(Rd2, Rd2, X2);
-        o.xdwt[i] = put_digits(mulmod(Rd4, modinv(mod(RM, X2), X2), X2));  // w = R^2 R_MP2^-1
-        o.xdw[i] = put_digits(Rd4);                                        // w = R^2
-        o.xhpR[i] = bl.put_limbs(mulmod(i ? hq : hp, RdX, X), sd);
-      }
-    }
-    o.p2x = bl.put_limbs(shl(P, 1), s1);
-    o.p_lim = bl.put_limbs(P, s1);
-    // non-DJN private obfuscation exponents ep = n mod phi(p^2) (context.py:51-52)
-    BigU ep = mod(n, mul(P, sub(P, BigU(1)))), eq = mod(n, mul(Q, sub(Q, BigU(1))));
-    ep_bits = (int)ep.bits();
-    eq_bits = (int)eq.bits();
-    o.ep = bl.put_words(ep, k->nw);
-    o.eq = bl.put_words(eq, k->nw);
-  }
-  // upload
-  HIPCHK(hipMalloc(&k->d_blob, bl.h.size() * sizeof(uint32_t)));
-  HIPCHK(hipMemcpy(k->d_blob, bl.h.data(), bl.h.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
-  uint32_t* B = k->d_blob;
+// Rewrites table rows as Montgomery digits in place: one launch per table
+// (tpr threads per row), then a device synchronisation.
+template <class F>
+void rows_to_digits(int64_t rows, int tpr, unsigned block, int ntab, F&& launch_one) {
+  const dim3 grid((unsigned)((rows * tpr + block - 1) / block));
+  for (int i = 0; i < ntab; ++i) launch_one(i, grid, dim3(block));
+  HIPCHK(hipDeviceSynchronize());
+}
+
+// Private DJN keys: h^(d 2^..) mod p^2 and mod q^2 as packed rows of Shape::RW
+// = K/32 words (p^2 < 2^K), then rewritten as the digit pairs (e, f) that
+// k_djn_pmd (2048) / k_djn_pmdx read.
+void build_private_tables(xhe_key* k, const KeyImage& im) {
   KeyDev& kd = k->kd;
-  kd.K = K;
-  kd.nw = k->nw;
-  kd.n2w = k->n2w;
-  kd.priv = k->priv;
-  kd.djn = k->djn;
-  kd.n_words = B + o_n;
-  kd.n2_words = B + o_n2;
-  kd.maxpos = B + o_maxpos;
-  kd.minneg = B + o_minneg;
-  kd.n_lim = B + o_nlim;
-  kd.n2 = moddev(B, o_n2m);
-  kd.n2X = moddev(B, o_n2X);
-  if (K == 2048) {
-    kd.n2w_N = B + o_n2wN;
-    kd.n2w_np = B + o_n2wnp;
-    kd.n2w_C = B + o_n2wC;
-    kd.n2w_R2 = B + o_n2wR2;
-    kd.n2_mu = B + o_n2mu;
-  }
-  kd.nR2_n2 = B + o_nR2n2;
-  kd.n_bits = (int)n.bits();
-  if (K == 2048) {
-    kd.ndig = 1;
-    kd.nd = moddev(B, on.nd);
-    kd.nd_kn2 = B + on.kn2;
-    kd.nd_rmn = B + on.rmn;
-    kd.nd_topc = B + on.topc;
-    kd.nd_dw = reinterpret_cast<const uint2*>(B + on.dw);
-    kd.nd_d1 = reinterpret_cast<const uint2*>(B + on.d1);
-    kd.nd_dwt = reinterpret_cast<const uint2*>(B + on.dwt);
-  }
-  if (k->priv) {
-    kd.p2 = moddev(B, o.p2);
-    kd.p2L = moddev(B, o.p2L);
-    kd.q2L = moddev(B, o.q2L);
-    kd.p2X = moddev(B, o.p2X);
-    kd.q2X = moddev(B, o.q2X);
-    kd.q2 = moddev(B, o.q2);
-    kd.nR2_p2 = B + o.nR2_p2;
-    kd.nR_p2 = B + o.nR_p2;
-    kd.nR_q2 = B + o.nR_q2;
-    kd.nR2C_p2X = B + o.nR2C_p2X;
-    kd.nR2C_q2X = B + o.nR2C_q2X;
-    kd.R1C_p2X = B + o.R1C_p2X;
-    kd.R1C_q2X = B + o.R1C_q2X;
-    kd.nR2_q2 = B + o.nR2_q2;
-    kd.nR2_p2L = B + o.nR2_p2L;
-    kd.nR2_q2L = B + o.nR2_q2L;
-    kd.q2invR_p2 = B + o.q2invR;
-    kd.q2_lim = B + o.q2_lim;
-    kd.p2x4_lim = B + o.p2x4;
-    kd.p = moddev(B, o.p);
-    kd.q = moddev(B, o.q);
-    kd.pm1_words = B + o.pm1;
-    kd.qm1_words = B + o.qm1;
-    kd.pm1_bits = pm1_bits;
-    kd.qm1_bits = qm1_bits;
-    kd.pinv_lim = B + o.pinv;
-    kd.qinv_lim = B + o.qinv;
-    kd.hpR = B + o.hpR;
-    kd.hqR = B + o.hqR;
-    kd.qinvpR = B + o.qinvpR;
-    kd.q_lim = B + o.q_lim;
-    kd.p2x_lim = B + o.p2x;
-    kd.p_lim = B + o.p_lim;
-    kd.ep_words = B + o.ep;
-    kd.eq_words = B + o.eq;
-    kd.ep_bits = ep_bits;
-    kd.eq_bits = eq_bits;
-    if (K == 2048) {
-      kd.p2_nprime = B + o.nprime_p2;
-      kd.q2_nprime = B + o.nprime_q2;
-      kd.rns = B + o.rns;
-      kd.rns_p = B + o.rns_p;
-      kd.rns_q = B + o.rns_q;
-    }
-    if (K == 2048) {
-      kd.topc_p = B + o.topc_p;
-      kd.topc_q = B + o.topc_q;
-    }
-    if (K == 3072 || K == 4096 || K == 8192) {
-      kd.pmdx_dec = 1;
-      kd.x_dw_p = reinterpret_cast<const uint2*>(B + o.xdw[0]);
-      kd.x_dw_q = reinterpret_cast<const uint2*>(B + o.xdw[1]);
-      kd.x_hpR_p = B + o.xhpR[0];
-      kd.x_hpR_q = B + o.xhpR[1];
-      kd.dp = moddev(B, o.xd[0]);
-      kd.dq = moddev(B, o.xd[1]);
-      kd.x_kn2_p = B + o.xkn2[0];
-      kd.x_kn2_q = B + o.xkn2[1];
-      kd.x_rmn_p = B + o.xrmn[0];
-      kd.x_rmn_q = B + o.xrmn[1];
-      kd.x_topc_p = B + o.xtopc[0];
-      kd.x_topc_q = B + o.xtopc[1];
-      kd.x_fold_p = B + o.xfold[0];
-      kd.x_fold_q = B + o.xfold[1];
-      kd.x_dwt_p = reinterpret_cast<const uint2*>(B + o.xdwt[0]);
-      kd.x_dwt_q = reinterpret_cast<const uint2*>(B + o.xdwt[1]);
-    }
-    if (k->djn) {
-      kd.win = win & 0xff;
-      win_layout(k->rand_bits, kd.win, (win & XHE_WIN_SPLIT) != 0, &kd.nwin, &kd.nhi);
-      size_t rows = (size_t)(kd.nwin + kd.nhi) << kd.win;
-      size_t tab_words = rows * (size_t)(K / 32);  // packed rows: Shape::RW = K/32 words (p^2 < 2^K)
-      HIPCHK(hipMalloc(&k->d_tab, 2 * tab_words * sizeof(uint32_t)));
-      kd.tab_rs = K / 32;
-      kd.tab_p2 = k->d_tab;
-      kd.tab_q2 = k->d_tab + tab_words;
-      const ModDev mds[2] = {kd.p2, kd.q2};
-      const uint32_t* hms[2] = {B + o.hM_p2, B + o.hM_q2};
-      uint32_t* tabs[2] = {const_cast<uint32_t*>(kd.tab_p2), const_cast<uint32_t*>(kd.tab_q2)};
-      with_shape(K, [&](auto sh) {
-        using Sh = decltype(sh);
-        build_tables_sync<typename Sh::MP2, Sh::RW>(k, mds, hms, tabs, 2);
+  const int64_t rows = table_rows(kd);
+  const size_t tab_words = (size_t)rows * (size_t)(k->K / 32);
+  HIPCHK(hipMalloc(&k->d_tab, 2 * tab_words * sizeof(uint32_t)));
+  kd.tab_rs = k->K / 32;
+  kd.tab_p2 = k->d_tab;
+  kd.tab_q2 = k->d_tab + tab_words;
+  const ModDev mds[2] = {kd.p2, kd.q2};
+  const uint32_t* hms[2] = {k->d_blob + im.hM_p2[0], k->d_blob + im.hM_p2[1]};
+  uint32_t* tabs[2] = {k->d_tab, k->d_tab + tab_words};
+  with_shape(k->K, [&](auto sh) {
+    using Sh = decltype(sh);
+    build_tables_sync<typename Sh::MP2, Sh::RW>(k, mds, hms, tabs, 2);
+    if constexpr (Sh::K == 2048) {
+      kd.pmd = 1;
+      const ModDev mp[2] = {kd.p, kd.q};
+      rows_to_digits(rows, 1, 256, 2, [&](int i, dim3 grid, dim3 block) {
+        launch((k_tab_to_pmd<Sh::MP::S, 64>), grid, block, nullptr, mp[i].N, mp[i].n0inv, mp[i].R1, tabs[i], rows,
+               (int64_t)kd.tab_rs);
       });
-      if (K == 2048) {
-        // rows as Montgomery digits (e, f) for k_djn_pmd
-        kd.pmd = 1;
-        const int64_t trows = (int64_t)(kd.nwin + kd.nhi) << kd.win;
-        const ModDev mp[2] = {kd.p, kd.q};
-        for (int i = 0; i < 2; ++i) {
-          launch((k_tab_to_pmd<37, 64>), dim3((unsigned)((trows + 255) / 256)), dim3(256), nullptr, mp[i].N,
-                 mp[i].n0inv, mp[i].R1, tabs[i], trows, (int64_t)kd.tab_rs);
-        }
-        HIPCHK(hipDeviceSynchronize());
-      }
-      if (K == 3072 || K == 4096 || K == 8192) {
-        // rows as Montgomery digits (e, f) for k_djn_pmdx
-        kd.pmdx = 1;
-        const int64_t trows = (int64_t)(kd.nwin + kd.nhi) << kd.win;
-        with_shape(K, [&](auto sh) {
-          using Sh = decltype(sh);
-          if constexpr (Sh::K == 3072 || Sh::K == 4096 || Sh::K == 8192) {
-            using D = typename Sh::PDXO;
-            for (int i = 0; i < 2; ++i) {
-              launch((k_tab_to_pmdx<D, Sh::RW>), dim3((unsigned)((trows * D::TPI + 127) / 128)), dim3(128), nullptr, kd,
-                     i, tabs[i], trows, (int64_t)kd.tab_rs);
-            }
-          }
-        });
-        HIPCHK(hipDeviceSynchronize());
-      }
+    } else {
+      kd.pmdx = 1;
+      using D = typename Sh::PDXO;
+      rows_to_digits(rows, D::TPI, 128, 2, [&](int i, dim3 grid, dim3 block) {
+        launch((k_tab_to_pmdx<D, Sh::RW>), grid, block, nullptr, kd, i, tabs[i], rows, (int64_t)kd.tab_rs);
+      });
     }
-  }
-  if (!k->priv && k->djn) {
-    kd.win = win & 0xff;
-    win_layout(k->rand_bits, kd.win, false, &kd.nwin, &kd.nhi);  // public tables stay uniform
-    size_t rows = (size_t)kd.nwin << kd.win;
-    size_t tab_words = rows * (size_t)(K / 16);  // packed rows: Shape::RW2 = n2w words
-    HIPCHK(hipMalloc(&k->d_tab, tab_words * sizeof(uint32_t)));
-    kd.tab_n2 = k->d_tab;
-    const uint32_t* hm = B + o_hMn2;
-    uint32_t* tab = k->d_tab;
-    with_shape(K, [&](auto sh) {
-      using Sh = decltype(sh);
-      build_tables_sync<typename Sh::MN2, Sh::RW2>(k, &kd.n2, &hm, &tab, 1);
-    });
-    if (K == 2048 && ndig_pub_on()) {
-      // rows as canonical Montgomery digits of n (e, f < n: 64 + 64 words,
-      // still 512 B) for k_djn_pub_nd
+  });
+}
+
+// Public DJN keys: h^(d 2^(win w)) mod n^2 as packed rows of Shape::RW2 = n2w
+// words, uniform windows; at 2048 bits rewritten as canonical Montgomery
+// digits of n (e, f < n: 64 + 64 words, still 512 B) for k_djn_pub_nd.
+void build_public_tables(xhe_key* k, const KeyImage& im) {
+  KeyDev& kd = k->kd;
+  const int64_t rows = table_rows(kd);
+  HIPCHK(hipMalloc(&k->d_tab, (size_t)rows * (size_t)(k->K / 16) * sizeof(uint32_t)));
+  kd.tab_n2 = k->d_tab;
+  const uint32_t* hm = k->d_blob + im.hM_n2;
+  uint32_t* tab = k->d_tab;
+  with_shape(k->K, [&](auto sh) {
+    using Sh = decltype(sh);
+    build_tables_sync<typename Sh::MN2, Sh::RW2>(k, &kd.n2, &hm, &tab, 1);
+    if constexpr (Sh::K == 2048) {
+      if (!ndig_pub_on()) return;
       kd.pub_nd = 1;
-      using D = PMDX<80, 4>;
-      launch((k_tab_to_pmdx<D, 128>), dim3((unsigned)((rows * D::TPI + 127) / 128)), dim3(128), nullptr, kd, 2, tab,
-             (int64_t)rows, (int64_t)128);
-      HIPCHK(hipDeviceSynchronize());
+      rows_to_digits(rows, ND2048::TPI, 128, 1, [&](int, dim3 grid, dim3 block) {
+        launch((k_tab_to_pmdx<ND2048, Sh::RW2>), grid, block, nullptr, kd, 2, tab, rows, (int64_t)Sh::RW2);
+      });
     }
-  }
+  });
+}
+
+// Derive the constants on the host (keyconst.hpp), upload them as one blob,
+// point the KeyDev into it, then build the DJN fixed-base tables.
+void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, const BigU* h, int win) {
+  const KeySpec spec = with_shape(k->K, [&](auto sh) { return key_spec<decltype(sh)>(k, win); });
+  const KeyImage im = derive_key_constants(spec, n, p, q, h);
+  k->rand_bits = im.rand_bits;
+  k->rand_words = im.rand_words;
+  HIPCHK(hipMalloc(&k->d_blob, im.words.size() * sizeof(uint32_t)));
+  HIPCHK(hipMemcpy(k->d_blob, im.words.data(), im.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
+  k->kd = im.bind(k->d_blob);
+  if (!k->djn) return;
+  if (k->priv) build_private_tables(k, im);
+  else build_public_tables(k, im);
 }
 
 int blocks_for(int64_t count, int tpi, int cap) {
@@ -1275,7 +715,7 @@ void encrypt_pub_djn_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r
     if (k->kd.pub_nd) {
       // fixed-base products in Montgomery digits of n (k_djn_pub_nd), then
       // (1 + n m) folded in base n on the way out (k_ndig_out)
-      using D = PMDX<80, 4>;  // ND2048
+      using D = ND2048;
       const int64_t chunk = std::min<int64_t>(count, kChunk);
       WsScope wsc(s);
       uint2* st = wsc.get<uint2>((size_t)D::K * chunk * sizeof(uint2));
@@ -1307,7 +747,6 @@ void encrypt_pub_djn_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r
   }
 }
 
-using ND2048 = PMDX<80, 4>;
 // $XHE_NDIG=0: the Montgomery mod-n^2 kernels instead (A/B measurement)
 bool ndig_on() {
   static const bool on = env_on("XHE_NDIG");
@@ -1397,7 +836,7 @@ void encrypt_nodjn_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r, 
     if (!k->priv && pub_wave(count)) {
       // (a pinned large batch: grid.x holds it, a block per element)
       ProfScope ps("k_nodjn_pub_wave", s);
-      launch((k_nodjn_pub_wave<154, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, m, r, k->rand_words, count, ct);
+      launch((k_nodjn_pub_wave<WaveN2::K_, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, m, r, k->rand_words, count, ct);
       return;
     }
   }
@@ -1502,7 +941,7 @@ void mulmod_impl(const xhe_key* k, const uint32_t* a, const int32_t* ea, const u
                  int64_t count, int dmax, uint32_t* out, int32_t* eout, hipStream_t s) {
   if constexpr (Sh::K == 2048) {
     if (count <= kWaveAddMax && dmax >= kWaveAddMinD && add_wave_on()) {
-      launch((k_mulmod_wave<154, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, a, ea, b, eb, count, out, eout);
+      launch((k_mulmod_wave<WaveN2::K_, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, a, ea, b, eb, count, out, eout);
       return;
     }
   }
@@ -1576,7 +1015,7 @@ int invert_impl(const xhe_key* k, const uint32_t* c, int64_t count, uint32_t* ou
   if (count <= 256) {
     // small batch: a product tree of whole-block products (dec_wave.hpp
     // k_wtree_*), one launch per level
-    constexpr int KW = 154;
+    constexpr int KW = WaveN2::K_;
     std::vector<int64_t> woff;
     int64_t wtot = 0;
     for (auto n : sizes) {
@@ -1874,7 +1313,7 @@ void multiexp_impl(const xhe_key* k, const uint32_t* bases, int64_t nbases, cons
       // small batches: one 16-wave block per column (latency; k_mexp_horner_wave)
       static const bool on = env_on("XHE_MEXP_WAVE");
       if (on && ncols <= 4096) {
-        launch((k_mexp_horner_wave<154, 16>), dim3((unsigned)ncols), dim3(1024), s, k->kd, P, nwin, c, ncols, out);
+        launch((k_mexp_horner_wave<WaveN2::K_, 16>), dim3((unsigned)ncols), dim3(1024), s, k->kd, P, nwin, c, ncols, out);
         wave = true;
       }
     }
@@ -2474,15 +1913,6 @@ int xhe_key_create(int device, int key_bits, const uint32_t* n_words, const uint
     k->n2w = 2 * k->nw;
     k->priv = p_words != nullptr;
     k->djn = h_pow_n_words != nullptr;
-    with_shape(key_bits, [&](auto sh) {
-      using Sh = decltype(sh);
-      k->mp2 = {Sh::MP2::S, Sh::MP2::W};
-      k->mp2L = {Sh::MP2L::S, Sh::MP2L::W};
-      k->mp2X = {Sh::MP2X::S, Sh::MP2X::W};
-      k->mp = {Sh::MP::S, Sh::MP::W};
-      k->mn2 = {Sh::MN2::S, Sh::MN2::W};
-      k->mn2X = {Sh::MN2X::S, Sh::MN2X::W};
-    });
     BigU n = BigU::from_words(n_words, k->nw);
     if ((int)n.bits() > key_bits || n.bits() + 2 < (size_t)key_bits)
       return fail(XHE_EINVAL, "xhe_key_create: n does not match key_bits");
