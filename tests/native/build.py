@@ -1,7 +1,9 @@
 """Build the device self-test harnesses of tests/native (test infrastructure,
 not the product): mont_selftest (Mont<S, W, TPI> products against host big
 integers for every limb shape) and pdigit_selftest (base-P digit arithmetic
-mod P^2). hipcc cross-compiles for gfx950 without a GPU; the
+mod P^2) and rand_selftest (the obfuscation draw kernels with
+tiny bit counts and bounds; it only prints what they wrote, the pytest compares
+it with tests/chacha_ref.py). hipcc cross-compiles for gfx950 without a GPU; the
 binaries land in tests/native/_build (git-ignored, shipped to the GPU box with
 the tree) and are run by tests/test_gpu_native_selftests.py. The host-only
 programs of this folder (host_fuzz.cpp, modinv_host.cpp, keyconst_check.cpp)
@@ -21,6 +23,7 @@ HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")
 TARGETS = {
     "mont_selftest": ["bn_dev.hpp", "hostbn.hpp"],
     "pdigit_selftest": ["bn_dev.hpp", "hostbn.hpp", "pdigit_dev.hpp"],
+    "rand_selftest": ["xhe_kernels.hpp", "bn_dev.hpp", "keydev.hpp", "pdigit_dev.hpp"],
 }
 
 

@@ -64,7 +64,14 @@ def test_host_encrypt_chunking_is_invisible():
     pinned staging); the
     randomness is drawn at global element positions, so the result equals one
     device-resident encode + draw + encrypt of the whole batch, and spot
-    elements equal the oracle's encryption with the drawn a."""
+    elements equal the oracle's encryption with the drawn a.
+
+    Both sides here are this library's draws: what the one-shot xhe_rand draws
+    is compared with the ChaCha20 reference in tests/test_gpu_rand.py, where
+    test_rand_deep_stream_positions checks row 2^18, the first row of this
+    pipeline's second chunk. Chunked == one-shot (here) and one-shot ==
+    reference (there) together pin rand_impl's `base` offset to the
+    reference."""
     import ctypes
 
     import torch
