@@ -422,3 +422,183 @@ def ndigits_check(bits, trials, rng):
         worst = max(worst, ctr.max_col)
     return {"ndigit_K": D.k, "ndigit_W": D.W, "ndigit_max_column_log2": worst.bit_length(),
             "ndigit_trials": trials}
+
+
+# ---------------------------------------------------------------------------
+# The fixed-base row product with an additive second digit (pdigit_dev.hpp
+# "Additive second digit"; k_djn_pmd). A table row y (a unit mod P) with the
+# pair (e, f) is stored as (e, lhat), lhat = f y^-1 mod P, which is l R^2 for
+# the l of  y R^2 = R e (1 + P l)  (mod P^2). The state is (a, c, Lhat) with
+#
+#     x R^2 = (R a + P c)(1 + P L),   Lhat = L R^2 (mod P), a plain sum
+#
+# and state x row is a' = REDC(a e), c' = REDC(c e) + (R-1-m) + E, Lhat' = Lhat
+# + lhat: MontDigits.mul without the f a mads (4 k^2) and one multi-word
+# addition. The finish folds the sum back: c_f = c + REDC(a Lhat), a Montgomery
+# product mod P, and (a, c_f) is a pair again.
+class LogDigits(MontDigits):
+    LW = None  # 32-bit words of the log sum (a value below R)
+
+    def __init__(self, P):
+        super().__init__(P)
+        self.LW = -(-W * self.k // 32)
+
+    # -- rows
+    def row_direct(self, y):
+        """(e, lhat) of a unit y by one inversion (the definition)"""
+        e, f = self.to_form(y)
+        return e, f * pow(y, -1, self.P) % self.P
+
+    def mont_mul(self, b, a, ctr):
+        """b a R^-1 mod P (< b + P), operand scanning over the limbs of a with
+        lazy 64-bit columns (Mont<K, 28, 1>::mul): 2 k^2 mads"""
+        k = self.k
+        bl, al = limbs_loose(b, k), limbs(a, k)
+        T = [0] * k
+        for i in range(k):
+            x0 = T[0] + al[i] * bl[0]
+            m = (x0 * self.n0inv) & MASK
+            x0 += m * self.Pl[0]
+            assert x0 & MASK == 0
+            for j in range(1, k):
+                T[j - 1] = T[j] + al[i] * bl[j] + m * self.Pl[j]
+            T[k - 1] = 0
+            T[0] += x0 >> W
+            ctr.mads += 2 * k
+            ctr.max_col = max(ctr.max_col, max(T))
+        t = _norm_value(T)
+        assert (t * self.R - a * b) % self.P == 0 and t < b + self.P
+        return t
+
+    def reduce_once(self, t):
+        assert t < 2 * self.P
+        return t - self.P if t >= self.P else t
+
+    # -- the state
+    def start(self, row):
+        e, lhat = row
+        return e, 0, self.words(lhat)
+
+    def words(self, x):
+        assert x >> (32 * self.LW) == 0
+        return [(x >> (32 * i)) & 0xFFFFFFFF for i in range(self.LW)]
+
+    def lam_add(self, s, lhat):
+        """the LW-word add-with-carry of PMD::lam_add; the carry out must be 0"""
+        out, cy = [], 0
+        for sw, lw in zip(s, self.words(lhat)):
+            x = sw + lw + cy
+            out.append(x & 0xFFFFFFFF)
+            cy = x >> 32
+        assert cy == 0, "log sum left its words"
+        return out
+
+    def mul_row(self, state, row, ctr):
+        """PMD::mul_row's step schedule on (a, c), and the sum"""
+        k = self.k
+        a, c, s = state
+        e, lhat = row
+        al, cl, el = limbs_loose(a, k), limbs_loose(c, k), limbs(e, k)
+        T1, T2 = [0] * k, [0] * k
+        for i in range(k):
+            x1 = T1[0] + el[i] * al[0]
+            m1 = (x1 * self.n0inv) & MASK
+            x1 += m1 * self.Pl[0]
+            x2 = T2[0] + el[i] * cl[0]
+            m2 = (x2 * self.n0inv) & MASK
+            x2 += m2 * self.Pl[0]
+            assert x1 & MASK == 0 and x2 & MASK == 0
+            for j in range(1, k):
+                T1[j - 1] = T1[j] + el[i] * al[j] + m1 * self.Pl[j]
+                T2[j - 1] = T2[j] + el[i] * cl[j] + m2 * self.Pl[j]
+            ctr.mads += 4 * k
+            T1[k - 1] = 0
+            T2[k - 1] = (MASK - m1) + self.El[i]
+            T1[0] += x1 >> W
+            T2[0] += x2 >> W
+            ctr.max_col = max(ctr.max_col, max(T1), max(T2))
+        return _norm_value(T1), _norm_value(T2), self.lam_add(s, lhat)
+
+    def join(self, x, y, ctr):
+        """two states (the lane tree): the general product on (a, c), the sums added"""
+        a, c = self.mul((x[0], x[1]), (y[0], y[1]), ctr)
+        return a, c, self.lam_add(x[2], sum(w << (32 * i) for i, w in enumerate(y[2])))
+
+    def finish(self, state, ctr):
+        """(a, c_f): the pair form of the same residue"""
+        a, c, s = state
+        L = sum(w << (32 * i) for i, w in enumerate(s))
+        assert L < self.R, "log sum outgrew K limbs"
+        t = self.mont_mul(a, L, ctr)
+        return a, c + t
+
+    def log_value(self, state):
+        a, c, s = state
+        P, P2 = self.P, self.P * self.P
+        L = sum(w << (32 * i) for i, w in enumerate(s)) * pow(self.R, -2, P) % P
+        return self.value(a, c) * (1 + P * L) % P2
+
+
+class InverseBaseTable:
+    """One window of a fixed-base table for the base Bw mod P^2 with its rows'
+    log digits formed as k_tab_to_pmd forms them: no inversion per row - y^-1
+    mod P is the same entry for the base Bw^-1 mod P, the product of a high and
+    a low chain entry (d = hi 2^half + lo; entries in Montgomery form mod P,
+    entry 0 = R mod P), so lhat = MontMul(MontMul(f, hi'), lo')."""
+
+    def __init__(self, D, Bw, win):
+        self.D, self.Bw, self.win, self.half = D, Bw, win, win // 2
+        P = D.P
+        Binv = pow(Bw, -1, P)
+        RP = D.R % P
+        self.lo = [pow(Binv, d, P) * RP % P for d in range((1 << self.half) + 1)]
+        self.hi = [pow(Binv, d << self.half, P) * RP % P for d in range(1 << (win - self.half))]
+
+    def row(self, d, ctr):
+        D = self.D
+        y = pow(self.Bw, d, D.P * D.P)
+        e, f = D.to_form(y)
+        lo, hi = d & ((1 << self.half) - 1), d >> self.half
+        t = D.reduce_once(D.mont_mul(f, self.hi[hi], ctr))
+        t = D.reduce_once(D.mont_mul(t, self.lo[lo], ctr))
+        return y, (e, t)
+
+
+def unit(rng, P, bound):
+    import math
+    while True:
+        y = rng.randrange(1, bound)
+        if math.gcd(y, P) == 1:
+            return y
+
+
+def log_digits_check(bits, trials, rng, chain=44):
+    """chains of row products against Python integers; returns the counters"""
+    worst = amax = lmax = 0
+    cmax = float("-inf")
+    for t in range(trials):
+        P = random_prime_like(bits // 2, rng)
+        D = LogDigits(P)
+        P2 = P * P
+        ys = [unit(rng, P, P2) for _ in range(chain + 1)]
+        st = D.start(D.row_direct(ys[0]))
+        acc = ys[0]
+        for y in ys[1:]:
+            ctr = Counter()
+            st = D.mul_row(st, D.row_direct(y), ctr)
+            acc = acc * y % P2
+            assert D.log_value(st) == acc, "row product wrong"
+            assert ctr.mads == 4 * D.k * D.k
+            worst = max(worst, ctr.max_col)
+            amax = max(amax, st[0] / P)
+            cmax = max(cmax, (st[1] - D.R) / P)
+        fin = Counter()
+        a, c = D.finish(st, fin)
+        assert D.value(a, c) == acc, "finish wrong"
+        worst = max(worst, fin.max_col)
+        cmax = max(cmax, (c - D.R) / P)
+        lmax = max(lmax, sum(w << (32 * i) for i, w in enumerate(st[2])).bit_length())
+    return {"log_digit_mads_per_row_product": 4 * D.k * D.k, "log_digit_finish_mads": fin.mads,
+            "log_digit_max_column_log2": worst.bit_length(), "log_digit_a_over_P": amax,
+            "log_digit_c_minus_R_over_P": cmax, "log_digit_sum_bits": lmax, "log_digit_chain": chain,
+            "log_digit_trials": trials}

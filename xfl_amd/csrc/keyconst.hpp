@@ -279,6 +279,10 @@ struct KeyImage {
   KeyDev kd{};  // scalars as derived, every pointer null (see bind)
   int rand_bits = 0, rand_words = 0;
   size_t hM_n2 = 0, hM_p2[2] = {0, 0};  // fixed-base table bases h R mod n^2 (public DJN), mod p^2 / q^2 (private)
+  // 2048-bit private DJN keys: h^-1 R mod p / q in the digit limbs (a row of
+  // S4 words each), the base of the chains k_tab_to_pmd takes the rows'
+  // inverses from. Needed only while the tables are built: not in the blob.
+  std::vector<uint32_t> hinvM_p[2];
 
   // rows start 16-byte aligned: every constant is padded to a multiple of 4 words
   void put(const std::vector<uint32_t>& v, Dst dst, size_t min_words = 0) {
@@ -550,6 +554,14 @@ inline void exponent_constants(KeyImage& im, const KeySpec& s, const BigU& n, co
   }
 }
 
+// The inverse table base h^-1 R mod P as a padded limb row: the one modular
+// inversion per prime behind the tables' log digits (pdigit_dev.hpp)
+inline std::vector<uint32_t> inverse_base_limbs(const ModSpec& s, const BigU& h, const BigU& P) {
+  std::vector<uint32_t> v = mulmod(modinv(mod(h, P), P), mod(s.R(), P), P).to_limbs(s.W, s.S);
+  v.resize((size_t)s.S4(), 0u);
+  return v;
+}
+
 // p, q: null for a public key; h (= h_pow_n, context.py:63): null for a non-DJN key.
 inline KeyImage derive_key_constants(const KeySpec& s, const BigU& n, const BigU* p, const BigU* q, const BigU* h) {
   KeyImage im;
@@ -583,6 +595,8 @@ inline KeyImage derive_key_constants(const KeySpec& s, const BigU& n, const BigU
     for (int i = 0; i < 2; ++i) pdigit_constants(im, s, pr[i], i);
   }
   exponent_constants(im, s, n, pr);
+  if (s.K == 2048 && s.djn)
+    for (int i = 0; i < 2; ++i) im.hinvM_p[i] = inverse_base_limbs(s.pmd, *h, pr[i].X);
   return im;
 }
 

@@ -75,7 +75,10 @@ struct KeyDev {
   const uint32_t* p2x_lim;    // 2 p (MP limbs)
   const uint32_t* p_lim;      // p (MP limbs)
   // ---- Montgomery-digit DJN encryption (k_djn_pmd, 2048-bit keys): the
-  // tables hold digit pairs (pmd = 1); MASK + ((1 - R) mod P) limbs per prime
+  // tables hold digit rows (pmd = 1) - words [0, K/64) the first digit e < P
+  // of the row's pair (e, f), words [K/64, K/32) its log digit lhat = f y^-1
+  // mod P < P (y the row's residue; pdigit_dev.hpp "Additive second digit") -
+  // and MASK + ((1 - R) mod P) limbs per prime
   int pmd;
   const uint32_t *topc_p, *topc_q;
   // ---- Montgomery digits mod n^2 (PMDX, 2048-bit keys, public or private):

@@ -29,10 +29,39 @@
 // a' < P (1 + 2P/R) and c' < R + 4P, so the state stays bounded; the top
 // limb of c may exceed 2^28 and is kept unmasked. Every accumulator stays
 // below 2^63 (3K products of < 2^57 plus carries).
+//
+// Additive second digit (fixed-base table rows; k_djn_pmd). A table row y is
+// a unit mod P, so its pair (e, f) can be written y R^2 = R e (1 + P l) (mod
+// P^2) with the same e and l = f (R e)^-1 mod P, and the state held as
+//
+//     x R^2 = R a (1 + P L) + P c = (R a + P c)(1 + P L)   (mod P^2).
+//
+// (1 + P L)(1 + P l) = 1 + P (L + l) mod P^2: the factor is a logarithm, and
+// state times row is
+//
+//     a' = REDC(a e),   c' = REDC(c e) + (R-1-m) + E,   L' = L + l
+//
+// - the product above with f = 0 (`mul_row`: 4 K^2 = 5,476 mads, the f a
+// mads gone) and one multi-word addition. Two states multiply by the general
+// product on (a, c) and the sum of their L. After the last product
+// x R^2 = R a + P (c + R a L): c_f = c + REDC(a Lhat) with the rows storing
+// lhat = l R^2 mod P = f y^-1 mod P (canonical, below P; k_tab_to_pmd), and
+// (a, c_f) is the pair form again (`finish`, then to_mont2).
+// Lhat is a plain sum, never reduced: it is below nwin P with nwin <= 86
+// windows (window 12), so below 2^1031 < R = 2^1036: LW = 33 words, K limbs,
+// and a Lhat < P (1 + 2P/R) R keeps REDC(a Lhat) below a + P < 2.001 P.
+// Ranges: a', c' as above (c' < R + 4P), c_f < R + 7P, inside what to_mont2
+// takes. Columns of the row product: 2K products plus carries.
+// (Model: tools/pdigit_model.py LogDigits.)
 #pragma once
 #include "bn_dev.hpp"
 
 namespace xhe {
+
+struct PmdLdsQ {  // K limbs quad-major in a lane's slot: limb i at q[(i / 4) * 256 + i % 4]
+  const uint32_t* q;
+  XHE_DEV uint4 load4(int i) const { return *reinterpret_cast<const uint4*>(q + (i >> 2) * 256); }
+};
 
 template <int K_>
 struct PMD {
@@ -237,6 +266,204 @@ struct PMD {
     normalize(T2, c);
   }
 
+  // ---- the fixed-base row product (header: "Additive second digit").
+  // blk12 without the f a mads: 24 mads per 6 positions
+  //   T1[j-1+k] = T1[j+k] + e a[j+k] + m1 P[j+k]
+  //   T2[j-1+k] = T2[j+k] + e c[j+k] + m2 P[j+k]
+  XHE_DEV void blk12_row(uint64_t (&T1)[K], uint64_t (&T2)[K], const uint32_t (&a)[K], const uint32_t (&c)[K],
+                         uint32_t e, uint32_t m1, uint32_t m2, int j) const {
+    asm(
+      "v_mad_u64_u32 %0, vcc, %14, %17, %1\n\t"
+      "v_mad_u64_u32 %1, vcc, %14, %18, %2\n\t"
+      "v_mad_u64_u32 %2, vcc, %14, %19, %3\n\t"
+      "v_mad_u64_u32 %3, vcc, %14, %20, %4\n\t"
+      "v_mad_u64_u32 %4, vcc, %14, %21, %5\n\t"
+      "v_mad_u64_u32 %5, vcc, %14, %22, %12\n\t"
+      "v_mad_u64_u32 %6, vcc, %14, %23, %7\n\t"
+      "v_mad_u64_u32 %7, vcc, %14, %24, %8\n\t"
+      "v_mad_u64_u32 %8, vcc, %14, %25, %9\n\t"
+      "v_mad_u64_u32 %9, vcc, %14, %26, %10\n\t"
+      "v_mad_u64_u32 %10, vcc, %14, %27, %11\n\t"
+      "v_mad_u64_u32 %11, vcc, %14, %28, %13\n\t"
+      "v_mad_u64_u32 %0, vcc, %15, %29, %0\n\t"
+      "v_mad_u64_u32 %1, vcc, %15, %30, %1\n\t"
+      "v_mad_u64_u32 %2, vcc, %15, %31, %2\n\t"
+      "v_mad_u64_u32 %3, vcc, %15, %32, %3\n\t"
+      "v_mad_u64_u32 %4, vcc, %15, %33, %4\n\t"
+      "v_mad_u64_u32 %5, vcc, %15, %34, %5\n\t"
+      "v_mad_u64_u32 %6, vcc, %16, %29, %6\n\t"
+      "v_mad_u64_u32 %7, vcc, %16, %30, %7\n\t"
+      "v_mad_u64_u32 %8, vcc, %16, %31, %8\n\t"
+      "v_mad_u64_u32 %9, vcc, %16, %32, %9\n\t"
+      "v_mad_u64_u32 %10, vcc, %16, %33, %10\n\t"
+      "v_mad_u64_u32 %11, vcc, %16, %34, %11"
+        : "+v"(T1[j - 1]), "+v"(T1[j]), "+v"(T1[j + 1]), "+v"(T1[j + 2]), "+v"(T1[j + 3]), "+v"(T1[j + 4]),
+          "+v"(T2[j - 1]), "+v"(T2[j]), "+v"(T2[j + 1]), "+v"(T2[j + 2]), "+v"(T2[j + 3]), "+v"(T2[j + 4])
+        : "v"(T1[j + 5]), "v"(T2[j + 5]), "v"(e), "v"(m1), "v"(m2), "v"(a[j]), "v"(a[j + 1]), "v"(a[j + 2]),
+          "v"(a[j + 3]), "v"(a[j + 4]), "v"(a[j + 5]), "v"(c[j]), "v"(c[j + 1]), "v"(c[j + 2]), "v"(c[j + 3]),
+          "v"(c[j + 4]), "v"(c[j + 5]), "s"(p[j]), "s"(p[j + 1]), "s"(p[j + 2]), "s"(p[j + 3]), "s"(p[j + 4]),
+          "s"(p[j + 5])
+        : "vcc");
+  }
+
+  // `step` for a row limb e: entry x1 = T1[0] + e a[0], x2 = T2[0] + e c[0];
+  // the quotient chain and the topc - m1 entry are those of `step`
+  XHE_DEV void step_row(uint64_t (&T1)[K], uint64_t (&T2)[K], const uint32_t (&a)[K], const uint32_t (&c)[K],
+                        uint32_t e, uint32_t en, uint32_t& m1, uint32_t& m2, uint64_t& x1, uint64_t& x2,
+                        uint32_t topc) const {
+    uint64_t x1n = 0, x2n = 0;
+    uint32_t t1 = 0, t2 = 0, m1n = 0, m2n = 0;
+    asm("v_mad_u64_u32 %0, vcc, %2, %4, %0\n\t"
+        "v_mad_u64_u32 %1, vcc, %3, %4, %1"
+        : "+v"(x1), "+v"(x2)
+        : "v"(m1), "v"(m2), "s"(p[0])
+        : "vcc");
+#pragma unroll
+    for (int b = 0; b < (K - 1) / BL; ++b) {
+      const int j = 1 + BL * b;
+      blk12_row(T1, T2, a, c, e, m1, m2, j);
+      if (b == 0) {
+        T1[0] += x1 >> W;
+        T2[0] += x2 >> W;
+        asm volatile("" : "+v"(T1[0]), "+v"(T2[0]));
+      } else if (b == 1) {
+        asm("v_mad_u64_u32 %0, vcc, %2, %3, %5\n\t"
+            "v_mad_u64_u32 %1, vcc, %2, %4, %6"
+            : "=&v"(x1n), "=&v"(x2n)
+            : "v"(en), "v"(a[0]), "v"(c[0]), "v"(T1[0]), "v"(T2[0])
+            : "vcc");
+        asm volatile("" : "+v"(x1n), "+v"(x2n));
+      } else if (b == 2) {
+        t1 = (uint32_t)x1n * n0inv;
+        t2 = (uint32_t)x2n * n0inv;
+        asm volatile("" : "+v"(t1), "+v"(t2));
+      } else if (b == 3) {
+        m1n = t1 & MASK;
+        m2n = t2 & MASK;
+        asm volatile("" : "+v"(m1n), "+v"(m2n));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    T1[K - 1] = 0;
+    T2[K - 1] = (uint64_t)(topc - m1);
+    x1 = x1n;
+    x2 = x2n;
+    m1 = m1n;
+    m2 = m2n;
+  }
+
+  // (a, c) <- (REDC(a e), REDC(c e) + (R-1-m) + E): the state times a table
+  // row whose second digit travels in the log sum. e: K limbs, plain
+  // quad-major in the lane's slot (limb i at slot[(i / 4) * 256 + i % 4],
+  // zero beyond K; unpack_e_lds). 4 K^2 mads. Two limbs per LDS read, one
+  // pair in flight ahead of the steps that consume it.
+  XHE_DEV void mul_row(uint32_t (&a)[K], uint32_t (&c)[K], const uint32_t* slot, const uint32_t* topc) const {
+    uint64_t T1[K], T2[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) T1[j] = T2[j] = 0;
+    uint2 p0 = *reinterpret_cast<const uint2*>(slot);
+    uint64_t x1 = mad64(p0.x, a[0], 0ull);
+    uint64_t x2 = mad64(p0.x, c[0], 0ull);
+    uint32_t m1 = ((uint32_t)x1 * n0inv) & MASK, m2 = ((uint32_t)x2 * n0inv) & MASK;
+    for (int h = 0; h < K / 2; ++h) {
+      const int k = 2 * h + 2;  // the next pair: limbs k, k + 1 (k <= K - 1: inside the padded image)
+      const uint2 tc = *reinterpret_cast<const uint2*>(topc + 2 * h);
+      const uint2 p1 = *reinterpret_cast<const uint2*>(slot + (k >> 2) * 256 + (k & 2));
+      __builtin_amdgcn_sched_barrier(0);
+      step_row(T1, T2, a, c, p0.x, p0.y, m1, m2, x1, x2, tc.x);
+      __builtin_amdgcn_sched_barrier(0);
+      step_row(T1, T2, a, c, p0.y, p1.x, m1, m2, x1, x2, tc.y);
+      __builtin_amdgcn_sched_barrier(0);
+      p0 = p1;
+    }
+    if constexpr (K & 1) step_row(T1, T2, a, c, p0.x, 0u, m1, m2, x1, x2, topc[K - 1]);
+    normalize(T1, a);
+    normalize(T2, c);
+  }
+
+  // The log sum of a lane: LW little-endian words in quads [EQ, NQ) of its
+  // slot, beside the EQ quads of the row's e limbs.
+  static constexpr int EQ = (K + 3) / 4;           // quads of e limbs
+  static constexpr int LW = (W * K + 31) / 32;  // words of a sum below R: 33 at K = 37
+  static_assert(EQ + (LW + 3) / 4 <= NQ, "e limbs and the log sum share the slot of an interleaved row");
+
+  // sum <- lam (FIRST: the start value) or sum + lam; lam: HW words in
+  // registers (a row's log digit, or another lane's sum)
+  template <int HW, bool FIRST>
+  XHE_DEV static void lam_add(uint32_t* slot, const uint32_t (&lam)[HW]) {
+    constexpr int LQ = (LW + 3) / 4;
+    static_assert(HW >= 1 && HW <= 4 * LQ, "at most a whole sum");
+    uint32_t s[4 * LQ];
+    if constexpr (FIRST) {
+#pragma unroll
+      for (int k = 0; k < 4 * LQ; ++k) s[k] = k < HW ? lam[k] : 0u;
+    } else {
+#pragma unroll
+      for (int q = 0; q < LQ; ++q) {
+        const uint4 v = *reinterpret_cast<const uint4*>(slot + (EQ + q) * 256);
+        s[4 * q] = v.x, s[4 * q + 1] = v.y, s[4 * q + 2] = v.z, s[4 * q + 3] = v.w;
+      }
+      uint32_t cy = 0;
+#pragma unroll
+      for (int k = 0; k < LW; ++k) {
+        const uint64_t x = (uint64_t)s[k] + (k < HW ? lam[k] : 0u) + cy;
+        s[k] = (uint32_t)x;
+        cy = (uint32_t)(x >> 32);
+      }
+    }
+#pragma unroll
+    for (int q = 0; q < LQ; ++q)
+      *reinterpret_cast<uint4*>(slot + (EQ + q) * 256) = make_uint4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
+  }
+  // sum <- sum + the sum in another lane's slot (the tree of a lane group)
+  XHE_DEV static void lam_add_slot(uint32_t* slot, const uint32_t* other) {
+    constexpr int LQ = (LW + 3) / 4;
+    uint32_t o[4 * LQ];
+#pragma unroll
+    for (int q = 0; q < LQ; ++q) {
+      const uint4 v = *reinterpret_cast<const uint4*>(other + (EQ + q) * 256);
+      o[4 * q] = v.x, o[4 * q + 1] = v.y, o[4 * q + 2] = v.z, o[4 * q + 3] = v.w;
+    }
+    lam_add<4 * LQ, false>(slot, o);
+  }
+
+  // The finish: c <- c + REDC(a Lhat), Lhat the log sum (< R: K limbs). Its
+  // limbs go into the e quads of the slot and stream through one Montgomery
+  // product mod P (2 K^2 + K mads); a stays, so (a, c) is what to_mont2 takes.
+  XHE_DEV void finish(const uint32_t (&a)[K], uint32_t (&c)[K], uint32_t* slot, const uint32_t* Pl) const {
+    constexpr int LQ = (LW + 3) / 4;
+    {
+      uint32_t s[4 * LQ + 1];
+#pragma unroll
+      for (int q = 0; q < LQ; ++q) {
+        const uint4 v = *reinterpret_cast<const uint4*>(slot + (EQ + q) * 256);
+        s[4 * q] = v.x, s[4 * q + 1] = v.y, s[4 * q + 2] = v.z, s[4 * q + 3] = v.w;
+      }
+      s[4 * LQ] = 0u;
+      auto limb = [&](int i) -> uint32_t {
+        const int bit = W * i, k = bit >> 5, sh = bit & 31;
+        return i < K ? (__builtin_amdgcn_alignbit(k + 1 < LW ? s[k + 1] : 0u, s[k], sh) & MASK) : 0u;
+      };
+#pragma unroll
+      for (int q = 0; q < EQ; ++q)
+        *reinterpret_cast<uint4*>(slot + q * 256) = make_uint4(limb(4 * q), limb(4 * q + 1), limb(4 * q + 2), limb(4 * q + 3));
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    uint32_t t[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) t[j] = a[j];
+    Mont<K, W, 1> MN;
+    MN.init(Pl, n0inv);
+    MN.mul(t, PmdLdsQ{slot});  // REDC(a Lhat) < a + P
+    uint32_t cy = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {
+      const uint32_t x = c[j] + t[j] + cy;
+      c[j] = j + 1 < K ? (x & MASK) : x;
+      cy = j + 1 < K ? (x >> W) : 0u;
+    }
+  }
+
   // carry-normalise into W-bit limbs; the top limb keeps the final carry
   XHE_DEV static void normalize(const uint64_t (&T)[K], uint32_t (&b)[K]) {
     uint64_t cy = 0;
@@ -422,6 +649,32 @@ XHE_DEV void unpack_pairs_lds(uint32_t* slot) {
   for (int q = 0; q < (2 * K + 3) / 4; ++q)
     *reinterpret_cast<uint4*>(slot + q * 256) =
         make_uint4(limb(0, 2 * q), limb(HW, 2 * q), limb(0, 2 * q + 1), limb(HW, 2 * q + 1));
+}
+
+// The e half of a packed row alone (HW words, staged quad-major in quads
+// [0, HW/4) of the slot by LDS-DMA) rewritten in place as (K + 3) / 4 quads of
+// plain 28-bit limbs, zero beyond K (PMD::mul_row's operand). The quads above
+// stay untouched: they hold the lane's log sum.
+template <int K, int HW>
+XHE_DEV void unpack_e_lds(uint32_t* slot) {
+  static_assert(HW % 4 == 0 && 32 * HW >= 28 * K - 27, "the packed digit holds K limbs");
+  uint32_t w[HW];
+#pragma unroll
+  for (int q = 0; q < HW / 4; ++q) {
+    const uint4 v = *reinterpret_cast<const uint4*>(slot + q * 256);
+    w[4 * q] = v.x;
+    w[4 * q + 1] = v.y;
+    w[4 * q + 2] = v.z;
+    w[4 * q + 3] = v.w;
+  }
+  auto limb = [&](int i) -> uint32_t {
+    const int bit = 28 * i, k = bit >> 5, sh = bit & 31;
+    const uint32_t lo = k < HW ? w[k] : 0u, hi = k + 1 < HW ? w[k + 1] : 0u;
+    return i < K ? (__builtin_amdgcn_alignbit(hi, lo, sh) & ((1u << 28) - 1u)) : 0u;
+  };
+#pragma unroll
+  for (int q = 0; q < (K + 3) / 4; ++q)
+    *reinterpret_cast<uint4*>(slot + q * 256) = make_uint4(limb(4 * q), limb(4 * q + 1), limb(4 * q + 2), limb(4 * q + 3));
 }
 
 }  // namespace xhe

@@ -228,11 +228,11 @@ void build_tables_sync(xhe_key* k, const ModDev* md, const uint32_t* const* d_hM
 // alive until s has drained): window bases (low entry 1 of every window) =
 // base^(2^(win w)) by one squaring chain over nbases >= nwin windows, every
 // window's low and high chains by doubling levels (k_tab_level: log2 depth
-// instead of 2^(win/2)), then every packed row as one product of a high and a
-// low entry.
-template <class MP2, int RW>
-void build_tables_seg(const ModDev& md, const uint32_t* d_base, int win, int nwin, int nbases, uint32_t* d_tab,
-                      int64_t rs, uint32_t* d_chain, uint32_t* d_ws, hipStream_t s) {
+// instead of 2^(win/2)) - build_chains_seg - then every packed row as one
+// product of a high and a low entry.
+template <class MP2>
+void build_chains_seg(const ModDev& md, const uint32_t* d_base, int win, int nwin, int nbases, uint32_t* d_chain,
+                      uint32_t* d_ws, hipStream_t s) {
   const int half = win / 2;
   launch(k_tab_bases<MP2>, dim3(1), dim3(64), s, md, d_base, win, nbases, d_chain, d_ws);
   auto blocks = [&](int64_t groups) { return dim3((unsigned)std::max<int64_t>(1, (groups * MP2::TPI + 255) / 256)); };
@@ -244,6 +244,13 @@ void build_tables_seg(const ModDev& md, const uint32_t* d_base, int win, int nwi
   for (int t = 0; (1 << t) < lim_hi - 1; ++t) {
     launch(k_tab_level<MP2>, blocks((int64_t)nwin << t), dim3(256), s, md, md.N, win, nwin, t, half, lim_hi, d_chain);
   }
+}
+
+template <class MP2, int RW>
+void build_tables_seg(const ModDev& md, const uint32_t* d_base, int win, int nwin, int nbases, uint32_t* d_tab,
+                      int64_t rs, uint32_t* d_chain, uint32_t* d_ws, hipStream_t s) {
+  build_chains_seg<MP2>(md, d_base, win, nwin, nbases, d_chain, d_ws, s);
+  auto blocks = [&](int64_t groups) { return dim3((unsigned)std::max<int64_t>(1, (groups * MP2::TPI + 255) / 256)); };
   int64_t rows = (int64_t)nwin << win;
   launch((k_tab_combine<MP2, RW>), blocks(rows), dim3(256), s, md, md.N, win, nwin, d_chain, d_tab, rs);
 }
@@ -266,6 +273,31 @@ void build_tables_m(xhe_key* k, const ModDev& md, const uint32_t* d_hM, uint32_t
                         MP2::S4 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
   build_tables_seg<MP2, RW>(md, base2, win, nwin - nhi, nwin - nhi, d_tab + ((size_t)nhi << (win + 1)) * rs, rs,
                             d_chain, d_ws, s);
+}
+
+// The chains alone of a key's table layout for the base d_hM in shape M, kept
+// side by side for k_tab_to_pmd (the wide windows' chains first, then the
+// narrow ones' from row nhi chain_rows(win + 1)), enqueued on `s`. d_chain:
+// inv_chain_words<M>() words, d_ws: 4 rows.
+template <class M>
+size_t inv_chain_words(const KeyDev& kd) {
+  return (size_t)(kd.nhi * chain_rows_h(kd.win + 1) + (kd.nwin - kd.nhi) * chain_rows_h(kd.win)) * M::S4;
+}
+template <class M>
+void build_chains_m(const KeyDev& kd, const ModDev& md, const uint32_t* d_hM, uint32_t* d_chain, uint32_t* d_ws,
+                    hipStream_t s) {
+  const int win = kd.win, nwin = kd.nwin, nhi = kd.nhi;
+  if (nhi == 0) {
+    build_chains_seg<M>(md, d_hM, win, nwin, nwin, d_chain, d_ws, s);
+    return;
+  }
+  // the base chain's last entry (window nhi) lands on the narrow chains'
+  // first rows: copied out before they are built
+  uint32_t* base2 = d_ws + 2 * M::S4;
+  uint32_t* narrow = d_chain + (size_t)nhi * chain_rows_h(win + 1) * M::S4;
+  build_chains_seg<M>(md, d_hM, win + 1, nhi, nhi + 1, d_chain, d_ws, s);
+  HIPCHK(hipMemcpyAsync(base2, narrow + M::S4, M::S4 * sizeof(uint32_t), hipMemcpyDeviceToDevice, s));
+  build_chains_seg<M>(md, base2, win, nwin - nhi, nwin - nhi, narrow, d_ws, s);
 }
 
 // The shapes keyconst.hpp derives a key's constants for, read from the types
@@ -313,8 +345,9 @@ void rows_to_digits(int64_t rows, int tpr, unsigned block, int ntab, F&& launch_
 }
 
 // Private DJN keys: h^(d 2^..) mod p^2 and mod q^2 as packed rows of Shape::RW
-// = K/32 words (p^2 < 2^K), then rewritten as the digit pairs (e, f) that
-// k_djn_pmd (2048) / k_djn_pmdx read.
+// = K/32 words (p^2 < 2^K), then rewritten as the digit rows k_djn_pmd reads
+// (2048: the first digit e and the log digit lhat, k_tab_to_pmd) or the digit
+// pairs (e, f) of k_djn_pmdx.
 void build_private_tables(xhe_key* k, const KeyImage& im) {
   KeyDev& kd = k->kd;
   const int64_t rows = table_rows(kd);
@@ -328,15 +361,35 @@ void build_private_tables(xhe_key* k, const KeyImage& im) {
   uint32_t* tabs[2] = {k->d_tab, k->d_tab + tab_words};
   with_shape(k->K, [&](auto sh) {
     using Sh = decltype(sh);
-    build_tables_sync<typename Sh::MP2, Sh::RW>(k, mds, hms, tabs, 2);
     if constexpr (Sh::K == 2048) {
-      kd.pmd = 1;
+      // the chains of h^-1 mod p, q (the rows' inverses for their log digits),
+      // on streams of their own under the table build
+      using MP = typename Sh::MP;
       const ModDev mp[2] = {kd.p, kd.q};
+      hipStream_t st[2];
+      uint32_t *inv[2], *ws[2];
+      for (int i = 0; i < 2; ++i) {
+        HIPCHK(hipStreamCreateWithFlags(&st[i], hipStreamNonBlocking));
+        HIPCHK(hipMalloc(&inv[i], inv_chain_words<MP>(kd) * sizeof(uint32_t)));
+        HIPCHK(hipMalloc(&ws[i], MP::S4 * sizeof(uint32_t) * 4));  // rows 0, 2: build_chains_m; 3: the base
+        uint32_t* base = ws[i] + 3 * MP::S4;
+        HIPCHK(hipMemcpy(base, im.hinvM_p[i].data(), MP::S4 * sizeof(uint32_t), hipMemcpyHostToDevice));
+        build_chains_m<MP>(kd, mp[i], base, inv[i], ws[i], st[i]);
+      }
+      build_tables_sync<typename Sh::MP2, Sh::RW>(k, mds, hms, tabs, 2);
+      for (int i = 0; i < 2; ++i) HIPCHK(hipStreamSynchronize(st[i]));
+      kd.pmd = 1;
       rows_to_digits(rows, 1, 256, 2, [&](int i, dim3 grid, dim3 block) {
-        launch((k_tab_to_pmd<Sh::MP::S, 64>), grid, block, nullptr, mp[i].N, mp[i].n0inv, mp[i].R1, tabs[i], rows,
+        launch((k_tab_to_pmd<MP, Sh::RW>), grid, block, nullptr, mp[i], mp[i].N, inv[i], kd.win, kd.nhi, tabs[i], rows,
                (int64_t)kd.tab_rs);
       });
+      for (int i = 0; i < 2; ++i) {
+        HIPCHK(hipFree(inv[i]));
+        HIPCHK(hipFree(ws[i]));
+        HIPCHK(hipStreamDestroy(st[i]));
+      }
     } else {
+      build_tables_sync<typename Sh::MP2, Sh::RW>(k, mds, hms, tabs, 2);
       kd.pmdx = 1;
       using D = typename Sh::PDXO;
       rows_to_digits(rows, D::TPI, 128, 2, [&](int i, dim3 grid, dim3 block) {

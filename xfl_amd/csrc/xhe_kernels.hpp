@@ -12,6 +12,8 @@
 #include "keydev.hpp"  // ModDev, KeyDev
 #include "pdigit_dev.hpp"
 
+#include <type_traits>
+
 namespace xhe {
 
 // ============================================================== encode
@@ -600,14 +602,18 @@ __global__ void __launch_bounds__(128, 2) k_djn_pow_lds(KeyDev key, const uint32
 // DJN encryption in Montgomery digits (pdigit_dev.hpp PMD; 2048-bit keys,
 // K = 37 limbs of P): c_P = (1 + n m) h^a mod P^2 as k_djn_pow_lds computes
 // it, with the table products in digit form. The tables hold each row as its
-// digits (e, f) < P (k_tab_to_pmd), packed 32 + 32 words. Per prime and
-// element: the first window's row is the start value; each further window's
-// row is LDS-DMA'd into the wave's image, unpacked into interleaved limb
-// pairs, and multiplied in (nwin - 1 digit products, 5 K^2 mads each); the
-// result goes back to the 74-limb Montgomery form (R a + P c = h^a R^2 mod
-// P^2, to_mont2) for the two Montgomery products that bring in (1 + n m) and
-// leave Montgomery form, exactly as in djn_prime_lds. Output rows as
-// k_djn_pow_lds (MP2 limbs, [prime][2 S4][count]) for k_crt_enc_w.
+// first digit e < P and its log digit lhat < P (k_tab_to_pmd; pdigit_dev.hpp
+// "Additive second digit"), packed 32 + 32 words. Per prime and element: the
+// first window's row is the start value (e, 0, lhat); each further window's
+// row is fetched in one visit - e by LDS-DMA into the wave's image and
+// unpacked into limbs, lhat into registers and added to the lane's log sum,
+// which lives in the upper quads of the lane's slot - and e is multiplied in
+// (nwin - 1 row products, 4 K^2 mads each); the sum is folded into c
+// (PMD::finish) and the result goes back to the 74-limb Montgomery form (R a
+// + P c = h^a R^2 mod P^2, to_mont2) for the two Montgomery products that
+// bring in (1 + n m) and leave Montgomery form, exactly as in djn_prime_lds.
+// Output rows as k_djn_pow_lds (MP2 limbs, [prime][2 S4][count]) for
+// k_crt_enc_w.
 //
 // G > 1 (small batches, where the chip is not full and the chain of nwin
 // dependent products is the latency): G adjacent lanes share an element; lane
@@ -615,7 +621,8 @@ __global__ void __launch_bounds__(128, 2) k_djn_pow_lds(KeyDev key, const uint32
 // combined by a tree through the lanes' LDS slots (log2 G levels, the writer's
 // state streamed as the reader's operand), so the chain is ~nwin/G + log2 G
 // products; lane 0 of the group finishes. Products of Montgomery-digit states
-// are digit states of the product, so the result is the same residue.
+// are digit states of the product (the general PMD::mul on (a, c), the log
+// sums added), so the result is the same residue.
 template <class MP2, int KP, int RW, int G = 1>
 __global__ void __launch_bounds__(128, 2) k_djn_pmd(KeyDev key, const uint32_t* __restrict__ Pp,
                                                     const uint32_t* __restrict__ Pq, const uint32_t* __restrict__ Np2,
@@ -643,37 +650,55 @@ __global__ void __launch_bounds__(128, 2) k_djn_pmd(KeyDev key, const uint32_t* 
   const uint32_t* ae = a_words + (size_t)e * aw;
   D M;
   M.init(prime ? Pq : Pp, prime ? key.q.n0inv : key.p.n0inv);
-  auto stage = [&](int w) XHE_INL {
+  // One visit to a row: its e half by LDS-DMA into quads [0, RW/8) of the
+  // image (below the lanes' log sums, quads [D::EQ, NQ)) and its lhat half
+  // straight into registers; then sum += lhat (T1, T2 are dead here) and the
+  // e limbs unpacked for mul_row.
+  auto stage = [&](int w, auto first) XHE_INL {
     int64_t row0;
     const uint32_t d = win_digit(key, ae, aw, w, row0);
     const uint32_t* row = tab + (size_t)(row0 + d) * key.tab_rs;
 #pragma unroll
-    for (int k = 0; k < RW / 4; ++k)
+    for (int k = 0; k < RW / 8; ++k)
       __builtin_amdgcn_global_load_lds((xhe_glb_void*)(row + 4 * k), (xhe_lds_void*)(img + k * 256), 16, 0, 0);
+    uint32_t lam[RW / 2];
+#pragma unroll
+    for (int k = 0; k < RW / 8; ++k) {
+      const uint4 v = *reinterpret_cast<const uint4*>(row + RW / 2 + 4 * k);
+      lam[4 * k] = v.x, lam[4 * k + 1] = v.y, lam[4 * k + 2] = v.z, lam[4 * k + 3] = v.w;
+    }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    unpack_pairs_lds<KP, RW>(slot);
+    D::template lam_add<RW / 2, decltype(first)::value>(slot, lam);
+    unpack_e_lds<KP, RW / 2>(slot);
   };
   uint32_t a[KP], c[KP];
   if (G == 1 || g < key.nwin) {
-    stage(g);
+    stage(g, std::true_type{});  // the start value: (e, 0) and the row's lhat
 #pragma unroll
-    for (int q = 0; q < D::NQ; ++q) {
+    for (int q = 0; q < D::EQ; ++q) {
       const uint4 v = *reinterpret_cast<const uint4*>(slot + q * 256);
-      if (2 * q < KP) a[2 * q] = v.x, c[2 * q] = v.y;
-      if (2 * q + 1 < KP) a[2 * q + 1] = v.z, c[2 * q + 1] = v.w;
+      if (4 * q < KP) a[4 * q] = v.x;
+      if (4 * q + 1 < KP) a[4 * q + 1] = v.y;
+      if (4 * q + 2 < KP) a[4 * q + 2] = v.z;
+      if (4 * q + 3 < KP) a[4 * q + 3] = v.w;
     }
+#pragma unroll
+    for (int j = 0; j < KP; ++j) c[j] = 0u;
   }
   for (int w = g + G; w < key.nwin; w += G) {
-    stage(w);
-    M.mul(a, c, slot, topc);
+    stage(w, std::false_type{});
+    M.mul_row(a, c, slot, topc);
   }
   if constexpr (G > 1) {
-    // tree over the group: at level s, lane g + s (g a multiple of 2s) parks
-    // its state in its slot and lane g multiplies it in
+    // tree over the group: at level s, lane g takes the log sum of lane g + s
+    // (g a multiple of 2s), which then parks its state over its slot, and
+    // lane g multiplies it in (the general product on (a, c))
 #pragma unroll
     for (int s = 1; s < G; s <<= 1) {
       const bool writer = (g & (2 * s - 1)) == s && g < key.nwin;
       const bool reader = (g & (2 * s - 1)) == 0 && g + s < key.nwin;
+      if (reader) D::lam_add_slot(slot, slot + 4 * s);
+      wave_sync_mem_();
       if (writer) {
 #pragma unroll
         for (int q = 0; q < D::NQ; ++q)
@@ -687,6 +712,8 @@ __global__ void __launch_bounds__(128, 2) k_djn_pmd(KeyDev key, const uint32_t* 
     }
     if (g != 0) return;
   }
+  M.finish(a, c, slot, prime ? Pq : Pp);  // the log sum folded into c: the pair form again
+  __builtin_amdgcn_sched_barrier(0);
   {
     uint32_t x[2 * KP];
     M.to_mont2(a, c, x);  // h^a R^2 mod P^2, unreduced (< 2^13 P^2)
@@ -1321,49 +1348,6 @@ __global__ void __launch_bounds__(128, 2) k_nodjn_pmd_out(KeyDev key, const uint
   N.mul(b, ALdsQ{slot});                          // (1 + n m) r^e mod P^2
   N.reduce_once(b);
   N.store_strided(b, rows + (size_t)prime * 2 * MP2::S4 * count + e, (int)count);
-}
-
-// Rewrite packed fixed-base table rows X = x R^2 mod P^2 (the 74-limb
-// Montgomery form k_tab_combine writes, RW words) as their Montgomery digits
-// (e, f) < P, RW/2 words each (pdigit_dev.hpp pmd_from_mont2). One thread per
-// row, in place; once per key after the table build.
-template <int KP, int RW>
-__global__ void __launch_bounds__(256, 2) k_tab_to_pmd(const uint32_t* __restrict__ P, uint32_t n0inv,
-                                                       const uint32_t* __restrict__ RmodP, uint32_t* __restrict__ tab,
-                                                       int64_t rows, int64_t rs) {
-  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (r >= rows) return;
-  uint32_t* row = tab + (size_t)r * rs;
-  uint32_t w[RW];
-#pragma unroll
-  for (int q = 0; q < RW / 4; ++q) {
-    const uint4 v = reinterpret_cast<const uint4*>(row)[q];
-    w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
-  }
-  uint32_t X[2 * KP];
-#pragma unroll
-  for (int l = 0; l < 2 * KP; ++l) {
-    const int bit = 28 * l, k = bit >> 5, sh = bit & 31;
-    const uint32_t lo = word_or0(w, k, RW), hi = word_or0(w, k + 1, RW);
-    X[l] = __builtin_amdgcn_alignbit(hi, lo, sh) & ((1u << 28) - 1u);
-  }
-  PMD<KP> M;
-  M.init(P, n0inv);
-  uint32_t e[KP], f[KP];
-  pmd_from_mont2<KP>(M, X, RmodP, e, f);
-  auto word = [&](const uint32_t (&l)[KP], int k) -> uint32_t {
-    const int bit = 32 * k, j = bit / 28, sh = bit - 28 * j;
-    uint64_t v = (uint64_t)l[j] >> sh;
-    if (j + 1 < KP) v |= (uint64_t)l[j + 1] << (28 - sh);
-    if (j + 2 < KP) v |= (uint64_t)l[j + 2] << (56 - sh);
-    return (uint32_t)v;
-  };
-#pragma unroll
-  for (int q = 0; q < RW / 8; ++q) {
-    reinterpret_cast<uint4*>(row)[q] = make_uint4(word(e, 4 * q), word(e, 4 * q + 1), word(e, 4 * q + 2), word(e, 4 * q + 3));
-    reinterpret_cast<uint4*>(row)[RW / 8 + q] =
-        make_uint4(word(f, 4 * q), word(f, 4 * q + 1), word(f, 4 * q + 2), word(f, 4 * q + 3));
-  }
 }
 
 // c = c_q + q^2 ((c_p + 4p^2 - c_q) (q^2)^-1 mod p^2) for element e (utils.py:38-43)
@@ -2577,6 +2561,76 @@ __global__ void __launch_bounds__(256, 2) k_tab_combine(ModDev md, const uint32_
   M.store_row(b, sc);
   wave_sync_mem_();
   pack_words_<MP2::W, MP2::TPI>(sc, 1, MP2::S, tab + (size_t)idx * rs, RW);
+}
+
+// Rewrite packed fixed-base table rows X = x R^2 mod P^2 (the 74-limb
+// Montgomery form k_tab_combine writes, RW words) as the first Montgomery
+// digit e < P and the log digit lhat = f y^-1 mod P < P of the row's pair
+// (e, f) (pdigit_dev.hpp pmd_from_mont2, "Additive second digit"), RW/2 words
+// each. y^-1 mod P is not inverted per row: it is the same table entry for
+// the base h^-1 mod P, the product of a high and a low entry of `inv`, the
+// chains k_tab_bases / k_tab_one / k_tab_level build in the mod-P shape MP
+// from h^-1 R mod P ([window][chain_rows] rows of MP::S4 limbs; the wide
+// windows' chains first, as the table's rows). So lhat is two Montgomery
+// products mod P, f by the high and by the low entry (an entry 0 is R, the
+// Montgomery one). One thread per row, in place; once per key after the
+// table build.
+template <class MP, int RW>
+__global__ void __launch_bounds__(256, 2) k_tab_to_pmd(ModDev mp, const uint32_t* __restrict__ P,
+                                                       const uint32_t* __restrict__ inv, int win, int nhi,
+                                                       uint32_t* __restrict__ tab, int64_t rows, int64_t rs) {
+  static_assert(MP::TPI == 1 && MP::W == 28, "one lane per row on the digit limbs");
+  constexpr int KP = MP::S;
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= rows) return;
+  uint32_t* row = tab + (size_t)r * rs;
+  uint32_t w[RW];
+#pragma unroll
+  for (int q = 0; q < RW / 4; ++q) {
+    const uint4 v = reinterpret_cast<const uint4*>(row)[q];
+    w[4 * q] = v.x, w[4 * q + 1] = v.y, w[4 * q + 2] = v.z, w[4 * q + 3] = v.w;
+  }
+  uint32_t X[2 * KP];
+#pragma unroll
+  for (int l = 0; l < 2 * KP; ++l) {
+    const int bit = 28 * l, k = bit >> 5, sh = bit & 31;
+    const uint32_t lo = word_or0(w, k, RW), hi = word_or0(w, k + 1, RW);
+    X[l] = __builtin_amdgcn_alignbit(hi, lo, sh) & ((1u << 28) - 1u);
+  }
+  PMD<KP> M;
+  M.init(P, mp.n0inv);
+  uint32_t e[KP], f[KP];
+  pmd_from_mont2<KP>(M, X, mp.R1, e, f);
+  __builtin_amdgcn_sched_barrier(0);
+  {
+    // the row's window and digit (win_digit's layout), its chain entries
+    const int64_t wide = (int64_t)nhi << (win + 1);
+    const bool hiw = r < wide;
+    const int wb = win + (hiw ? 1 : 0), half = wb / 2;
+    const int64_t rr = hiw ? r : r - wide;
+    const int64_t d = rr & (((int64_t)1 << wb) - 1);
+    const uint32_t* cw = inv + ((size_t)(rr >> wb) * chain_rows(wb) + (hiw ? 0 : (size_t)nhi * chain_rows(win + 1))) * MP::S4;
+    const int64_t lo = d & (((int64_t)1 << half) - 1), hi = d >> half;
+    MP N;
+    N.init(P, mp.n0inv);
+    N.mul(f, ARow{cw + (size_t)(hi ? chain_index(hi, half, half) : 0) * MP::S4});
+    N.reduce_once(f);
+    N.mul(f, ARow{cw + (size_t)chain_index(lo, 0, half) * MP::S4});
+    N.reduce_once(f);
+  }
+  auto word = [&](const uint32_t (&l)[KP], int k) -> uint32_t {
+    const int bit = 32 * k, j = bit / 28, sh = bit - 28 * j;
+    uint64_t v = (uint64_t)l[j] >> sh;
+    if (j + 1 < KP) v |= (uint64_t)l[j + 1] << (28 - sh);
+    if (j + 2 < KP) v |= (uint64_t)l[j + 2] << (56 - sh);
+    return (uint32_t)v;
+  };
+#pragma unroll
+  for (int q = 0; q < RW / 8; ++q) {
+    reinterpret_cast<uint4*>(row)[q] = make_uint4(word(e, 4 * q), word(e, 4 * q + 1), word(e, 4 * q + 2), word(e, 4 * q + 3));
+    reinterpret_cast<uint4*>(row)[RW / 8 + q] =
+        make_uint4(word(f, 4 * q), word(f, 4 * q + 1), word(f, 4 * q + 2), word(f, 4 * q + 3));
+  }
 }
 
 // Montgomery product of two rows (host-side setup helper / unit tests):
