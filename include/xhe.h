@@ -287,6 +287,18 @@ int xhe_zstd_raw_extract(const uint8_t* src, int64_t len, uint8_t* dst, int64_t 
  * arrays of the drop-in (Paillier.encrypt's return, paillier.py:289-339). */
 int xhe_host_prefault(void* p, int64_t nbytes);
 
+/* Key-prime search (utils.py:79-89 getprimeover -> gmpy2.next_prime): the
+ * base-2 Fermat test of `count` candidates N_i = starts[which[i]] + offs[i]
+ * (starts: nstarts rows of bits/32 little-endian words; host pointers), one
+ * lane group per candidate with its own modulus. Needs no key.
+ * bits is a prime width the build has: 1024, 1536, 2048, 4096 (half of each
+ * key size; a -D XHE_ONLY_BITS=K build has K/2 only, else XHE_ENOTSUP).
+ * Every N_i must be odd with 2^(bits-1) <= N_i < 2^bits, else XHE_EINVAL and
+ * nothing is launched. pass[i] = 1 iff 2^(N_i - 1) == 1 (mod N_i), else 0.
+ * Timed as "k_fermat2" under xhe_profile. */
+int xhe_fermat2_host(int device, int bits, const uint32_t* starts, int nstarts, const int32_t* which,
+                     const uint32_t* offs, int64_t count, uint8_t* pass);
+
 /* Kernel timing: when enabled, the library brackets each launch of its
  * dominant kernels (k_djn_pow, k_dec_pow) with hipEvents on the launch stream.
  * xhe_profile(1) enables and clears, xhe_profile(0) disables and clears;

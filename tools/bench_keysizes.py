@@ -3,8 +3,9 @@ DJN-CRT encrypt (encode + draw + encrypt, precision 7, obfuscated) and CRT
 decrypt of the same ciphertexts, with the round trip checked bit-exactly.
 
 Keys are the reference-generated fixture keys (tests/golden/paillier_K_djn.json)
-so no host key generation runs here (pure-Python keygen of an 8192-bit DJN
-key takes minutes).
+so the rates are those of known keys and no key generation runs here (an
+8192-bit DJN key takes tens of seconds of host GMP, or a few seconds with the
+device prime search: tools/bench_keygen.py).
 
     python tools/bench_keysizes.py [--bits 2048,3072,4096,8192] > profiles/r1/keysizes.jsonl
 """

@@ -96,6 +96,7 @@ SIGNATURES = {
     "xhe_zstd_raw_frame": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
     "xhe_zstd_raw_extract": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, ctypes.c_int64,
                                             ctypes.POINTER(ctypes.c_int64)]),
+    "xhe_fermat2_host": (ctypes.c_int, [ctypes.c_int, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int64, _vp]),
     "xhe_profile": (ctypes.c_int, [ctypes.c_int]),
     "xhe_profile_read": (ctypes.c_int, [ctypes.c_char_p, ctypes.POINTER(ctypes.c_double),
                                         ctypes.POINTER(ctypes.c_int64)]),
@@ -370,6 +371,31 @@ def words_to_ints(w):
 
 def ptr(a):
     return a.ctypes.data_as(_u32p)
+
+
+def fermat2_rc(bits, starts, which, offs, device=0):
+    """xhe_fermat2_host on Python ints: (return code, verdicts). starts: ints
+    below 2^bits; candidate i is starts[which[i]] + offs[i]."""
+    nw = max(1, bits // 32)
+    sw = ints_to_words(starts, nw)
+    which = np.ascontiguousarray(which, dtype=np.int32)
+    offs = np.ascontiguousarray(offs, dtype=np.uint32)
+    if which.shape != offs.shape or which.ndim != 1:
+        raise ValueError("fermat2: which and offs must be 1-D arrays of one length")
+    out = np.zeros(len(offs), dtype=np.uint8)
+    rc = lib().xhe_fermat2_host(device, bits, sw.ctypes.data, len(starts), which.ctypes.data, offs.ctypes.data,
+                                len(offs), out.ctypes.data)
+    return rc, out
+
+
+def fermat2(bits, starts, which, offs, device=0):
+    """Base-2 Fermat verdicts (bool array) of the candidates starts[which[i]] +
+    offs[i] of `bits` bits; None when the loaded build lacks that width."""
+    rc, out = fermat2_rc(bits, starts, which, offs, device)
+    if rc == XHE_ENOTSUP:
+        return None
+    check(rc, "xhe_fermat2_host")
+    return out.astype(bool)
 
 
 TABLE_ROW_WORDS = {2048: 64, 3072: 96, 4096: 128, 8192: 256}  # packed rows: xhe.hip Shape<K>::RW = K/32

@@ -22,6 +22,7 @@
 #include "hostbn.hpp"
 #include "keyconst.hpp"
 #include "xhe_kernels.hpp"
+#include "fermat_dev.hpp"
 #include "dec_wave.hpp"
 #include "barrett_dev.hpp"
 #include "rns_dev.hpp"
@@ -156,6 +157,28 @@ decltype(auto) with_shape(int K, F&& f) {
 // Shapes that only 2048-bit keys have:
 using ND2048 = PMDX<80, 4>;           // Montgomery digits mod n^2 (k_ndig_*, k_djn_pub_nd)
 using WaveN2 = WaveMont<154, 16, 27>;  // one-block products mod n^2 (k_*_wave<WaveN2::K_, 16>)
+
+// Prime search (k_fermat2, fermat_dev.hpp): a candidate prime of K/2 bits per
+// lane group, the shapes with the fewest limbs per lane (L = 5, 7, 5, 10):
+// the launch is as long as one candidate's chain of squarings.
+constexpr bool fermat_bits_supported(int bits) { return key_bits_supported(2 * bits); }
+template <int B>
+using FermatBits = std::integral_constant<int, B>;
+template <class F>
+void with_fermat_shape(int bits, F&& f) {
+#ifdef XHE_ONLY_BITS
+  (void)bits;
+  if constexpr (XHE_ONLY_BITS == 2048) f(Mont<40, 28, 8>{}, FermatBits<1024>{});
+  else if constexpr (XHE_ONLY_BITS == 3072) f(Mont<56, 28, 8>{}, FermatBits<1536>{});
+  else if constexpr (XHE_ONLY_BITS == 4096) f(Mont<80, 28, 16>{}, FermatBits<2048>{});
+  else f(Mont<160, 27, 16>{}, FermatBits<4096>{});
+#else
+  if (bits == 1024) f(Mont<40, 28, 8>{}, FermatBits<1024>{});
+  else if (bits == 1536) f(Mont<56, 28, 8>{}, FermatBits<1536>{});
+  else if (bits == 2048) f(Mont<80, 28, 16>{}, FermatBits<2048>{});
+  else f(Mont<160, 27, 16>{}, FermatBits<4096>{});
+#endif
+}
 
 // $XHE_NDIG_PUB=0: public DJN keys keep Montgomery n^2 tables (k_djn_pub; A/B)
 bool ndig_pub_on() {
@@ -2487,6 +2510,51 @@ int xhe_multiexp_host(const xhe_key* key, const uint32_t* bases, int64_t nbases,
                           win_bits, dout.as<uint32_t>(), st.s);
     if (rc != XHE_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)ncols * key->n2w * 4, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    return XHE_OK;
+  });
+}
+
+int xhe_fermat2_host(int device, int bits, const uint32_t* starts, int nstarts, const int32_t* which,
+                     const uint32_t* offs, int64_t count, uint8_t* pass) {
+  return guarded([&]() -> int {
+    if (bits <= 0 || bits % 32 || !fermat_bits_supported(bits))
+      return fail(XHE_ENOTSUP, "xhe_fermat2_host: prime width " + std::to_string(bits) + " not built");
+    if (count < 0 || count > (int64_t)1 << 24 || nstarts <= 0 || !starts || (count > 0 && (!which || !offs || !pass)))
+      return fail(XHE_EINVAL, "xhe_fermat2_host: bad argument");
+    if (count == 0) return XHE_OK;
+    const int nw = bits / 32;
+    // per start: top bit set; do the words above the lowest all carry on?
+    std::vector<uint8_t> ripples((size_t)nstarts);
+    for (int s = 0; s < nstarts; ++s) {
+      const uint32_t* w = starts + (size_t)s * nw;
+      if (!(w[nw - 1] >> 31)) return fail(XHE_EINVAL, "xhe_fermat2_host: a start is below 2^(bits-1)");
+      bool ones = true;
+      for (int k = 1; k < nw; ++k) ones = ones && w[k] == 0xffffffffu;
+      ripples[s] = ones;
+    }
+    for (int64_t i = 0; i < count; ++i) {
+      if (which[i] < 0 || which[i] >= nstarts) return fail(XHE_EINVAL, "xhe_fermat2_host: start index out of range");
+      const uint32_t lo = starts[(size_t)which[i] * nw], sum = lo + offs[i];
+      if (!(sum & 1u)) return fail(XHE_EINVAL, "xhe_fermat2_host: an even candidate");
+      if (sum < lo && ripples[which[i]]) return fail(XHE_EINVAL, "xhe_fermat2_host: a candidate reaches 2^bits");
+    }
+    DevGuard dg(device);
+    Stream st;
+    const size_t sb = (size_t)nstarts * nw * 4, cb = (size_t)count * 4;
+    DevBuf ds(sb, st.s), dw(cb, st.s), dof(cb, st.s), dp((size_t)count, st.s);
+    HIPCHK(hipMemcpyAsync(ds.p, starts, sb, hipMemcpyHostToDevice, st.s));
+    HIPCHK(hipMemcpyAsync(dw.p, which, cb, hipMemcpyHostToDevice, st.s));
+    HIPCHK(hipMemcpyAsync(dof.p, offs, cb, hipMemcpyHostToDevice, st.s));
+    with_fermat_shape(bits, [&](auto m, auto width) {
+      using M = decltype(m);
+      constexpr int BITS = decltype(width)::value;
+      const int64_t gpw = 64 / M::TPI;  // candidates per wave
+      ProfScope ps("k_fermat2", st.s);
+      launch((k_fermat2<M, BITS>), dim3((unsigned)((count + gpw - 1) / gpw)), dim3(64), st.s, ds.as<uint32_t>(),
+             dw.as<int32_t>(), dof.as<uint32_t>(), count, dp.as<uint8_t>());
+    });
+    HIPCHK(hipMemcpyAsync(pass, dp.p, (size_t)count, hipMemcpyDeviceToHost, st.s));
     HIPCHK(hipStreamSynchronize(st.s));
     return XHE_OK;
   });

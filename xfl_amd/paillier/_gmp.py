@@ -32,6 +32,7 @@ def _load():
                               ("__gmpz_get_str", ctypes.c_char_p, [ctypes.c_char_p, ctypes.c_int, P]),
                               ("__gmpz_sizeinbase", ctypes.c_size_t, [P, ctypes.c_int]),
                               ("__gmpz_nextprime", None, [P, P]),
+                              ("__gmpz_probab_prime_p", ctypes.c_int, [P, ctypes.c_int]),
                               ("__gmpz_powm", None, [P, P, P, P])):
             f = getattr(lib, fn)
             f.restype = res
@@ -74,6 +75,13 @@ def next_prime(x):
     a, r = _Z(x), _Z()
     _F["nextprime"](ctypes.byref(r.z), ctypes.byref(a.z))
     return r.value()
+
+
+def probab_prime(x, reps=25):
+    """mpz_probab_prime_p(x, reps) != 0: the test mpz_nextprime applies (with
+    reps = 25) to the candidates its sieve leaves."""
+    a = _Z(x)
+    return _F["probab_prime_p"](ctypes.byref(a.z), reps) != 0
 
 
 def powmod(b, e, m):

@@ -77,12 +77,13 @@ class PaillierContext(object):
         return self
 
     @classmethod
-    def generate(cls, key_bit_size: int = 2048, djn_on: bool = False):
-        """context.py:73-84"""
-        p, q = cls._generate_paillier_private_key(key_bit_size, djn_on)
+    def generate(cls, key_bit_size: int = 2048, djn_on: bool = False, rng=None):
+        """context.py:73-84. rng (default: the system's) draws the prime
+        starts and the DJN base, for reproducible keys in tests and tools."""
+        p, q = cls._generate_paillier_private_key(key_bit_size, djn_on, rng=rng)
         if djn_on:
             n = p * q
-            x = secrets.SystemRandom().getrandbits(n.bit_length())
+            x = (rng or secrets.SystemRandom()).getrandbits(n.bit_length())
             x |= 1 << (n.bit_length() - 1)
             h = -pow(x, 2)
             from . import _gmp
@@ -127,8 +128,15 @@ class PaillierContext(object):
         return pub_context
 
     @staticmethod
-    def _generate_paillier_private_key(n_length: int = 2048, djn_on: bool = False, seed: Optional[int] = None):
-        """context.py:123-150 (DJN keys need gcd(p-1, q-1) = 2)."""
+    def _generate_paillier_private_key(n_length: int = 2048, djn_on: bool = False, seed: Optional[int] = None,
+                                       rng=None):
+        """context.py:123-150 (DJN keys need gcd(p-1, q-1) = 2). Where
+        $XHE_KEYGEN selects the device (primes.keygen_on_device), both starts
+        of a round are drawn first, in the reference's order and with its
+        top-bit rule, and searched in one primes.next_primes call; the primes
+        are the ones the host search finds from the same draws."""
+        from .primes import device_ready, keygen_on_device, next_primes
+        on_device = keygen_on_device(n_length // 2)
         p, q = None, None
         if djn_on:
             def f(x, y):
@@ -137,8 +145,14 @@ class PaillierContext(object):
             def f(x, y):
                 return x == y
         while f(p, q):
-            p = getprimeover(n_length // 2)
-            q = getprimeover(n_length // 2)
+            if on_device:
+                draw = rng or secrets.SystemRandom()
+                half = n_length // 2
+                starts = [draw.getrandbits(half) | (1 << (half - 1)) for _ in range(2)]
+                p, q = next_primes(starts, device=PaillierContext.own_device() if device_ready() else 0)
+                continue
+            p = getprimeover(n_length // 2, rng=rng)
+            q = getprimeover(n_length // 2, rng=rng)
         return p, q
 
     def serialize(self, save_private_key: bool = True):

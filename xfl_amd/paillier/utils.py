@@ -78,10 +78,16 @@ def is_probable_prime(n, rounds=32, rng=None):
     return True
 
 
-def next_prime(x, rng=None):
+def next_prime(x, rng=None, device=None):
     """Smallest probable prime > x (gmpy2.next_prime semantics): GMP's
-    mpz_nextprime when libgmp is present (what gmpy2 calls), else Miller-Rabin."""
+    mpz_nextprime when libgmp is present (what gmpy2 calls), else Miller-Rabin.
+    With device = a GPU index the candidates are tested on that GPU
+    (primes.next_primes: the same integer; the host serves what the device
+    cannot)."""
     from . import _gmp
+    if device is not None:
+        from .primes import next_primes
+        return next_primes([x], device=device)[0]
     if _gmp.available() and x >= 0:
         return _gmp.next_prime(int(x))
     n = x + 1
@@ -94,8 +100,8 @@ def next_prime(x, rng=None):
     return n
 
 
-def getprimeover(n, seed: Optional[int] = None, rng=None):
+def getprimeover(n, seed: Optional[int] = None, rng=None, device=None):
     """utils.py:79-89: random n-bit number with the top bit set -> next_prime."""
     rng = rng or secrets.SystemRandom()
     r = rng.getrandbits(n) | (1 << (n - 1))
-    return next_prime(r, rng=rng)
+    return next_prime(r, rng=rng, device=device)
