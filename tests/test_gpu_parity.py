@@ -17,24 +17,29 @@ def _dkey(g, private=True):
     return DeviceKey(g["key_bits"], hx(k["n"]), None, None, h)
 
 
+_okeys = {}
+
+
 def _okey(g):
     k = g["key"]
-    return O.derive_private(hx(k["p"]), hx(k["q"]), hx(k["h_pow_n"]) if k["djn_on"] else None)
+    if k["n"] not in _okeys:  # (an 8192-bit derivation takes Python a second)
+        _okeys[k["n"]] = O.derive_private(hx(k["p"]), hx(k["q"]), hx(k["h_pow_n"]) if k["djn_on"] else None)
+    return _okeys[k["n"]]
 
 
 ENC_CASES = ["priv_f32_p7", "priv_f64_none", "priv_packed_p0", "pub_f32_p7", "pub_f64_none_max-60",
              "pub_i32_none", "priv_edge_p7_noobf"]
 
 
-@pytest.mark.parametrize("fx", FIXTURES)
-@pytest.mark.parametrize("case", ENC_CASES)
-def test_encrypt_bit_exact(fx, case):
-    """Every encryption mode (DJN/non-DJN x private CRT/public, obfuscated or
-    not) with the reference's recorded obfuscation draws."""
+DEC_CASES = ["priv_f32_p7", "pub_f32_p7", "priv_f64_none", "priv_packed_p0", "priv_edge_p7_noobf", "pub_i32_none"]
+
+
+def check_encrypt_case(g, case, dk):
+    """the golden case of fixture g encrypts on the device key dk to the
+    reference's ciphertexts (also run by tests/test_gpu_key_structure.py on
+    keys with p and q exchanged)"""
     from xfl_amd._native import ints_to_words, words_to_ints
-    g = load_fixture(fx)
     c = g["encrypt"][case]
-    dk = _dkey(g, private=c["private"])
     ok = _okey(g)
     xs = [hx(v) for v in c["input"]] if c["kind"] == "int" else [float.fromhex(v) for v in c["input"]]
     ms = [O.encode_element(ok, x, c["precision"], c["max_exponent"])[0] for x in xs]
@@ -44,19 +49,31 @@ def test_encrypt_bit_exact(fx, case):
     assert out == [hx(r) for r in c["raw"]]
 
 
-@pytest.mark.parametrize("fx", FIXTURES)
-@pytest.mark.parametrize("case", ["priv_f32_p7", "pub_f32_p7", "priv_f64_none", "priv_packed_p0",
-                                  "priv_edge_p7_noobf", "pub_i32_none"])
-def test_decrypt_bit_exact(fx, case):
+def check_decrypt_case(g, case, dk):
+    """the golden ciphertexts of the case decrypt on dk to the reference's m"""
     from xfl_amd._native import ints_to_words, words_to_ints
-    g = load_fixture(fx)
-    dk = _dkey(g)
     enc = g["encrypt"][case]
     dec = g["decrypt"][case]
     ms = dec["m"][len(dec["m"]) - len(enc["raw"]):]
     cw = ints_to_words([hx(r) for r in enc["raw"]], dk.n2w)
     out = words_to_ints(dk.decrypt_words(cw))
     assert out == [hx(m) for m in ms]
+
+
+@pytest.mark.parametrize("fx", FIXTURES)
+@pytest.mark.parametrize("case", ENC_CASES)
+def test_encrypt_bit_exact(fx, case):
+    """Every encryption mode (DJN/non-DJN x private CRT/public, obfuscated or
+    not) with the reference's recorded obfuscation draws."""
+    g = load_fixture(fx)
+    check_encrypt_case(g, case, _dkey(g, private=g["encrypt"][case]["private"]))
+
+
+@pytest.mark.parametrize("fx", FIXTURES)
+@pytest.mark.parametrize("case", DEC_CASES)
+def test_decrypt_bit_exact(fx, case):
+    g = load_fixture(fx)
+    check_decrypt_case(g, case, _dkey(g))
 
 
 def test_host_encrypt_chunking_is_invisible():

@@ -6,8 +6,10 @@ with ASan + UBSan like test_host_sanitize.py's harness, started as a separate
 process) derives the image of a key, binds it to the host vector and prints
 every KeyDev field with the limbs it points at. This module rebuilds Python
 integers from the limbs and checks each constant against int/pow, for the five
-golden keys in private form and the 2048-bit DJN key also in public form, and
-that a field is present (non-null, 16-byte aligned, inside the blob, disjoint
+golden keys in private form and the 2048-bit DJN key also in public form, for
+the structured keys of tests/structured_keys.py whose primes sit at the ends of
+their range (2048 bits: top, bottom and pattern; 3072 bits: bottom; as private
+DJN keys), and that a field is present (non-null, 16-byte aligned, inside the blob, disjoint
 from every other) exactly when a key of that size and kind uses it.
 
 The RNS blocks' contents stay with tests/test_rns_constants.py.
@@ -32,10 +34,24 @@ XHE_WIN_SPLIT = 0x100
 # (fixture, private, window): the split layout on the key whose production window uses it
 CASES = [(fx, True, 23 | XHE_WIN_SPLIT if fx == "paillier_2048_djn.json" else 16) for fx in FIXTURES]
 CASES.append(("paillier_2048_djn.json", False, 16))
+# structured_<bits>_<name>: tests/structured_keys.key(bits, name) as a private DJN key
+CASES += [(f"structured_2048_{name}", True, 16) for name in ("top", "bottom", "pattern")]
+CASES.append(("structured_3072_bottom", True, 16))
 
 
 def _key_bits(fixture):
-    return int(fixture.split("_")[1])  # paillier_<bits>_...
+    return int(fixture.split("_")[1])  # paillier_<bits>_... / structured_<bits>_...
+
+
+def _load_key(fixture):
+    """the fixture's key record; for a structured key the same fields from structured_keys and the oracle"""
+    if not fixture.startswith("structured_"):
+        return load_fixture(fixture)["key"]
+    from oracle import paillier_oracle as O
+    from tests import structured_keys as SK
+    k = SK.key(_key_bits(fixture), fixture.split("_", 2)[2])
+    return {"n": hex(k.n), "p": hex(k.p), "q": hex(k.q), "djn_on": True, "h_pow_n": hex(k.h),
+            "hp": hex(O.derive_private(k.p, k.q, k.h)["hp"])}
 
 
 @pytest.fixture(scope="module")
@@ -101,7 +117,7 @@ _images = {}
 def _image(case, program):
     fx, priv, win = case
     if case not in _images:
-        k = load_fixture(fx)["key"]
+        k = _load_key(fx)
         n, p, q = hx(k["n"]), hx(k["p"]), hx(k["q"])
         djn = bool(k["djn_on"])
         h = hx(k["h_pow_n"]) if djn else None
@@ -121,7 +137,8 @@ def _image(case, program):
 def _cases(keep):
     """A fixture over the cases `keep` selects (the image of a key is derived once per module)."""
     @pytest.fixture(params=[c for c in CASES if keep(_key_bits(c[0]), c[1])],
-                    ids=lambda c: f"{c[0][9:-5]}-{'priv' if c[1] else 'pub'}-w{c[2] & 0xff}")
+                    ids=lambda c: f"{c[0][9:-5] if c[0].endswith('.json') else c[0][11:]}-"
+                                  f"{'priv' if c[1] else 'pub'}-w{c[2] & 0xff}")
     def fixture(request, program):
         return _image(request.param, program)
     return fixture

@@ -5,7 +5,12 @@ base extensions per product summed in two halves, the DPP partial sums, the
 exit's columns and the reduction mod P^2 - emulated in numpy on those blocks,
 through a whole c^(P-1) mod P^2 on the kernel's window schedule against
 Python's pow. The model itself is checked against Python integers (bounds,
-exactness) by its own asserts."""
+exactness) by its own asserts.
+
+Besides the fixture primes, both primes of the structured 2048-bit keys of
+tests/structured_keys.py: `top` (P - 1 nearly all ones: the most windows),
+`bottom` (P - 1 one run of 1,012 zeros: a squaring count far beyond the
+20 or so of a random prime, in the schedule's `sq << 8` field) and `pattern`."""
 import ctypes
 import os
 import sys
@@ -54,11 +59,23 @@ def test_header_sizes():
     assert f"#define XHE_RNS_SHARED_WORDS {S_WORDS}" in hdr and f"#define XHE_RNS_PRIME_WORDS {P_WORDS}" in hdr
 
 
-@pytest.mark.parametrize("fx", ["paillier_2048_djn.json", "paillier_2048_nodjn.json"])
-def test_constants_match_model(model, fx):
+STRUCTURED = ["top", "bottom", "pattern"]
+
+
+def _primes(fx):
+    """(p, q) of a fixture file or of the structured 2048-bit key of that name"""
+    if fx in STRUCTURED:
+        from tests import structured_keys as SK
+        k = SK.key(2048, fx)
+        return k.p, k.q
     k = load_fixture(fx)["key"]
+    return hx(k["p"]), hx(k["q"])
+
+
+@pytest.mark.parametrize("fx", ["paillier_2048_djn.json", "paillier_2048_nodjn.json"] + STRUCTURED)
+def test_constants_match_model(model, fx):
     shoup = lambda w, m: (w << 32) // m  # noqa: E731
-    for P in (hx(k["p"]), hx(k["q"])):
+    for P in _primes(fx):
         sh, pb = _blocks(P)
         mk = model.Key(P)
         for slot in range(NSLOT):
@@ -208,13 +225,15 @@ class _Kernel:
         return X % N
 
 
-@pytest.mark.parametrize("fx", ["paillier_2048_djn.json"])
+@pytest.mark.parametrize("fx", ["paillier_2048_djn.json"] + [f"{s}-{x}" for s in STRUCTURED for x in "pq"])
 def test_kernel_emulation_exponentiation(fx):
-    k = load_fixture(fx)["key"]
-    P = hx(k["p"])
+    fx, _, which = fx.partition("-")  # the fixture's p; a structured key's p or q
+    P = _primes(fx)[which == "q"]
     N = P * P
     sh, pb = _blocks(P)
     kern = _Kernel(sh, pb)
+    if fx == "bottom":  # the long run of squarings is one schedule entry
+        assert max(w >> 8 for w in kern.sched[1:]) >= 1000
     rng = np.random.default_rng(3)
     c = int.from_bytes(rng.bytes(512), "little")
     m = kern.m.astype(object)
