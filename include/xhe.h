@@ -73,6 +73,24 @@ int xhe_rand(const xhe_key* key, const uint8_t* seed32, uint64_t nonce, int64_t 
 int xhe_encrypt(const xhe_key* key, const uint32_t* m_dev, const uint32_t* rand_dev, int64_t count,
                 uint32_t* ct_dev, void* stream);
 
+/* Offline / online split of the obfuscated encryption. The factor X that
+ * xhe_encrypt multiplies in (h^a for DJN keys, r^n otherwise) does not depend
+ * on the plaintext: xhe_obf_fill makes obfuscators ahead of time, with the
+ * kernels, tables and batch-size policy of xhe_encrypt (it is xhe_encrypt of
+ * m = 0), and xhe_encrypt_obf finishes an encryption on one in a single
+ * launch for every key mode: with x0 = X mod n and t = m x0 mod n,
+ * ct = X + n t (- n^2 when it reaches it) = (1 + n m) X mod n^2 - two
+ * products mod n and one wide product, no product mod n^2. Any X < n^2 is
+ * accepted. An obfuscator must be used once: wipe != 0 zeroes its row in the
+ * same launch. Timed as "k_enc_obf" under xhe_profile.
+ * obf[i] = the factor xhe_encrypt would multiply in for rand[i] (= xhe_encrypt of m = 0) */
+int xhe_obf_fill(const xhe_key* key, const uint32_t* rand_dev, int64_t count, uint32_t* obf_dev, void* stream);
+/* ct[i] = (1 + n m[i]) * obf[i] mod n^2, one launch; wipe != 0 zeroes obf[i] after use.
+ * m: nw words per element (m < n), obf and ct: n2w words per element;
+ * XHE_EINVAL when count < 0 or ct overlaps obf. */
+int xhe_encrypt_obf(const xhe_key* key, const uint32_t* m_dev, uint32_t* obf_dev, int64_t count, int wipe,
+                    uint32_t* ct_dev, void* stream);
+
 /* Paillier._decrypt_single arithmetic (paillier.py:341-366): ct -> encoded m. */
 int xhe_decrypt(const xhe_key* key, const uint32_t* ct_dev, int64_t count, uint32_t* m_dev, void* stream);
 

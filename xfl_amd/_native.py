@@ -40,6 +40,8 @@ SIGNATURES = {
                                       _vp, _vp, _vp, _vp]),
     "xhe_rand": (ctypes.c_int, [_vp, ctypes.c_char_p, ctypes.c_uint64, ctypes.c_int64, _vp, _vp, _vp]),
     "xhe_encrypt": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp]),
+    "xhe_obf_fill": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp]),
+    "xhe_encrypt_obf": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp]),
     "xhe_decrypt": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp]),
     "xhe_decode": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, _vp, _vp, _vp]),
     "xhe_embed_f64": (ctypes.c_int, [_vp, _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, _vp,

@@ -7,7 +7,10 @@
 // Every constant is stored together with the KeyDev field that will point at
 // it (KeyImage::put*), so a constant cannot be stored without being bound and
 // a field never stored stays null. The order of the put calls is the blob's
-// layout (alignment, which constants share cache lines): append only.
+// layout (alignment, which constants share cache lines): append only, inside
+// a family - the blob ends with a constant tests/native/keyconst_check.cpp
+// names (tests/test_keyconst.py test_presence), so a new family goes before
+// the last put of n2_constants, as k_enc_obf's did.
 #pragma once
 #include <algorithm>
 #include <cstdint>
@@ -432,6 +435,11 @@ inline void n2_constants(KeyImage& im, const KeySpec& s, const BigU& n, const Bi
     im.put_limbs(mulmod(Rw2, modinv(mod(s.mn2X.R(), n2), n2), n2), sw, &KeyDev::n2w_C);
     im.put_limbs(Rw2, sw, &KeyDev::n2w_R2);
   }
+  // k_enc_obf: x0 = X mod n and t = m x0 mod n are Montgomery products mod n
+  // in the 4-lane shape (R >= 16 n as for p^2, both below 2^K); n^2 in 2 S of
+  // its limbs for the last compare-and-subtract
+  im.put_mod(n, s.mp2L, &KeyDev::nL);
+  im.put_limbs(n2, ModSpec{2 * s.mp2L.S, s.mp2L.W}, &KeyDev::n2_limL);
   const BigU Rn2 = mod(s.mn2.R(), n2);
   im.put_limbs(mulmod(n, mulmod(Rn2, Rn2, n2), n2), s.mn2, &KeyDev::nR2_n2);
   if (h_pub) im.put_limbs(mulmod(mod(*h_pub, n2), Rn2, n2), s.mn2, &im.hM_n2);  // public DJN table base

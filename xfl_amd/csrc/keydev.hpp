@@ -116,6 +116,11 @@ struct KeyDev {
   // ---- Barrett reduction mod n^2 (k_add_barrett, 2048-bit keys):
   // floor(2^(27*304) / n^2) as 153 limbs of 27 bits
   const uint32_t* n2_mu;
+  // ---- online encryption on a precomputed obfuscator (k_enc_obf,
+  // enc_obf_dev.hpp; every key): n itself as a Montgomery modulus in the
+  // 4-lane (p2L) limb shape, and n^2 as 2 S plain limbs of that shape
+  ModDev nL;
+  const uint32_t* n2_limL;
 };
 
 }  // namespace xhe

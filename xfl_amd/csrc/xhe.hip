@@ -26,6 +26,7 @@
 #include "dec_wave.hpp"
 #include "barrett_dev.hpp"
 #include "rns_dev.hpp"
+#include "enc_obf_dev.hpp"
 
 using namespace xhe;
 
@@ -2086,6 +2087,60 @@ int xhe_encrypt(const xhe_key* key, const uint32_t* m_dev, const uint32_t* rand_
     } else {
       with_shape(key->K, [&](auto sh) { encrypt_nodjn_impl<decltype(sh)>(key, m_dev, rand_dev, count, ct_dev, s); });
     }
+    return XHE_OK;
+  });
+}
+
+// Obfuscators ahead of time: xhe_encrypt's own dispatch on zero plaintexts
+// (1 + n 0 = 1, so the result is the factor itself). The zeros are one
+// workspace of at most kObfFillZeroBytes, reused pass by pass: 1 M elements a
+// pass at 2048 bits, the encryption's own launch chunk (with 64 MiB, four
+// launches of 256 k, a 1 M fill ran 10 % below the direct rate). A pass is at
+// least 65,536 elements, above every batch-size threshold of the encryption
+// shapes, so a large fill runs the kernels a large encryption runs.
+constexpr size_t kObfFillZeroBytes = (size_t)256 << 20;
+int xhe_obf_fill(const xhe_key* key, const uint32_t* rand_dev, int64_t count, uint32_t* obf_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (!key || count < 0 || (count > 0 && (!rand_dev || !obf_dev)))
+      return fail(XHE_EINVAL, "xhe_obf_fill: null argument or negative count");
+    if (count == 0) return XHE_OK;
+    DevGuard dg(key->device);
+    hipStream_t s = (hipStream_t)stream;
+    const size_t row = (size_t)key->nw * sizeof(uint32_t);
+    const int64_t pass = std::min<int64_t>(count, std::max<int64_t>(65536, (int64_t)(kObfFillZeroBytes / row)));
+    WsScope wsc(s);
+    uint32_t* zero = wsc.get<uint32_t>((size_t)pass * row);
+    HIPCHK(hipMemsetAsync(zero, 0, (size_t)pass * row, s));
+    for (int64_t off = 0; off < count; off += pass) {
+      const int64_t n = std::min(pass, count - off);
+      const int rc = xhe_encrypt(key, zero, rand_dev + (size_t)off * key->rand_words, n,
+                                 obf_dev + (size_t)off * key->n2w, stream);
+      if (rc != XHE_OK) return rc;
+    }
+    return XHE_OK;
+  });
+}
+
+int xhe_encrypt_obf(const xhe_key* key, const uint32_t* m_dev, uint32_t* obf_dev, int64_t count, int wipe,
+                    uint32_t* ct_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (!key || (count > 0 && (!m_dev || !obf_dev || !ct_dev)))
+      return fail(XHE_EINVAL, "xhe_encrypt_obf: null argument");
+    if (count < 0) return fail(XHE_EINVAL, "xhe_encrypt_obf: negative count");
+    if (count == 0) return XHE_OK;
+    const size_t words = (size_t)count * key->n2w;
+    if (ct_dev < obf_dev + words && obf_dev < ct_dev + words)
+      return fail(XHE_EINVAL, "xhe_encrypt_obf: ct overlaps the obfuscators");
+    DevGuard dg(key->device);
+    hipStream_t s = (hipStream_t)stream;
+    with_shape(key->K, [&](auto sh) {
+      using M = typename decltype(sh)::MP2L;
+      // one launch: no workspace bounds the batch (a 256-thread block holds 256 / TPI elements)
+      const int64_t blocks = (count * M::TPI + 255) / 256;
+      if (blocks > 0x7fffffff) throw std::invalid_argument("xhe_encrypt_obf: count too large for one launch");
+      ProfScope ps("k_enc_obf", s);
+      launch(k_enc_obf<M>, dim3((unsigned)blocks), dim3(256), s, key->kd, m_dev, obf_dev, count, wipe, ct_dev);
+    });
     return XHE_OK;
   });
 }

@@ -376,7 +376,9 @@ class PaillierArray(_EABase):
             raise ValueError(f"ciphertext rows of {self._st.n2w} words, the key's n^2 has {n2w}")
         dev = resident.device_for(ctx)
         if self._resident_on(dev):
-            new = resident.obfuscate(ctx.device_key(dev), self._dw(dev))
+            dk = ctx.device_key(dev)
+            new = resident.obfuscate(dk, self._dw(dev))
+            resident.obf_top_up(ctx, dk)
             if self._whole():
                 self._st.d = new
             else:

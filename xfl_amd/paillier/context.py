@@ -219,6 +219,7 @@ class PaillierContext(object):
         keys are rebuilt on next use."""
         from .._native import parse_win
         self._win_pinned = None if win_bits is None else parse_win(win_bits)
+        self.drop_obfuscators()
         self._dev = {}
 
     def _wanted_window(self):
@@ -270,7 +271,7 @@ class PaillierContext(object):
                     win -= 2
                 if k is not None and self._key_fits(k, (win, split)):
                     return k
-                dev.pop(device, None)
+                self._drop_pool(dev.pop(device, None))
                 k = None  # free the old tables before building the new ones
             if self.__is_private:
                 k = DeviceKey(bits, self.__n, self.__p, self.__q, h, device=device, win_bits=win | flag if win else 0)
@@ -278,6 +279,53 @@ class PaillierContext(object):
                 k = DeviceKey(bits, self.__n, None, None, h, device=device)
             dev[device] = k
         return k
+
+    # ------------------------------------------------------------ obfuscators
+    # The obfuscator of an encryption (h^a, r^n) does not depend on the
+    # plaintext. A pool of them made ahead of time (resident.ObfPool, kept on
+    # the device key: one per context and device) turns a later
+    # Paillier.encrypt / Paillier.obfuscate into one launch of two products
+    # mod n per element (include/xhe.h xhe_encrypt_obf). Every obfuscator is
+    # used once and zeroed by the launch that uses it. The pool is never
+    # pickled or copied: it lives with the device key, which __getstate__ and
+    # _copy_public_from leave behind.
+    def reserve_obfuscators(self, count: int, device=None) -> int:
+        """Top the pool of `device` (default: the process's own GPU) up to
+        `count` obfuscators and return how many are available. The fill is
+        queued behind the work already on the drop-in stream; the call does not
+        wait for it. The pool's size is clipped to what resident_budget()
+        ($XHE_RESIDENT_MAX_BYTES) allows a resident batch. Returns 0, and does
+        nothing, where arrays are not resident ($XHE_RESIDENT=0, contexts
+        sharded over several GPUs, no GPU)."""
+        from . import resident
+        own = resident.device_for(self)
+        if own is None or int(count) <= 0:
+            return 0 if own is None else self.obfuscators_available(device)
+        dk = self.device_key(own if device is None else device)
+        with _KEY_LOCK:
+            pool = getattr(dk, "obf_pool", None)
+            if pool is None:
+                pool = dk.obf_pool = resident.ObfPool(dk.device, dk.n2w)
+        return pool.reserve(dk, count, resident.obf_pool_rows(self, dk, count))
+
+    def obfuscators_available(self, device=None) -> int:
+        keys = getattr(self, "_dev", None) or {}
+        if not keys:
+            return 0
+        pool = getattr(keys.get(self.own_device() if device is None else device), "obf_pool", None)
+        return pool.available if pool is not None else 0
+
+    def drop_obfuscators(self):
+        """Zero and free every pool of this context."""
+        for k in list((getattr(self, "_dev", None) or {}).values()):
+            self._drop_pool(k)
+
+    @staticmethod
+    def _drop_pool(key):
+        pool = getattr(key, "obf_pool", None)
+        if pool is not None:
+            pool.drop()
+            key.obf_pool = None
 
     @staticmethod
     def own_device():

@@ -297,9 +297,11 @@ class Paillier(object):
                 if dev is not None:  # results stay in HBM (resident.py)
                     if obfuscation:
                         context.note_encrypt_volume(n)
-                    d, e, st = resident.encrypt_floats(context.device_key(dev), flat, precision, max_exponent,
-                                                       obfuscation)
+                    dk = context.device_key(dev)
+                    d, e, st = resident.encrypt_floats(dk, flat, precision, max_exponent, obfuscation)
                     Paillier._raise_status(st)
+                    if obfuscation:
+                        resident.obf_top_up(context, dk)
                     return PaillierArray.from_device(context, d, e, shape)
                 w, e, st = ops.encrypt_floats_words(context, flat, precision, max_exponent, obfuscation, num_cores)
                 Paillier._raise_status(st)
@@ -314,7 +316,10 @@ class Paillier(object):
                     ms, es = _encode_ints(context, flat.tolist(), precision, max_exponent)
                     if obfuscation:
                         context.note_encrypt_volume(n)
-                    d = resident.encrypt_encoded(context.device_key(dev), nat.ints_to_words(ms, nw), obfuscation)
+                    dk = context.device_key(dev)
+                    d = resident.encrypt_encoded(dk, nat.ints_to_words(ms, nw), obfuscation)
+                    if obfuscation:
+                        resident.obf_top_up(context, dk)
                     return PaillierArray.from_device(context, d, np.asarray(es, dtype=np.int32), shape)
             else:
                 for i, x in enumerate(flat):
@@ -369,7 +374,10 @@ class Paillier(object):
         if dev is not None:  # results stay in HBM (resident.py)
             if obfuscation:
                 context.note_encrypt_volume(n)
-            d, st = resident.encrypt_packed(context.device_key(dev), data.cols, ib, data.precision, obfuscation)
+            dk = context.device_key(dev)
+            d, st = resident.encrypt_packed(dk, data.cols, ib, data.precision, obfuscation)
+            if obfuscation:
+                resident.obf_top_up(context, dk)
             return None if st.any() else PaillierArray.from_device(context, d, exps, (n,))
         mw, st = ops.embed_words(context, data.cols, ib, data.precision, num_cores)
         if st.any():

@@ -245,6 +245,168 @@ def _seed():
     return s()
 
 
+# ------------------------------------------------------------ obfuscator pool
+class _DeviceObfOps:
+    """What an ObfPool does to its rows on a GPU: all of it queued on the
+    drop-in stream of `dev`, so stream order puts a fill before every use of
+    its rows and a use before the next fill."""
+
+    def __init__(self, dev):
+        self.dev = dev
+
+    def alloc(self, cap, n2w):
+        torch = _torch()
+        with _On(self.dev):
+            return torch.zeros((cap, n2w), dtype=torch.int32, device=f"cuda:{self.dev}")
+
+    def fill(self, dk, rows):
+        """rows <- fresh obfuscators, drawn as _encrypt_pipeline draws: a new
+        seed per chunk, xhe_rand, then the encryption kernels on m = 0"""
+        torch = _torch()
+        L = nat.lib()
+        n = rows.shape[0]
+        c = max(1, min(n, CHUNK))
+        with _On(self.dev):
+            rnd = torch.empty((c, dk.rand_words), dtype=torch.int32, device=f"cuda:{self.dev}")
+        s = _sp(self.dev)
+        for lo in range(0, n, c):
+            k = min(c, n - lo)
+            seed, nonce = _seed()
+            nat.check(L.xhe_rand(dk.handle, seed, nonce, k, _dp(rnd), None, s), "rand")
+            nat.check(L.xhe_obf_fill(dk.handle, _dp(rnd), k, _dp(rows[lo:]), s), "obf_fill")
+
+    def zero(self, rows):
+        with _On(self.dev):
+            rows.zero_()
+
+    def copy(self, dst, src):
+        with _On(self.dev):
+            dst.copy_(src)
+
+
+class ObfPool:
+    """Obfuscators made ahead of time for one device key: a ring of [cap, n2w]
+    int32 rows, `available` of them filled starting at row `head`. Every row
+    is handed out once: take() moves the head past the rows it returns before
+    anything is launched on them, and the kernels that use a row zero it
+    (xhe_encrypt_obf's wipe; obfuscate() zeroes its rows after the product).
+    The bookkeeping and the queuing of fills and uses happen under one lock:
+    a refill cannot be queued between the hand-out of rows and the launch
+    that reads them. `ops` (alloc, fill, zero, copy) stands in for the device
+    in the host tests."""
+
+    def __init__(self, dev, n2w, ops=None):
+        self.dev = dev
+        self.n2w = n2w
+        self.ops = ops if ops is not None else _DeviceObfOps(dev)
+        self.lock = threading.RLock()
+        self.rows = None
+        self.cap = 0
+        self.head = 0
+        self.available = 0
+
+    def _spans(self, start, k):
+        """the k rows from `start` on as one view, or two at the wrap"""
+        first = min(k, self.cap - start)
+        return [self.rows[start:start + first]] + ([self.rows[0:k - first]] if k > first else [])
+
+    def reserve(self, dk, count, max_rows=None):
+        """fill rows until min(count, max_rows) are available (the ring grows
+        when it is smaller; the rows it holds move over) -> rows available"""
+        want = int(count) if max_rows is None else min(int(count), int(max_rows))
+        with self.lock:
+            if want > self.cap:
+                new = self.ops.alloc(want, self.n2w)
+                if self.rows is not None:
+                    off = 0
+                    for v in self._spans(self.head, self.available) if self.available else []:
+                        self.ops.copy(new[off:off + v.shape[0]], v)
+                        off += v.shape[0]
+                    self.ops.zero(self.rows)
+                self.rows, self.cap, self.head = new, want, 0
+            need = want - self.available
+            if need > 0:
+                for v in self._spans((self.head + self.available) % self.cap, need):
+                    self.ops.fill(dk, v)
+                self.available += need  # counted once every fill is queued
+            return self.available
+
+    def take(self, k):
+        """the next min(k, available) rows -> list of views (none, one, or two
+        at the wrap). The head has moved past them on return. A caller that
+        launches on them holds `lock` from here until the launch is queued
+        (consume does)."""
+        with self.lock:
+            k = min(int(k), self.available)
+            if k <= 0:
+                return []
+            views = self._spans(self.head, k)
+            self.head = (self.head + k) % self.cap
+            self.available -= k
+            return views
+
+    def consume(self, k, launch):
+        """take(k), then launch(view, offset) per view (offset: rows handed
+        out before it) -> rows served. The rows are gone from the pool even
+        when launch raises."""
+        with self.lock:
+            off = 0
+            for v in self.take(k):
+                launch(v, off)
+                off += v.shape[0]
+            return off
+
+    def drop(self):
+        """zero the storage and free it"""
+        with self.lock:
+            if self.rows is not None:
+                self.ops.zero(self.rows)
+            self.rows, self.cap, self.head, self.available = None, 0, 0, 0
+
+
+def obf_pool(dk):
+    """the pool of obfuscators reserved for the device key dk (None: none)"""
+    return getattr(dk, "obf_pool", None)
+
+
+def obf_pool_rows(ctx, dk, count):
+    """`count` clipped to the rows resident_budget() leaves a pool on dk's device"""
+    cap = resident_budget(ctx, dk.device)
+    return int(count) if cap is None else min(int(count), cap // (4 * dk.n2w))
+
+
+_OBF_AUTO = None
+
+
+def obf_auto():
+    """$XHE_OBF_POOL=N (read once): a resident Paillier.encrypt / obfuscate
+    tops the pool up to N after its own work is queued"""
+    global _OBF_AUTO
+    if _OBF_AUTO is None:
+        v = os.environ.get("XHE_OBF_POOL", "").strip()
+        _OBF_AUTO = int(v) if v.isdigit() else 0
+    return _OBF_AUTO
+
+
+def obf_top_up(ctx, dk):
+    """the refill behind a resident call ($XHE_OBF_POOL; nothing when unset)"""
+    n = obf_auto()
+    if n > 0 and ctx is not None:
+        ctx.reserve_obfuscators(n, dk.device)
+
+
+def _encrypt_obf(dk, m, pool, k, ct):
+    """ct[:s] = (1 + n m[:s]) X on the next s = min(k, pool rows) obfuscators
+    X, wiped by the same launch, on the drop-in stream -> s"""
+    L = nat.lib()
+    s = _sp(dk.device)
+
+    def launch(rows, off):
+        nat.check(L.xhe_encrypt_obf(dk.handle, _dp(m[off:]), _dp(rows), rows.shape[0], 1, _dp(ct[off:]), s),
+                  "encrypt_obf")
+    return pool.consume(k, launch)
+
+
 ENC_STREAMS = int(os.environ.get("XHE_ENC_STREAMS", 2))  # streams the pieces of a pipelined encryption alternate on
 CHUNK = 1 << 20  # elements per encode/draw/encrypt pass: bounds the m + draw temporaries (~400 MB at 2048 bits)
 
@@ -310,6 +472,13 @@ def _encrypt_pipeline(dk, n, encode, obfuscation):
                 for _ in range(2 if sub < c and ENC_STREAMS > 1 else 1)] if obfuscation else [None, None]
     main = stream(dev)
     streams = [main, aux_stream(dev)] if sub < c and ENC_STREAMS > 1 else [main]
+    # Reserved obfuscators (ObfPool) serve the leading elements of a piece in
+    # one xhe_encrypt_obf launch on the drop-in stream; what the pool cannot
+    # cover is drawn and encrypted as without a pool. Only in a one-pass call,
+    # where the statuses are back before anything is encrypted: a bad input
+    # raises with the pool untouched.
+    pool = obf_pool(dk) if obfuscation and n <= c else None
+    direct = False  # some piece went through xhe_rand + xhe_encrypt
     es_h = None
     marks = []
     j = 0
@@ -335,16 +504,30 @@ def _encrypt_pipeline(dk, n, encode, obfuscation):
             st = streams[j % len(streams)]
             rnd = rnds[j % len(rnds)] if obfuscation else None
             sp = ctypes.c_void_p(st.cuda_stream)
-            if obfuscation:
-                seed, nonce = _seed()
-                nat.check(L.xhe_rand(dk.handle, seed, nonce, ks, _dp(rnd), None, sp), "rand")
-            nat.check(L.xhe_encrypt(dk.handle, _dp(m[so:]), _dp(rnd), ks, _dp(ct[lo + so:]), sp), "encrypt")
-            if bits is not None:  # the piece's bit lengths for the serializer's layout, behind the piece
-                nat.check(L.xhe_row_bits(_dp(ct[lo + so:]), ks, dk.n2w, _dp(bits[lo + so:]), sp), "row bits")
+            served = 0
+            if pool is not None and pool.available:
+                served = _encrypt_obf(dk, m[so:], pool, ks, ct[lo + so:])
+                if served and bits is not None:
+                    nat.check(L.xhe_row_bits(_dp(ct[lo + so:]), served, dk.n2w, _dp(bits[lo + so:]), _sp(dev)),
+                              "row bits")
+                if 0 < served < ks and st is not main:  # the piece's mark (on st) covers its pooled rows too
+                    with _On(dev):
+                        ev = torch.cuda.Event()
+                        ev.record(main)
+                        st.wait_event(ev)
+            if served < ks:
+                direct = True
+                a, kr = so + served, ks - served
+                if obfuscation:
+                    seed, nonce = _seed()
+                    nat.check(L.xhe_rand(dk.handle, seed, nonce, kr, _dp(rnd), None, sp), "rand")
+                nat.check(L.xhe_encrypt(dk.handle, _dp(m[a:]), _dp(rnd), kr, _dp(ct[lo + a:]), sp), "encrypt")
+                if bits is not None:  # the piece's bit lengths for the serializer's layout, behind the piece
+                    nat.check(L.xhe_row_bits(_dp(ct[lo + a:]), kr, dk.n2w, _dp(bits[lo + a:]), sp), "row bits")
             if sub < c:
                 with _On(dev):
                     ev = torch.cuda.Event()
-                    ev.record(st)
+                    ev.record(st if served < ks else main)
                 marks.append((lo + so + ks, ev))
             j += 1
         with _On(dev):  # the next pass's encode (and everything after) waits for both streams
@@ -352,7 +535,7 @@ def _encrypt_pipeline(dk, n, encode, obfuscation):
                 done = torch.cuda.Event()
                 done.record(st)
                 main.wait_event(done)
-    if marks:
+    if marks and direct:  # (a call the pool served whole ran on the drop-in stream alone)
         ct._xhe_ready = marks
     if bits is not None:
         ct._xhe_bits = bits
@@ -371,10 +554,30 @@ def obfuscate(dk, c):
     torch = _torch()
     dev = dk.device
     n = c.shape[0]
+    pool = obf_pool(dk)
+    served, out = 0, None
+    if pool is not None and pool.available:
+        # reserved obfuscators are the fresh encryptions of 0 themselves: the
+        # product straight on the pool's rows, zeroed behind it
+        L = nat.lib()
+        with _On(dev):
+            out = torch.empty((n, dk.n2w), dtype=torch.int32, device=f"cuda:{dev}")
+
+        def launch(rows, off):
+            nat.check(L.xhe_mulmod(dk.handle, _dp(c[off:]), None, _dp(rows), None, rows.shape[0], 0, _dp(out[off:]),
+                                   None, _sp(dev)), "add")
+            pool.ops.zero(rows)
+        served = pool.consume(n, launch)
+        if served == n:
+            return out
     with _On(dev):
-        zero = torch.zeros((n, dk.nw), dtype=torch.int32, device=f"cuda:{dev}")
+        zero = torch.zeros((n - served, dk.nw), dtype=torch.int32, device=f"cuda:{dev}")
     x = encrypt_encoded_dev(dk, zero, True)
-    return mulmod(dk, c, None, x, None, 0)
+    if not served:
+        return mulmod(dk, c, None, x, None, 0)
+    nat.check(nat.lib().xhe_mulmod(dk.handle, _dp(c[served:]), None, _dp(x), None, n - served, 0, _dp(out[served:]),
+                                   None, _sp(dev)), "add")
+    return out
 
 
 def encrypt_encoded_dev(dk, md, obfuscation):
@@ -388,8 +591,14 @@ def encrypt_encoded_dev(dk, md, obfuscation):
         ct = torch.empty((n, dk.n2w), dtype=torch.int32, device=f"cuda:{dev}")
         rnd = torch.empty((c, dk.rand_words), dtype=torch.int32, device=f"cuda:{dev}") if obfuscation else None
     s = _sp(dev)
+    pool = obf_pool(dk) if obfuscation else None
     for lo in range(0, n, c):
         k = min(c, n - lo)
+        if pool is not None and pool.available:  # the chunk's leading elements on reserved obfuscators
+            served = _encrypt_obf(dk, md[lo:], pool, k, ct[lo:])
+            lo, k = lo + served, k - served
+            if k == 0:
+                continue
         if obfuscation:
             seed, nonce = _seed()
             nat.check(L.xhe_rand(dk.handle, seed, nonce, k, _dp(rnd), None, s), "rand")
