@@ -538,6 +538,104 @@ class LogDigits(MontDigits):
         L = sum(w << (32 * i) for i, w in enumerate(s)) * pow(self.R, -2, P) % P
         return self.value(a, c) * (1 + P * L) % P2
 
+    # -- the plaintext as a logarithm (pdigit_dev.hpp "The plaintext as a
+    # logarithm"; k_djn_pmd). With n = P Q, 1 + n m = 1 + P (Q m): the factor
+    # (1 + n m) is the log digit muhat = Q m R^2 mod P, the start value of the
+    # sum. After the finish R a + P c_f = (1 + n m) x R^2 (mod P^2), and one
+    # REDC on the 2k limbs of P^2 leaves Montgomery form.
+    def mu_const(self, Q):
+        """Q R^4 mod P (KeyDev::mu_p / mu_q)"""
+        return Q % self.P * pow(self.R, 4, self.P) % self.P
+
+    def redc_wide(self, T, ctr):
+        """pmd_redc_wide: 2k lazy columns (value < R P) -> t = value R^-1 mod P
+        (< 2P), one row of k mads per quotient digit"""
+        k = self.k
+        T = list(T)
+        assert len(T) == 2 * k and _norm_value(T) < self.R * self.P
+        v = _norm_value(T)
+        cy = 0
+        for i in range(k):
+            x = T[i] + cy
+            m = (x * self.n0inv) & MASK
+            x += m * self.Pl[0]
+            assert x & MASK == 0
+            cy = x >> W
+            for j in range(1, k):
+                T[i + j] += m * self.Pl[j]
+            ctr.mads += k
+            ctr.max_col = max(ctr.max_col, x, max(T[i + 1:i + k]))
+        out = []
+        for j in range(k):
+            x = T[k + j] + cy
+            out.append(x & MASK if j + 1 < k else x)
+            cy = x >> W
+            ctr.max_col = max(ctr.max_col, x)
+        t = _norm_value(out)
+        assert out[-1] < 1 << 32 and t < 2 * self.P and (t * self.R - v) % self.P == 0
+        return t
+
+    def plain_log(self, m, mu, ctr, nw=64):
+        """pmd_lam_plain: the nw words of m as 2k limbs, REDC by P, the product
+        by mu = Q R^4 mod P; returns muhat (< 2P) as the LW words of a sum"""
+        k = self.k
+        assert 0 <= m < 1 << (32 * nw) and 32 * nw <= W * 2 * k and 1 << (32 * nw) <= self.R * self.P
+        t = self.redc_wide(limbs(m, 2 * k), ctr)
+        muhat = self.mont_mul(t, mu, ctr)
+        assert muhat < 2 * self.P and (muhat * self.R - t * mu) % self.P == 0
+        return self.words(muhat)
+
+    def start_plain(self, row, mu_words):
+        """the first window's row on the lane that carries the plaintext: the
+        row's log digit is added to muhat"""
+        e, lhat = row
+        return e, 0, self.lam_add(mu_words, lhat)
+
+    def to_mont2(self, a, c, ctr):
+        """PMD::to_mont2: X = R a + P c as 2k limbs (top limb unmasked) from lazy
+        columns; k^2 mads"""
+        k = self.k
+        al, cl = limbs_loose(a, k), limbs_loose(c, k)
+        T = [0] * k + al
+        for i in range(k):
+            for j in range(k):
+                T[i + j] += cl[j] * self.Pl[i]
+            ctr.mads += k
+        ctr.max_col = max(ctr.max_col, max(T))
+        out, cy = [], 0
+        for j in range(2 * k):
+            v = T[j] + cy
+            out.append(v & MASK if j + 1 < 2 * k else v)
+            cy = v >> W
+            ctr.max_col = max(ctr.max_col, v)
+        assert out[-1] < 1 << 32 and _norm_value(out) == self.R * a + self.P * c
+        return out
+
+    def redc_out(self, X, ctr):
+        """Mont<2k, 28, 1>::redc_wide with a zero high half, then reduce_once:
+        X R^-2 mod P^2, canonical. X: 2k limbs, value < R^2 P^2; (2k)^2 mads"""
+        k2 = 2 * self.k
+        P2 = self.P * self.P
+        Nl = limbs(P2, k2)
+        n0 = (-pow(P2, -1, B)) % B
+        v = _norm_value(X)
+        assert len(X) == k2 and v < self.R * self.R * P2
+        T = list(X)
+        for _ in range(k2):
+            x0 = T[0]
+            m = (x0 * n0) & MASK
+            x0 += m * Nl[0]
+            assert x0 & MASK == 0
+            for j in range(1, k2):
+                T[j - 1] = T[j] + m * Nl[j]
+            T[k2 - 1] = 0
+            T[0] += x0 >> W
+            ctr.mads += k2
+            ctr.max_col = max(ctr.max_col, x0, max(T))
+        t = _norm_value(normalize(T, k2))
+        assert t < 2 * P2 and (t * self.R * self.R - v) % P2 == 0
+        return t - P2 if t >= P2 else t
+
 
 class InverseBaseTable:
     """One window of a fixed-base table for the base Bw mod P^2 with its rows'

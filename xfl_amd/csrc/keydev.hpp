@@ -78,9 +78,13 @@ struct KeyDev {
   // tables hold digit rows (pmd = 1) - words [0, K/64) the first digit e < P
   // of the row's pair (e, f), words [K/64, K/32) its log digit lhat = f y^-1
   // mod P < P (y the row's residue; pdigit_dev.hpp "Additive second digit") -
-  // and MASK + ((1 - R) mod P) limbs per prime
+  // and MASK + ((1 - R) mod P) limbs per prime; mu_p = Q R^4 mod P and mu_q =
+  // P R^4 mod Q (R = 2^(28*37), Mont<37, 28, 1> limbs; DJN keys): the factor
+  // that turns a plaintext m into its log digit Q m R^2 mod P (1 + n m =
+  // 1 + P (Q m); pdigit_dev.hpp "The plaintext as a logarithm")
   int pmd;
   const uint32_t *topc_p, *topc_q;
+  const uint32_t *mu_p, *mu_q;
   // ---- Montgomery digits mod n^2 (PMDX, 2048-bit keys, public or private):
   // n as 80 limbs of 27 bits (R = 2^2160), ceil(R/n) n^2 (160 limbs), R - n,
   // the digits of R^2 mod n^2 and of 1 (80 pairs each), MASK + E_i

@@ -47,11 +47,27 @@
 // x R^2 = R a + P (c + R a L): c_f = c + REDC(a Lhat) with the rows storing
 // lhat = l R^2 mod P = f y^-1 mod P (canonical, below P; k_tab_to_pmd), and
 // (a, c_f) is the pair form again (`finish`, then to_mont2).
-// Lhat is a plain sum, never reduced: it is below nwin P with nwin <= 86
-// windows (window 12), so below 2^1031 < R = 2^1036: LW = 33 words, K limbs,
-// and a Lhat < P (1 + 2P/R) R keeps REDC(a Lhat) below a + P < 2.001 P.
+// Lhat is a plain sum, never reduced: nwin canonical log digits and the
+// plaintext's muhat < 2P (below), so below (nwin + 2) P, and nwin <= 1024 (a
+// window of one bit) with R/P >= 2^12 keeps it below R = 2^1036: LW = 33
+// words, K limbs, and a Lhat < P (1 + 2P/R) R keeps REDC(a Lhat) below a + P <
+// 2.001 P.
 // Ranges: a', c' as above (c' < R + 4P), c_f < R + 7P, inside what to_mont2
 // takes. Columns of the row product: 2K products plus carries.
+//
+// The plaintext as a logarithm (k_djn_pmd). With n = P Q, 1 + n m = 1 + P (Q
+// m) (mod P^2) is itself of the form 1 + P l: multiplying the obfuscator h^a by
+// (1 + n m) is adding l = Q m to the logarithm,
+//
+//     (1 + P L)(1 + P Q m) = 1 + P (L + Q m)   (mod P^2).
+//
+// In the sum's scaling that is muhat = Q m R^2 mod P: t = REDC(m) = m R^-1 mod
+// P (pmd_redc_wide on the 2K limbs of m; any m below 2^2048 is below R P), and
+// muhat = MontMul(t, Q R^4 mod P) < 2P (pmd_lam_plain; K^2 + 2 K^2 + K mads).
+// It is the start value of the sum; `finish` then returns the pair of (1 + n
+// m) h^a at no further cost, and after to_mont2 one REDC on the 2K limbs of
+// P^2 (zero high half, (2K)^2 mads) and a reduce_once give the canonical
+// residue - in place of two 2K-limb Montgomery products (4 (2K)^2 mads).
 // (Model: tools/pdigit_model.py LogDigits.)
 #pragma once
 #include "bn_dev.hpp"
@@ -387,29 +403,30 @@ struct PMD {
   static constexpr int LW = (W * K + 31) / 32;  // words of a sum below R: 33 at K = 37
   static_assert(EQ + (LW + 3) / 4 <= NQ, "e limbs and the log sum share the slot of an interleaved row");
 
-  // sum <- lam (FIRST: the start value) or sum + lam; lam: HW words in
-  // registers (a row's log digit, or another lane's sum)
-  template <int HW, bool FIRST>
+  // The start value of a sum is the plaintext's log digit (pmd_lam_plain) on
+  // the lane that carries it, and zero on the other lanes of a group:
+  XHE_DEV static void lam_zero(uint32_t* slot) {
+#pragma unroll
+    for (int q = 0; q < (LW + 3) / 4; ++q) *reinterpret_cast<uint4*>(slot + (EQ + q) * 256) = make_uint4(0u, 0u, 0u, 0u);
+  }
+  // sum <- sum + lam; lam: HW words in registers (a row's log digit, or
+  // another lane's sum)
+  template <int HW>
   XHE_DEV static void lam_add(uint32_t* slot, const uint32_t (&lam)[HW]) {
     constexpr int LQ = (LW + 3) / 4;
     static_assert(HW >= 1 && HW <= 4 * LQ, "at most a whole sum");
     uint32_t s[4 * LQ];
-    if constexpr (FIRST) {
 #pragma unroll
-      for (int k = 0; k < 4 * LQ; ++k) s[k] = k < HW ? lam[k] : 0u;
-    } else {
+    for (int q = 0; q < LQ; ++q) {
+      const uint4 v = *reinterpret_cast<const uint4*>(slot + (EQ + q) * 256);
+      s[4 * q] = v.x, s[4 * q + 1] = v.y, s[4 * q + 2] = v.z, s[4 * q + 3] = v.w;
+    }
+    uint32_t cy = 0;
 #pragma unroll
-      for (int q = 0; q < LQ; ++q) {
-        const uint4 v = *reinterpret_cast<const uint4*>(slot + (EQ + q) * 256);
-        s[4 * q] = v.x, s[4 * q + 1] = v.y, s[4 * q + 2] = v.z, s[4 * q + 3] = v.w;
-      }
-      uint32_t cy = 0;
-#pragma unroll
-      for (int k = 0; k < LW; ++k) {
-        const uint64_t x = (uint64_t)s[k] + (k < HW ? lam[k] : 0u) + cy;
-        s[k] = (uint32_t)x;
-        cy = (uint32_t)(x >> 32);
-      }
+    for (int k = 0; k < LW; ++k) {
+      const uint64_t x = (uint64_t)s[k] + (k < HW ? lam[k] : 0u) + cy;
+      s[k] = (uint32_t)x;
+      cy = (uint32_t)(x >> 32);
     }
 #pragma unroll
     for (int q = 0; q < LQ; ++q)
@@ -424,7 +441,7 @@ struct PMD {
       const uint4 v = *reinterpret_cast<const uint4*>(other + (EQ + q) * 256);
       o[4 * q] = v.x, o[4 * q + 1] = v.y, o[4 * q + 2] = v.z, o[4 * q + 3] = v.w;
     }
-    lam_add<4 * LQ, false>(slot, o);
+    lam_add<4 * LQ>(slot, o);
   }
 
   // The finish: c <- c + REDC(a Lhat), Lhat the log sum (< R: K limbs). Its
@@ -527,6 +544,49 @@ XHE_DEV void pmd_redc_wide(const PMD<K>& M, uint64_t (&T)[2 * K], uint32_t (&t)[
     t[j] = j + 1 < K ? ((uint32_t)x & MASK) : (uint32_t)x;
     cy = x >> 28;
   }
+}
+
+// The plaintext as a logarithm (header: "The plaintext as a logarithm"): the
+// start value of a lane's log sum, muhat = Q m R^2 mod P (< 2P), in the LW
+// words of the slot's sum quads. m: nw little-endian words, any value (below
+// 2^(32 nw) <= 2^(28 * 2K) and below R P: 2K limbs into lazy columns, one
+// REDC by P - t = m R^-1 mod P < 2P); mu: Q R^4 mod P as K limbs (a uniform
+// row), multiplied in by one Montgomery product mod P. Runs before the lane's
+// state exists (the registers of a, c, T1, T2 are free): K^2 + 2 K^2 + K mads.
+template <int K>
+XHE_DEV void pmd_lam_plain(const PMD<K>& M, uint32_t* slot, const uint32_t* __restrict__ mw, int nw,
+                           const uint32_t* mu, const uint32_t* Pl) {
+  using D = PMD<K>;
+  constexpr int LQ = (D::LW + 3) / 4;
+  uint32_t t[K];
+  {
+    uint64_t T[2 * K];
+#pragma unroll
+    for (int j = 0; j < 2 * K; ++j) {
+      const int bit = 28 * j, k = bit >> 5, sh = bit & 31;
+      const uint32_t lo = word_or0(mw, k, nw);
+      const uint32_t hi = sh + 28 > 32 ? word_or0(mw, k + 1, nw) : 0u;
+      T[j] = (uint32_t)((((uint64_t)hi << 32) | lo) >> sh) & D::MASK;
+    }
+    uint32_t q[K];
+    pmd_redc_wide<K>(M, T, t, q);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  Mont<K, 28, 1> MN;
+  MN.init(Pl, M.n0inv);
+  MN.mul(t, ARow{mu});  // Q m R^2 mod P, < 2P: normalised limbs
+  uint32_t s[4 * LQ];
+#pragma unroll
+  for (int k = 0; k < 4 * LQ; ++k) {
+    const int bit = 32 * k, j = bit / 28, sh = bit - 28 * j;
+    uint64_t v = j < K ? (uint64_t)t[j] : 0ull;
+    if (j + 1 < K) v |= (uint64_t)t[j + 1] << 28;
+    if (j + 2 < K) v |= (uint64_t)t[j + 2] << 56;
+    s[k] = k < D::LW ? (uint32_t)(v >> sh) : 0u;
+  }
+#pragma unroll
+  for (int q = 0; q < LQ; ++q)
+    *reinterpret_cast<uint4*>(slot + (D::EQ + q) * 256) = make_uint4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
 }
 
 // r - s (K limbs each, both < 2^(28K)); returns the borrow out (1 if r < s)

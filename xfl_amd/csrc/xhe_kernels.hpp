@@ -604,16 +604,19 @@ __global__ void __launch_bounds__(128, 2) k_djn_pow_lds(KeyDev key, const uint32
 // it, with the table products in digit form. The tables hold each row as its
 // first digit e < P and its log digit lhat < P (k_tab_to_pmd; pdigit_dev.hpp
 // "Additive second digit"), packed 32 + 32 words. Per prime and element: the
-// first window's row is the start value (e, 0, lhat); each further window's
-// row is fetched in one visit - e by LDS-DMA into the wave's image and
-// unpacked into limbs, lhat into registers and added to the lane's log sum,
-// which lives in the upper quads of the lane's slot - and e is multiplied in
-// (nwin - 1 row products, 4 K^2 mads each); the sum is folded into c
-// (PMD::finish) and the result goes back to the 74-limb Montgomery form (R a
-// + P c = h^a R^2 mod P^2, to_mont2) for the two Montgomery products that
-// bring in (1 + n m) and leave Montgomery form, exactly as in djn_prime_lds.
-// Output rows as k_djn_pow_lds (MP2 limbs, [prime][2 S4][count]) for
-// k_crt_enc_w.
+// log sum starts from the plaintext - 1 + n m = 1 + P (Q m), so (1 + n m) is
+// the log digit muhat = Q m R^2 mod P (pmd_lam_plain: a REDC of m by P and one
+// Montgomery product mod P by the key's Q R^4, before the state exists); the
+// first window's row is the start value (e, 0), its lhat added to the sum;
+// each further window's row is fetched in one visit - e by LDS-DMA into the
+// wave's image and unpacked into limbs, lhat into registers and added to the
+// lane's log sum, which lives in the upper quads of the lane's slot - and e is
+// multiplied in (nwin - 1 row products, 4 K^2 mads each); the sum is folded
+// into c (PMD::finish), the result goes back to the 74-limb Montgomery form (R
+// a + P c = (1 + n m) h^a R^2 mod P^2, to_mont2) and one REDC mod P^2 on a
+// zero high half (S^2 mads) leaves it. The stored residue is the canonical one
+// djn_prime_lds writes. Output rows as k_djn_pow_lds (MP2 limbs, [prime][2
+// S4][count]) for k_crt_enc_w.
 //
 // G > 1 (small batches, where the chip is not full and the chain of nwin
 // dependent products is the latency): G adjacent lanes share an element; lane
@@ -622,7 +625,11 @@ __global__ void __launch_bounds__(128, 2) k_djn_pow_lds(KeyDev key, const uint32
 // state streamed as the reader's operand), so the chain is ~nwin/G + log2 G
 // products; lane 0 of the group finishes. Products of Montgomery-digit states
 // are digit states of the product (the general PMD::mul on (a, c), the log
-// sums added), so the result is the same residue.
+// sums added), so the result is the same residue. Lane 0 also carries muhat
+// (the other lanes' sums start from zero): the lanes of a group sit in one
+// wave, so the prologue's instructions are issued once per wave whichever
+// lane is active in them; lane 0 has a window for every nwin >= 1 and its sum
+// needs no tree step to arrive where the finish reads it.
 template <class MP2, int KP, int RW, int G = 1>
 __global__ void __launch_bounds__(128, 2) k_djn_pmd(KeyDev key, const uint32_t* __restrict__ Pp,
                                                     const uint32_t* __restrict__ Pq, const uint32_t* __restrict__ Np2,
@@ -654,7 +661,7 @@ __global__ void __launch_bounds__(128, 2) k_djn_pmd(KeyDev key, const uint32_t* 
   // image (below the lanes' log sums, quads [D::EQ, NQ)) and its lhat half
   // straight into registers; then sum += lhat (T1, T2 are dead here) and the
   // e limbs unpacked for mul_row.
-  auto stage = [&](int w, auto first) XHE_INL {
+  auto stage = [&](int w) XHE_INL {
     int64_t row0;
     const uint32_t d = win_digit(key, ae, aw, w, row0);
     const uint32_t* row = tab + (size_t)(row0 + d) * key.tab_rs;
@@ -668,12 +675,21 @@ __global__ void __launch_bounds__(128, 2) k_djn_pmd(KeyDev key, const uint32_t* 
       lam[4 * k] = v.x, lam[4 * k + 1] = v.y, lam[4 * k + 2] = v.z, lam[4 * k + 3] = v.w;
     }
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    D::template lam_add<RW / 2, decltype(first)::value>(slot, lam);
+    D::template lam_add<RW / 2>(slot, lam);
     unpack_e_lds<KP, RW / 2>(slot);
   };
+  // The log sum starts from the plaintext: lane 0 of the group (the lane that
+  // finishes, and one that always has a window) takes muhat = Q m R^2 mod P,
+  // the logarithm of 1 + n m; the other lanes start from zero. The state (a,
+  // c) and the products' accumulators are not live yet.
+  if (G == 1 || g == 0)
+    pmd_lam_plain<KP>(M, slot, m_words + (size_t)e * key.nw, key.nw, prime ? key.mu_q : key.mu_p, prime ? Pq : Pp);
+  else
+    D::lam_zero(slot);
+  __builtin_amdgcn_sched_barrier(0);
   uint32_t a[KP], c[KP];
   if (G == 1 || g < key.nwin) {
-    stage(g, std::true_type{});  // the start value: (e, 0) and the row's lhat
+    stage(g);  // the start value: (e, 0); the row's lhat joins the sum
 #pragma unroll
     for (int q = 0; q < D::EQ; ++q) {
       const uint4 v = *reinterpret_cast<const uint4*>(slot + q * 256);
@@ -686,7 +702,7 @@ __global__ void __launch_bounds__(128, 2) k_djn_pmd(KeyDev key, const uint32_t* 
     for (int j = 0; j < KP; ++j) c[j] = 0u;
   }
   for (int w = g + G; w < key.nwin; w += G) {
-    stage(w, std::false_type{});
+    stage(w);
     M.mul_row(a, c, slot, topc);
   }
   if constexpr (G > 1) {
@@ -712,26 +728,19 @@ __global__ void __launch_bounds__(128, 2) k_djn_pmd(KeyDev key, const uint32_t* 
     }
     if (g != 0) return;
   }
-  M.finish(a, c, slot, prime ? Pq : Pp);  // the log sum folded into c: the pair form again
+  M.finish(a, c, slot, prime ? Pq : Pp);  // the log sum folded into c: the pair form of (1 + n m) h^a
   __builtin_amdgcn_sched_barrier(0);
-  {
-    uint32_t x[2 * KP];
-    M.to_mont2(a, c, x);  // h^a R^2 mod P^2, unreduced (< 2^13 P^2)
-#pragma unroll
-    for (int q = 0; q < MP2::S4 / 4; ++q)
-      *reinterpret_cast<uint4*>(slot + q * 256) =
-          make_uint4(4 * q < 2 * KP ? x[4 * q] : 0u, 4 * q + 1 < 2 * KP ? x[4 * q + 1] : 0u,
-                     4 * q + 2 < 2 * KP ? x[4 * q + 2] : 0u, 4 * q + 3 < 2 * KP ? x[4 * q + 3] : 0u);
-  }
+  uint32_t b[MP2::L];
+  M.to_mont2(a, c, b);  // (1 + n m) h^a R^2 mod P^2, unreduced (< 2^15 P^2 < R^2 P^2, top limb < 2^17)
+  __builtin_amdgcn_sched_barrier(0);
   MP2 N;
   N.init(prime ? Nq2 : Np2, prime ? key.q2.n0inv : key.p2.n0inv);
-  uint32_t b[MP2::L];
-  N.load_words(b, m_words + (size_t)e * key.nw, key.nw);
-  N.mul(b, ARow{prime ? key.nR_q2 : key.nR_p2});  // n m mod P^2 (< 2 P^2), plain
-  b[0] += 1u;                                     // 1 + n m
-  N.mul(b, ALdsQ{slot});                          // (1 + n m) h^a mod P^2
+  N.redc_wide(b, AZero{});  // out of Montgomery form: (1 + n m) h^a mod P^2 (< 2 P^2)
   N.reduce_once(b);
-  N.store_strided(b, ws + (size_t)prime * 2 * MP2::S4 * count + e, (int)count);
+  // the element index formed again from the thread index: held in registers
+  // from the prologue to here, it spilled in the lane-group kernels
+  const int64_t eo = ((int64_t)blockIdx.x * blockDim.x + (uint32_t)opaque_i((int)threadIdx.x)) / G;
+  N.store_strided(b, ws + (size_t)prime * 2 * MP2::S4 * count + eo, (int)count);
 }
 
 // x <- x^E mod P^2 in Montgomery digits for an exponent E shared by every
