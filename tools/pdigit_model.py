@@ -580,7 +580,7 @@ class LogDigits(MontDigits):
         by mu = Q R^4 mod P; returns muhat (< 2P) as the LW words of a sum"""
         k = self.k
         assert 0 <= m < 1 << (32 * nw) and 32 * nw <= W * 2 * k and 1 << (32 * nw) <= self.R * self.P
-        t = self.redc_wide(limbs(m, 2 * k), ctr)
+        t = self.redc_p_block(m, ctr, nw)
         muhat = self.mont_mul(t, mu, ctr)
         assert muhat < 2 * self.P and (muhat * self.R - t * mu) % self.P == 0
         return self.words(muhat)
@@ -635,6 +635,58 @@ class LogDigits(MontDigits):
         t = _norm_value(normalize(T, k2))
         assert t < 2 * P2 and (t * self.R * self.R - v) % P2 == 0
         return t - P2 if t >= P2 else t
+
+    # -- the block-form reductions of k_djn_pmd (bn_dev.hpp Mont::red_rows:
+    # the rows of step1_red, limb i of the high half entering at the top of
+    # row i). `redc_out` above is the same row with a zero high half.
+    def redc_p_block(self, m, ctr, nw=64):
+        """pmd_redc_words: the nw words of m (below R P) as 2k limbs, the low k
+        the start columns, the high k streamed into the rows: m R^-1 mod P (<
+        2P), the value pmd_redc_wide returns"""
+        k = self.k
+        assert 0 <= m < 1 << (32 * nw) and 32 * nw <= W * 2 * k + 31 and m < self.R * self.P
+        ml = limbs(m, 2 * k)
+        t = _norm_value(normalize(red_rows(ml[:k], ml[k:], self.Pl, self.n0inv, ctr), k))
+        assert t < 2 * self.P and (t * self.R - m) % self.P == 0
+        return t
+
+    def redc_out_block(self, X, ctr):
+        """Mont<2k, 28, 1>::redc_wide(b, AZero) in block form, then reduce_once:
+        X R^-2 mod P^2, canonical. X: 2k limbs (top limb unmasked)"""
+        k2 = 2 * self.k
+        P2 = self.P * self.P
+        v = _norm_value(X)
+        assert len(X) == k2 and v < self.R * self.R * P2
+        T = red_rows(X, [0] * k2, limbs(P2, k2), (-pow(P2, -1, B)) % B, ctr)
+        t = _norm_value(normalize(T, k2))
+        assert t < 2 * P2 and (t * self.R * self.R - v) % P2 == 0
+        return t - P2 if t >= P2 else t
+
+
+def red_rows(lo, hi, Nl, n0inv, ctr):
+    """Mont::red_rows: L rows T <- (T + m N) / 2^W on the lazy columns T = lo
+    (L values, limbs or an unmasked top limb), limb i of `hi` written to the top
+    column at the end of row i (step1_red: T[L-1] = hi_i after the row's blocks
+    consumed the old top). Returns the L columns of (lo + hi 2^(W L) + q N) /
+    2^(W L); every column is recorded in ctr.max_col (the kernel holds them in
+    64 bits and adds products below 2^(2W): they must stay below 2^63)."""
+    L = len(lo)
+    assert len(hi) == L and len(Nl) == L
+    T = list(lo)
+    x0 = T[0]
+    m = (x0 * n0inv) & MASK
+    for i in range(L):
+        x0 += m * Nl[0]
+        assert x0 & MASK == 0
+        for j in range(1, L):
+            T[j - 1] = T[j] + m * Nl[j]
+        T[0] += x0 >> W
+        T[L - 1] = hi[i]
+        ctr.mads += L
+        ctr.max_col = max(ctr.max_col, x0, max(T))
+        x0 = T[0]  # the next row's digit, formed under this row's blocks
+        m = (x0 * n0inv) & MASK
+    return T
 
 
 class InverseBaseTable:

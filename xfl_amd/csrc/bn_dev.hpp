@@ -598,6 +598,14 @@ struct Mont {
 #pragma unroll
     for (int j = 0; j < L; ++j) T[j] = lo[j];
     hi.sync();
+    red_rows(T, hi);
+    normalize(T, b);
+  }
+  // The S rows of a Montgomery reduction in block form (TPI == 1 shapes with
+  // the SGPR modulus pipeline): T <- (T + hi 2^(W S) + q N) / 2^(W S), limb i
+  // of `hi` entering at the top of row i (step1_red).
+  template <class HI>
+  XHE_DEV void red_rows(uint64_t (&T)[L], const HI& hi) const {
     const uint32_t* Np = np();
     NRes R;
     load_res(Np, R);
@@ -620,7 +628,6 @@ struct Mont {
     }
 #pragma unroll
     for (int r = 0; r < (S & 3); ++r) step1_red(Np, R, T, comp4(cur, r), m, x0);
-    normalize(T, b);
   }
 
   // One column of the product: T <- (T + a_i*b + m*N) / 2^W, software-
@@ -805,6 +812,11 @@ struct Mont {
     uint64_t T[L];
 #pragma unroll
     for (int j = 0; j < L; ++j) T[j] = b[j];
+    if constexpr (TPI == 1 && L >= 13) {  // the rows in block form, as the reduction of sqr
+      red_rows(T, hi);
+      normalize(T, b);
+      return;
+    }
     const bool lead = G::g() == 0;
     const bool last = G::g() == TPI - 1;
     const uint32_t* Np = np();

@@ -62,7 +62,7 @@
 //     (1 + P L)(1 + P Q m) = 1 + P (L + Q m)   (mod P^2).
 //
 // In the sum's scaling that is muhat = Q m R^2 mod P: t = REDC(m) = m R^-1 mod
-// P (pmd_redc_wide on the 2K limbs of m; any m below 2^2048 is below R P), and
+// P (pmd_redc_words on the 2K limbs of m; any m below 2^2048 is below R P), and
 // muhat = MontMul(t, Q R^4 mod P) < 2P (pmd_lam_plain; K^2 + 2 K^2 + K mads).
 // It is the start value of the sum; `finish` then returns the pair of (1 + n
 // m) h^a at no further cost, and after to_mont2 one REDC on the 2K limbs of
@@ -322,8 +322,49 @@ struct PMD {
         : "vcc");
   }
 
+  // blk12_row of a product's first step, where both accumulators are zero:
+  // the e a, e c mads take the literal 0 as addend and T1, T2 are written, not
+  // read - the accumulators need no zero fill before the product
+  //   T1[j-1+k] = e a[j+k] + m1 P[j+k],   T2[j-1+k] = e c[j+k] + m2 P[j+k]
+  XHE_DEV void blk12_row0(uint64_t (&T1)[K], uint64_t (&T2)[K], const uint32_t (&a)[K], const uint32_t (&c)[K],
+                          uint32_t e, uint32_t m1, uint32_t m2, int j) const {
+    asm(
+      "v_mad_u64_u32 %0, vcc, %12, %15, 0\n\t"
+      "v_mad_u64_u32 %1, vcc, %12, %16, 0\n\t"
+      "v_mad_u64_u32 %2, vcc, %12, %17, 0\n\t"
+      "v_mad_u64_u32 %3, vcc, %12, %18, 0\n\t"
+      "v_mad_u64_u32 %4, vcc, %12, %19, 0\n\t"
+      "v_mad_u64_u32 %5, vcc, %12, %20, 0\n\t"
+      "v_mad_u64_u32 %6, vcc, %12, %21, 0\n\t"
+      "v_mad_u64_u32 %7, vcc, %12, %22, 0\n\t"
+      "v_mad_u64_u32 %8, vcc, %12, %23, 0\n\t"
+      "v_mad_u64_u32 %9, vcc, %12, %24, 0\n\t"
+      "v_mad_u64_u32 %10, vcc, %12, %25, 0\n\t"
+      "v_mad_u64_u32 %11, vcc, %12, %26, 0\n\t"
+      "v_mad_u64_u32 %0, vcc, %13, %27, %0\n\t"
+      "v_mad_u64_u32 %1, vcc, %13, %28, %1\n\t"
+      "v_mad_u64_u32 %2, vcc, %13, %29, %2\n\t"
+      "v_mad_u64_u32 %3, vcc, %13, %30, %3\n\t"
+      "v_mad_u64_u32 %4, vcc, %13, %31, %4\n\t"
+      "v_mad_u64_u32 %5, vcc, %13, %32, %5\n\t"
+      "v_mad_u64_u32 %6, vcc, %14, %27, %6\n\t"
+      "v_mad_u64_u32 %7, vcc, %14, %28, %7\n\t"
+      "v_mad_u64_u32 %8, vcc, %14, %29, %8\n\t"
+      "v_mad_u64_u32 %9, vcc, %14, %30, %9\n\t"
+      "v_mad_u64_u32 %10, vcc, %14, %31, %10\n\t"
+      "v_mad_u64_u32 %11, vcc, %14, %32, %11"
+        : "=&v"(T1[j - 1]), "=&v"(T1[j]), "=&v"(T1[j + 1]), "=&v"(T1[j + 2]), "=&v"(T1[j + 3]), "=&v"(T1[j + 4]),
+          "=&v"(T2[j - 1]), "=&v"(T2[j]), "=&v"(T2[j + 1]), "=&v"(T2[j + 2]), "=&v"(T2[j + 3]), "=&v"(T2[j + 4])
+        : "v"(e), "v"(m1), "v"(m2), "v"(a[j]), "v"(a[j + 1]), "v"(a[j + 2]), "v"(a[j + 3]), "v"(a[j + 4]),
+          "v"(a[j + 5]), "v"(c[j]), "v"(c[j + 1]), "v"(c[j + 2]), "v"(c[j + 3]), "v"(c[j + 4]), "v"(c[j + 5]),
+          "s"(p[j]), "s"(p[j + 1]), "s"(p[j + 2]), "s"(p[j + 3]), "s"(p[j + 4]), "s"(p[j + 5])
+        : "vcc");
+  }
+
   // `step` for a row limb e: entry x1 = T1[0] + e a[0], x2 = T2[0] + e c[0];
-  // the quotient chain and the topc - m1 entry are those of `step`
+  // the quotient chain and the topc - m1 entry are those of `step`. FIRST: the
+  // product's first step (T1 = T2 = 0 on entry, never read: blk12_row0).
+  template <bool FIRST = false>
   XHE_DEV void step_row(uint64_t (&T1)[K], uint64_t (&T2)[K], const uint32_t (&a)[K], const uint32_t (&c)[K],
                         uint32_t e, uint32_t en, uint32_t& m1, uint32_t& m2, uint64_t& x1, uint64_t& x2,
                         uint32_t topc) const {
@@ -337,7 +378,8 @@ struct PMD {
 #pragma unroll
     for (int b = 0; b < (K - 1) / BL; ++b) {
       const int j = 1 + BL * b;
-      blk12_row(T1, T2, a, c, e, m1, m2, j);
+      if constexpr (FIRST) blk12_row0(T1, T2, a, c, e, m1, m2, j);
+      else blk12_row(T1, T2, a, c, e, m1, m2, j);
       if (b == 0) {
         T1[0] += x1 >> W;
         T2[0] += x2 >> W;
@@ -374,25 +416,24 @@ struct PMD {
   // zero beyond K; unpack_e_lds). 4 K^2 mads. Two limbs per LDS read, one
   // pair in flight ahead of the steps that consume it.
   XHE_DEV void mul_row(uint32_t (&a)[K], uint32_t (&c)[K], const uint32_t* slot, const uint32_t* topc) const {
-    uint64_t T1[K], T2[K];
-#pragma unroll
-    for (int j = 0; j < K; ++j) T1[j] = T2[j] = 0;
+    static_assert(K & 1, "the first step alone, then pairs of steps");
+    uint64_t T1[K], T2[K];  // first written by the first step (step_row<true>), never zero-filled
     uint2 p0 = *reinterpret_cast<const uint2*>(slot);
     uint64_t x1 = mad64(p0.x, a[0], 0ull);
     uint64_t x2 = mad64(p0.x, c[0], 0ull);
     uint32_t m1 = ((uint32_t)x1 * n0inv) & MASK, m2 = ((uint32_t)x2 * n0inv) & MASK;
+    step_row<true>(T1, T2, a, c, p0.x, p0.y, m1, m2, x1, x2, topc[0]);
     for (int h = 0; h < K / 2; ++h) {
-      const int k = 2 * h + 2;  // the next pair: limbs k, k + 1 (k <= K - 1: inside the padded image)
-      const uint2 tc = *reinterpret_cast<const uint2*>(topc + 2 * h);
+      const int k = 2 * h + 2;  // the next pair: limbs k, k + 1 (k <= K - 1: inside the padded image, limb K = 0)
+      const uint32_t tc1 = topc[2 * h + 1], tc2 = topc[2 * h + 2];
       const uint2 p1 = *reinterpret_cast<const uint2*>(slot + (k >> 2) * 256 + (k & 2));
       __builtin_amdgcn_sched_barrier(0);
-      step_row(T1, T2, a, c, p0.x, p0.y, m1, m2, x1, x2, tc.x);
+      step_row(T1, T2, a, c, p0.y, p1.x, m1, m2, x1, x2, tc1);
       __builtin_amdgcn_sched_barrier(0);
-      step_row(T1, T2, a, c, p0.y, p1.x, m1, m2, x1, x2, tc.y);
+      step_row(T1, T2, a, c, p1.x, p1.y, m1, m2, x1, x2, tc2);
       __builtin_amdgcn_sched_barrier(0);
       p0 = p1;
     }
-    if constexpr (K & 1) step_row(T1, T2, a, c, p0.x, 0u, m1, m2, x1, x2, topc[K - 1]);
     normalize(T1, a);
     normalize(T2, c);
   }
@@ -409,25 +450,65 @@ struct PMD {
 #pragma unroll
     for (int q = 0; q < (LW + 3) / 4; ++q) *reinterpret_cast<uint4*>(slot + (EQ + q) * 256) = make_uint4(0u, 0u, 0u, 0u);
   }
+  // Eight words of a carry chain in one statement, in place (tied operands:
+  // the sum's quads stay in the registers they were read into): s[k..k+8) +=
+  // l[k..k+8) + carry. The carry travels in vcc inside the statement and in
+  // the scalar pair cy between statements (FIRST: no carry in).
+  template <bool FIRST, int NS, int NL>
+  XHE_DEV static void add8(uint32_t (&s)[NS], const uint32_t (&l)[NL], int k, uint64_t& cy) {
+    if constexpr (FIRST) {
+      asm("v_add_co_u32 %0, vcc, %0, %9\n\t"
+          "v_addc_co_u32 %1, vcc, %1, %10, vcc\n\t"
+          "v_addc_co_u32 %2, vcc, %2, %11, vcc\n\t"
+          "v_addc_co_u32 %3, vcc, %3, %12, vcc\n\t"
+          "v_addc_co_u32 %4, vcc, %4, %13, vcc\n\t"
+          "v_addc_co_u32 %5, vcc, %5, %14, vcc\n\t"
+          "v_addc_co_u32 %6, vcc, %6, %15, vcc\n\t"
+          "v_addc_co_u32_e64 %7, %8, %7, %16, vcc"
+          : "+v"(s[k]), "+v"(s[k + 1]), "+v"(s[k + 2]), "+v"(s[k + 3]), "+v"(s[k + 4]), "+v"(s[k + 5]),
+            "+v"(s[k + 6]), "+v"(s[k + 7]), "=s"(cy)
+          : "v"(l[k]), "v"(l[k + 1]), "v"(l[k + 2]), "v"(l[k + 3]), "v"(l[k + 4]), "v"(l[k + 5]), "v"(l[k + 6]),
+            "v"(l[k + 7])
+          : "vcc");
+    } else {
+      asm("v_addc_co_u32_e64 %0, vcc, %0, %9, %8\n\t"
+          "v_addc_co_u32 %1, vcc, %1, %10, vcc\n\t"
+          "v_addc_co_u32 %2, vcc, %2, %11, vcc\n\t"
+          "v_addc_co_u32 %3, vcc, %3, %12, vcc\n\t"
+          "v_addc_co_u32 %4, vcc, %4, %13, vcc\n\t"
+          "v_addc_co_u32 %5, vcc, %5, %14, vcc\n\t"
+          "v_addc_co_u32 %6, vcc, %6, %15, vcc\n\t"
+          "v_addc_co_u32_e64 %7, %8, %7, %16, vcc"
+          : "+v"(s[k]), "+v"(s[k + 1]), "+v"(s[k + 2]), "+v"(s[k + 3]), "+v"(s[k + 4]), "+v"(s[k + 5]),
+            "+v"(s[k + 6]), "+v"(s[k + 7]), "+s"(cy)
+          : "v"(l[k]), "v"(l[k + 1]), "v"(l[k + 2]), "v"(l[k + 3]), "v"(l[k + 4]), "v"(l[k + 5]), "v"(l[k + 6]),
+            "v"(l[k + 7])
+          : "vcc");
+    }
+  }
   // sum <- sum + lam; lam: HW words in registers (a row's log digit, or
-  // another lane's sum)
+  // another lane's sum). One add per word: v_add_co on word 0, v_addc_co on
+  // the words above, the words past HW taking the carry alone.
   template <int HW>
   XHE_DEV static void lam_add(uint32_t* slot, const uint32_t (&lam)[HW]) {
     constexpr int LQ = (LW + 3) / 4;
-    static_assert(HW >= 1 && HW <= 4 * LQ, "at most a whole sum");
+    constexpr int NW = HW < LW ? HW : LW;  // words of lam that enter
+    static_assert(HW >= 8 && HW <= 4 * LQ, "at least one block of the chain, at most a whole sum");
     uint32_t s[4 * LQ];
 #pragma unroll
     for (int q = 0; q < LQ; ++q) {
       const uint4 v = *reinterpret_cast<const uint4*>(slot + (EQ + q) * 256);
       s[4 * q] = v.x, s[4 * q + 1] = v.y, s[4 * q + 2] = v.z, s[4 * q + 3] = v.w;
     }
-    uint32_t cy = 0;
+    uint64_t cy;
+    add8<true>(s, lam, 0, cy);
 #pragma unroll
-    for (int k = 0; k < LW; ++k) {
-      const uint64_t x = (uint64_t)s[k] + (k < HW ? lam[k] : 0u) + cy;
-      s[k] = (uint32_t)x;
-      cy = (uint32_t)(x >> 32);
-    }
+    for (int k = 8; k + 8 <= NW; k += 8) add8<false>(s, lam, k, cy);
+#pragma unroll
+    for (int k = NW & ~7; k < NW; ++k)
+      asm("v_addc_co_u32_e64 %0, %1, %0, %2, %1" : "+v"(s[k]), "+s"(cy) : "v"(lam[k]));
+#pragma unroll
+    for (int k = NW; k < LW; ++k) asm("v_addc_co_u32_e64 %0, %1, 0, %0, %1" : "+v"(s[k]), "+s"(cy));
 #pragma unroll
     for (int q = 0; q < LQ; ++q)
       *reinterpret_cast<uint4*>(slot + (EQ + q) * 256) = make_uint4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
@@ -546,34 +627,49 @@ XHE_DEV void pmd_redc_wide(const PMD<K>& M, uint64_t (&T)[2 * K], uint32_t (&t)[
   }
 }
 
+// The REDC of pmd_lam_plain: t = m R^-1 mod P (< 2P, K normalised limbs) for m
+// of nw little-endian words (below 2^(28 * 2K) and below R P). The upper K
+// limbs of m go through the e quads of the lane's slot (free before the first
+// row is staged) and enter the block-form reduction rows of Mont<K, 28, 1> as
+// its streamed high half; the quotient digits are not kept.
+template <int K>
+XHE_DEV void pmd_redc_words(const Mont<K, 28, 1>& MN, uint32_t* slot, const uint32_t* __restrict__ mw, int nw,
+                            uint32_t (&t)[K]) {
+  constexpr uint32_t MASK = PMD<K>::MASK;
+  auto limb = [&](int j) -> uint32_t {
+    const int bit = 28 * j, k = bit >> 5, sh = bit & 31;
+    const uint32_t lo = word_or0(mw, k, nw);
+    const uint32_t hi = sh + 28 > 32 ? word_or0(mw, k + 1, nw) : 0u;
+    return j < 2 * K ? (uint32_t)((((uint64_t)hi << 32) | lo) >> sh) & MASK : 0u;
+  };
+#pragma unroll
+  for (int q = 0; q < PMD<K>::EQ; ++q)
+    *reinterpret_cast<uint4*>(slot + q * 256) =
+        make_uint4(limb(K + 4 * q), limb(K + 4 * q + 1), limb(K + 4 * q + 2), limb(K + 4 * q + 3));
+#pragma unroll
+  for (int j = 0; j < K; ++j) t[j] = limb(j);
+  __builtin_amdgcn_sched_barrier(0);
+  MN.redc_wide(t, PmdLdsQ{slot});
+}
+
 // The plaintext as a logarithm (header: "The plaintext as a logarithm"): the
 // start value of a lane's log sum, muhat = Q m R^2 mod P (< 2P), in the LW
 // words of the slot's sum quads. m: nw little-endian words, any value (below
-// 2^(32 nw) <= 2^(28 * 2K) and below R P: 2K limbs into lazy columns, one
-// REDC by P - t = m R^-1 mod P < 2P); mu: Q R^4 mod P as K limbs (a uniform
-// row), multiplied in by one Montgomery product mod P. Runs before the lane's
-// state exists (the registers of a, c, T1, T2 are free): K^2 + 2 K^2 + K mads.
+// 2^(32 nw) <= 2^(28 * 2K) and below R P: 2K limbs, one REDC by P
+// (pmd_redc_words) - t = m R^-1 mod P < 2P); mu: Q R^4 mod P as K limbs (a
+// uniform row), multiplied in by one Montgomery product mod P. Runs before the
+// lane's state exists (the registers of a, c, T1, T2 are free, and so are the e
+// quads of the slot): K^2 + 2 K^2 + K mads.
 template <int K>
 XHE_DEV void pmd_lam_plain(const PMD<K>& M, uint32_t* slot, const uint32_t* __restrict__ mw, int nw,
                            const uint32_t* mu, const uint32_t* Pl) {
   using D = PMD<K>;
   constexpr int LQ = (D::LW + 3) / 4;
-  uint32_t t[K];
-  {
-    uint64_t T[2 * K];
-#pragma unroll
-    for (int j = 0; j < 2 * K; ++j) {
-      const int bit = 28 * j, k = bit >> 5, sh = bit & 31;
-      const uint32_t lo = word_or0(mw, k, nw);
-      const uint32_t hi = sh + 28 > 32 ? word_or0(mw, k + 1, nw) : 0u;
-      T[j] = (uint32_t)((((uint64_t)hi << 32) | lo) >> sh) & D::MASK;
-    }
-    uint32_t q[K];
-    pmd_redc_wide<K>(M, T, t, q);
-  }
-  __builtin_amdgcn_sched_barrier(0);
   Mont<K, 28, 1> MN;
   MN.init(Pl, M.n0inv);
+  uint32_t t[K];
+  pmd_redc_words<K>(MN, slot, mw, nw, t);
+  __builtin_amdgcn_sched_barrier(0);
   MN.mul(t, ARow{mu});  // Q m R^2 mod P, < 2P: normalised limbs
   uint32_t s[4 * LQ];
 #pragma unroll
