@@ -14,7 +14,7 @@ from tests.conftest import hx, load_fixture
 
 pytestmark = pytest.mark.gpu
 
-COUNT = 6000  # above kN2RowMax (4096): the 4-lane regime
+COUNT = 6000  # above paths.hpp kN2RowMax (4096): the 4-lane regime
 
 
 def _ctx(fx):

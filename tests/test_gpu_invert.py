@@ -50,8 +50,8 @@ def test_invert_batch_sizes(counts):
 
 def test_invert_no_inverse_level_tree():
     """The level-by-level tree's no-inverse return, in both of its shapes: 300
-    elements (above the whole-block tree's 256: 16 lanes) and 4,100 (above
-    kN2RowMax = 4096: 4 lanes), each with one multiple of p in the middle;
+    elements (above the whole-block tree's kWtreeMax = 256: 16 lanes) and 4,100
+    (above kN2RowMax = 4096: 4 lanes; both in csrc/paths.hpp), each with one multiple of p in the middle;
     the next valid batch in the same process still inverts."""
     import torch
 

@@ -21,7 +21,8 @@ The expected values of a key are computed once (pure Python costs 40 ms per
 distinct (m, draw) pairs; they are tiled to the batch sizes that select each
 kernel shape, and every produced row is compared.
 
-Batch sizes (thresholds read from xhe.hip):
+Batch sizes (the thresholds and rules live in xfl_amd/csrc/paths.hpp, where
+tests/test_paths.py pins each of them on the CPU; the names below are its):
   2048-bit DJN private encrypt, k_djn_pmd, pmd_split(): 16 lanes per element
     up to 2,048 elements, 4 up to 16,384, 1 beyond -> 1, 65, 3,000, 17,000
   2048-bit public non-DJN: k_nodjn_pub_wave up to kPubWaveMax = 2,048, the
@@ -31,11 +32,11 @@ Batch sizes (thresholds read from xhe.hip):
     16-lane limit kEncRowMax = 20,480 gates only k_djn_pow_x, which a key with
     digit tables never reaches) -> 3 and 21,000 (past that limit all the same)
     for DJN private, 3 and 6,000 otherwise; 8192 bits: 2 and 21,000 / 300
-  decrypt, decrypt_impl: 2048 bits k_dec_rns up to kDecWaveMax = 1,024, 16
+  decrypt, decrypt(): 2048 bits k_dec_rns up to kDecWaveMax = 1,024, 16
     lanes up to kDecRowMax = 5,120, 4 up to kDecQuadMax = 28,672, one lane
     (k_dec_pmd_*) beyond -> 15, 1,100, 5,200, 29,000; 3072/4096 bits 16 lanes
     up to 5,120, then the digit kernels k_dec_pmdx_* -> 15 and 6,000
-  mod n^2, n2_row(): 16 lanes up to kN2RowMax = 4,096, 4 beyond (equal
+  mod n^2, n2_shape(): 16 lanes up to kN2RowMax = 4,096, 4 beyond (equal
     exponents: k_add_barrett); adds up to kWaveAddMax = 256 run k_mulmod_wave
     -> 300 and 6,000
 Where the library records a launch (xhe_profile_read) the test asserts once

@@ -95,11 +95,14 @@ def test_multiexp_both_shapes(ctx, nbases, ncols):
 
 
 def test_djn_encrypt_both_shapes():
-    """DJN private encryption: the 16-lane small-batch kernel (k_djn_pow_x, on
-    the one-lane tables with the (R'/R)^nwin start factor) and the one-lane
-    kernel give identical ciphertexts, equal to the closed form - with uniform
-    windows and with split layouts (XHE_WIN_SPLIT: the first rand_bits mod w
-    windows w+1 bits wide, their tables built as a second segment)."""
+    """DJN private encryption: a small, a middle and a large batch give
+    identical ciphertexts, equal to the closed form - with uniform windows and
+    with split layouts (XHE_WIN_SPLIT: the first rand_bits mod w windows w+1
+    bits wide, their tables built as a second segment). Every private DJN key
+    has digit tables, so these run the digit kernels (paths.hpp enc_djn:
+    k_djn_pmd in its three splits at 2048 bits, k_djn_pmdx beyond at every
+    size), not k_djn_pow_x and the one-lane kernel this test was written
+    for."""
     from oracle import paillier_oracle as O
     from xfl_amd._native import XHE_WIN_SPLIT, DeviceKey, ints_to_words, win_layout, words_to_ints
     for fx in FIXTURES:
@@ -113,7 +116,7 @@ def test_djn_encrypt_both_shapes():
                 assert win_layout(g["key_bits"] // 2, win)[1] > 0  # really split
             dk = DeviceKey(g["key_bits"], n, p, q, h, win_bits=win)
             rng = random.Random(win)
-            nbig = 24000  # above the 16-lane encryption limit (20,480)
+            nbig = 24000  # above k_djn_pmd's 4-lane split (16,384) and the row-shape limit (20,480)
             ms = [rng.randrange(n) for _ in range(nbig)]
             rs = [rng.randrange(1, 1 << dk.rand_bits) for _ in range(nbig)]
             mw, rw = ints_to_words(ms, dk.nw), ints_to_words(rs, dk.rand_words)

@@ -403,7 +403,7 @@ def fermat2(bits, starts, which, offs, device=0):
 TABLE_ROW_WORDS = {2048: 64, 3072: 96, 4096: 128, 8192: 256}  # packed rows: xhe.hip Shape<K>::RW = K/32
 
 
-PUB_WAVE_MAX = 2048  # xhe.hip kPubWaveMax: public non-DJN 2048-bit encrypts up to here run one block per element
+PUB_WAVE_MAX = 2048  # csrc/paths.hpp kPubWaveMax (tests/test_paths.py holds them equal): public non-DJN 2048-bit encrypts up to here run one block per element
 
 XHE_WIN_SPLIT = 0x100  # include/xhe.h: floor(rand_bits/w) windows, the first rand_bits mod w of them w+1 bits
 

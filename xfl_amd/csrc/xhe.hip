@@ -21,6 +21,7 @@
 #include "abi_common.hpp"
 #include "hostbn.hpp"
 #include "keyconst.hpp"
+#include "paths.hpp"
 #include "xhe_kernels.hpp"
 #include "fermat_dev.hpp"
 #include "dec_wave.hpp"
@@ -53,13 +54,21 @@ void launch(void (*kernel)(KArgs...), dim3 grid, dim3 block, hipStream_t s, Args
   HIPCHK(hipGetLastError());
 }
 
-// Run-time switches ($XHE_*; INTEGRATION.md "Other kernel switches"). The
+// The kernel switches ($XHE_*; INTEGRATION.md "Other kernel switches"), read
+// together once per process; paths.hpp turns them into kernel paths.
+const paths::Pins& pins() {
+  static const paths::Pins p = paths::parse_pins(getenv);
+  return p;
+}
+// A path the planner chose that this key size has no kernels for (guarded:
+// XHE_EINVAL).
+[[noreturn]] void no_path(const char* what) {
+  throw std::logic_error(std::string(what) + ": no such kernel path for this key size");
+}
+
+// The host-side settings (chunking, tracing, test hooks, window bits). The
 // callers keep the value in a function-local static: read once per process.
 const char* env_str(const char* name) { return getenv(name); }
-bool env_on(const char* name) {  // on unless the value starts with '0'
-  const char* e = env_str(name);
-  return !(e && e[0] == '0');
-}
 int64_t env_int(const char* name, int64_t dflt) {
   const char* e = env_str(name);
   return e ? atoll(e) : dflt;
@@ -179,12 +188,6 @@ void with_fermat_shape(int bits, F&& f) {
   else if (bits == 2048) f(Mont<80, 28, 16>{}, FermatBits<2048>{});
   else f(Mont<160, 27, 16>{}, FermatBits<4096>{});
 #endif
-}
-
-// $XHE_NDIG_PUB=0: public DJN keys keep Montgomery n^2 tables (k_djn_pub; A/B)
-bool ndig_pub_on() {
-  static const bool on = env_on("XHE_NDIG_PUB");
-  return on;
 }
 
 }  // namespace
@@ -437,7 +440,7 @@ void build_public_tables(xhe_key* k, const KeyImage& im) {
     using Sh = decltype(sh);
     build_tables_sync<typename Sh::MN2, Sh::RW2>(k, &kd.n2, &hm, &tab, 1);
     if constexpr (Sh::K == 2048) {
-      if (!ndig_pub_on()) return;
+      if (!pins().ndig_pub) return;  // Montgomery n^2 tables kept (k_djn_pub; A/B)
       kd.pub_nd = 1;
       rows_to_digits(rows, ND2048::TPI, 128, 1, [&](int, dim3 grid, dim3 block) {
         launch((k_tab_to_pmdx<ND2048, Sh::RW2>), grid, block, nullptr, kd, 2, tab, rows, (int64_t)Sh::RW2);
@@ -459,13 +462,6 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
   if (!k->djn) return;
   if (k->priv) build_private_tables(k, im);
   else build_public_tables(k, im);
-}
-
-int blocks_for(int64_t count, int tpi, int cap) {
-  int64_t threads = count * tpi;
-  int64_t b = (threads + 255) / 256;
-  if (b < 1) b = 1;
-  return (int)std::min<int64_t>(b, cap);
 }
 
 // Workspaces of the kernel entry points. Normally stream-ordered pool
@@ -676,16 +672,6 @@ struct ProfScope {
   }
 };
 
-// DJN private encryption in the 16-lane shape up to kEncRowMax elements
-// (tools/dec_shapes.py --enc: 64 elements 0.50 ms vs 1.95 ms one lane per
-// residue, 16 k 1.86 vs 2.16 ms, 64 k 6.2 vs 3.8 ms); $XHE_ENC_TPI (16 or 0)
-// pins it.
-constexpr int64_t kEncRowMax = 20480;
-bool enc_row(int64_t count) {
-  static const int pin = (int)env_int("XHE_ENC_TPI", -1);
-  return pin >= 0 ? pin == 16 : count <= kEncRowMax;
-}
-
 // CRT of the two prime rows in ws into ciphertext words (k_crt_enc; the
 // one-lane shape writes through LDS so its stores are whole lines)
 template <class Sh, class MP2 = typename Sh::MP2>
@@ -695,15 +681,6 @@ void crt_enc_launch(const xhe_key* k, int64_t n, uint32_t* ws, uint32_t* ct, hip
     launch((k_crt_enc_w<MP2, 2 * Sh::K / 32>), dim3(blocks), dim3(256), s, k->kd, k->kd.p2.N, n, ws, ct);
   else
     launch(k_crt_enc<MP2>, dim3(blocks), dim3(256), s, k->kd, k->kd.p2.N, n, ws, ct);
-}
-
-// lanes per element of k_djn_pmd: 16 up to 2 k elements, 4 up to 16 k, else
-// 1 (the chip holds ~128 k one-lane residues: 2 waves x 1024 SIMDs x 64);
-// $XHE_PMD_SPLIT pins it (1, 4 or 16)
-int pmd_split(int64_t n) {
-  static const int pin = (int)env_int("XHE_PMD_SPLIT", 0);
-  if (pin == 1 || pin == 4 || pin == 16) return pin;
-  return n <= 2048 ? 16 : n <= 16384 ? 4 : 1;
 }
 
 template <class Sh>
@@ -716,64 +693,72 @@ void encrypt_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r, int64_
   uint32_t *xrows = nullptr, *xwords = nullptr;
   for (int64_t off = 0; off < count; off += chunk) {
     int64_t n = std::min(chunk, count - off);
-    int blocks = (int)((n * MP2::TPI + 255) / 256);
-    if constexpr (Sh::K == 2048) {
-      if (k->kd.pmd) {
-        ProfScope ps("k_djn_pmd", s);
-        // small batches split each element's windows over G lanes (latency:
-        // ~nwin/G + log2 G dependent products instead of nwin)
-        const int G = pmd_split(n);
-        const dim3 grid((unsigned)((n * G + 127) / 128), 2);
-        auto run = [&](auto kern) {
-          launch(kern, grid, dim3(128), s, k->kd, k->kd.p.N, k->kd.q.N, k->kd.p2.N, k->kd.q2.N, m + (size_t)off * k->nw,
-                 r + (size_t)off * k->rand_words, k->rand_words, n, ws);
-        };
-        if (G == 16) run(k_djn_pmd<MP2, 37, Sh::RW, 16>);
-        else if (G == 4) run(k_djn_pmd<MP2, 37, Sh::RW, 4>);
-        else run(k_djn_pmd<MP2, 37, Sh::RW, 1>);
-        crt_enc_launch<Sh>(k, n, ws, ct + (size_t)off * k->n2w, s);
-        continue;
-      }
-    }
-    if constexpr (Sh::K == 3072 || Sh::K == 4096 || Sh::K == 8192) {
-      if (k->kd.pmdx) {
-        using D = typename Sh::PDX;
-        if (!xst) {
-          xst = wsc.get<uint2>((size_t)2 * D::K * chunk * sizeof(uint2));
-          xrows = wsc.get<uint32_t>((size_t)2 * 2 * Sh::PDXO::MN::S4 * chunk * sizeof(uint32_t));
-          xwords = wsc.get<uint32_t>((size_t)2 * chunk * Sh::RW * sizeof(uint32_t));
-        }
-        const dim3 g4((unsigned)((n * D::TPI + 127) / 128), 2);
-        {
-          ProfScope ps("k_djn_pmdx", s);
-          launch((k_djn_pmdx<D, Sh::RW>), g4, dim3(128), s, k->kd, r + (size_t)off * k->rand_words, k->rand_words, n,
-                 xst);
-        }
-        using DO = typename Sh::PDXO;  // the same state layout ([pair][count]) whatever the lanes per element
-        launch((k_pmdx_enc_out<DO, Sh::RW>), dim3((unsigned)((n * DO::TPI + 127) / 128), 2), dim3(128), s, k->kd,
-               m + (size_t)off * k->nw, n, xst, xrows, xwords);
-        launch(k_words_to_rows<MP2>, dim3((unsigned)((n * MP2::TPI + 255) / 256), 2), dim3(256), s, xwords, Sh::RW, n,
-               ws);
-        crt_enc_launch<Sh>(k, n, ws, ct + (size_t)off * k->n2w, s);
-        continue;
-      }
-    }
-    if (enc_row(n)) {
-      // small batch: one 16-lane DPP row per residue (latency-bound regime)
-      using MX = typename Sh::MP2X;
-      launch((k_djn_pow_x<MX, MP2::S4, Sh::RW>), dim3((unsigned)((n * MX::TPI + 255) / 256), 2), dim3(256), s, k->kd,
-             m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, ws);
-    } else {
-      // labelled by the kernel rocprof shows (k_djn_pow_lds / k_djn_pow)
-      ProfScope ps(MP2::TPI == 1 ? "k_djn_pow_lds" : "k_djn_pow", s);
-      if constexpr (MP2::TPI == 1) {  // table rows staged in LDS by LDS-DMA bursts
-        const dim3 grid((unsigned)((n + 127) / 128), 2);
-        launch((k_djn_pow_lds<MP2, Sh::RW>), grid, dim3(128), s, k->kd, k->kd.p2.N, k->kd.q2.N, m + (size_t)off * k->nw,
-               r + (size_t)off * k->rand_words, k->rand_words, n, ws);
-      } else {
-        launch((k_djn_pow<MP2, Sh::RW>), dim3(blocks, 2), dim3(256), s, k->kd, k->kd.p2.N, k->kd.q2.N,
+    switch (paths::enc_djn(Sh::K, MP2::TPI, k->kd.pmd, k->kd.pmdx, n, pins())) {
+      case paths::EncDjn::PMD:
+        if constexpr (Sh::K == 2048) {
+          ProfScope ps("k_djn_pmd", s);  // (the label's time includes the CRT launch)
+          // small batches split each element's windows over G lanes (latency:
+          // ~nwin/G + log2 G dependent products instead of nwin)
+          const int G = paths::pmd_split(n, pins());
+          const dim3 grid((unsigned)((n * G + 127) / 128), 2);
+          auto run = [&](auto kern) {
+            launch(kern, grid, dim3(128), s, k->kd, k->kd.p.N, k->kd.q.N, k->kd.p2.N, k->kd.q2.N,
+                   m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, ws);
+          };
+          if (G == 16) run(k_djn_pmd<MP2, 37, Sh::RW, 16>);
+          else if (G == 4) run(k_djn_pmd<MP2, 37, Sh::RW, 4>);
+          else run(k_djn_pmd<MP2, 37, Sh::RW, 1>);
+          crt_enc_launch<Sh>(k, n, ws, ct + (size_t)off * k->n2w, s);
+          continue;
+        } else no_path("encrypt (k_djn_pmd)");
+      case paths::EncDjn::PMDX:
+        if constexpr (Sh::K != 2048) {
+          using D = typename Sh::PDX;
+          if (!xst) {
+            xst = wsc.get<uint2>((size_t)2 * D::K * chunk * sizeof(uint2));
+            xrows = wsc.get<uint32_t>((size_t)2 * 2 * Sh::PDXO::MN::S4 * chunk * sizeof(uint32_t));
+            xwords = wsc.get<uint32_t>((size_t)2 * chunk * Sh::RW * sizeof(uint32_t));
+          }
+          const dim3 g4((unsigned)((n * D::TPI + 127) / 128), 2);
+          {
+            ProfScope ps("k_djn_pmdx", s);
+            launch((k_djn_pmdx<D, Sh::RW>), g4, dim3(128), s, k->kd, r + (size_t)off * k->rand_words, k->rand_words, n,
+                   xst);
+          }
+          using DO = typename Sh::PDXO;  // the same state layout ([pair][count]) whatever the lanes per element
+          launch((k_pmdx_enc_out<DO, Sh::RW>), dim3((unsigned)((n * DO::TPI + 127) / 128), 2), dim3(128), s, k->kd,
+                 m + (size_t)off * k->nw, n, xst, xrows, xwords);
+          launch(k_words_to_rows<MP2>, dim3((unsigned)((n * MP2::TPI + 255) / 256), 2), dim3(256), s, xwords, Sh::RW,
+                 n, ws);
+          crt_enc_launch<Sh>(k, n, ws, ct + (size_t)off * k->n2w, s);
+          continue;
+        } else no_path("encrypt (k_djn_pmdx)");
+      case paths::EncDjn::POW_X: {
+        // small batch: one 16-lane DPP row per residue (latency-bound regime)
+        using MX = typename Sh::MP2X;
+        launch((k_djn_pow_x<MX, MP2::S4, Sh::RW>), dim3((unsigned)((n * MX::TPI + 255) / 256), 2), dim3(256), s, k->kd,
                m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, ws);
+        break;
       }
+      // labelled by the kernel rocprof shows (k_djn_pow_lds / k_djn_pow)
+      case paths::EncDjn::POW_LDS:
+        if constexpr (MP2::TPI == 1) {  // table rows staged in LDS by LDS-DMA bursts
+          ProfScope ps("k_djn_pow_lds", s);
+          const dim3 grid((unsigned)((n + 127) / 128), 2);
+          launch((k_djn_pow_lds<MP2, Sh::RW>), grid, dim3(128), s, k->kd, k->kd.p2.N, k->kd.q2.N,
+                 m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, ws);
+          break;
+        } else no_path("encrypt (k_djn_pow_lds)");
+      case paths::EncDjn::POW:
+        if constexpr (MP2::TPI != 1) {
+          ProfScope ps("k_djn_pow", s);
+          const int blocks = (int)((n * MP2::TPI + 255) / 256);
+          launch((k_djn_pow<MP2, Sh::RW>), dim3(blocks, 2), dim3(256), s, k->kd, k->kd.p2.N, k->kd.q2.N,
+                 m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, ws);
+          break;
+        } else no_path("encrypt (k_djn_pow)");
+      default:
+        no_path("encrypt");
     }
     crt_enc_launch<Sh>(k, n, ws, ct + (size_t)off * k->n2w, s);
   }
@@ -788,8 +773,8 @@ int pow_grid(int64_t count, int cap_blocks) {
 template <class Sh>
 void encrypt_pub_djn_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r, int64_t count, uint32_t* ct,
                           hipStream_t s) {
-  if constexpr (Sh::K == 2048) {
-    if (k->kd.pub_nd) {
+  if (paths::enc_pub_djn(Sh::K, k->kd.pub_nd) == paths::EncPubDjn::PUB_ND) {
+    if constexpr (Sh::K == 2048) {
       // fixed-base products in Montgomery digits of n (k_djn_pub_nd), then
       // (1 + n m) folded in base n on the way out (k_ndig_out)
       using D = ND2048;
@@ -809,7 +794,7 @@ void encrypt_pub_djn_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r
                ct + (size_t)off * k->n2w, rows);
       }
       return;
-    }
+    } else no_path("encrypt (k_djn_pub_nd)");
   }
   using MN2 = typename Sh::MN2;
   int64_t chunk = std::min<int64_t>(count, kChunk);
@@ -824,11 +809,7 @@ void encrypt_pub_djn_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r
   }
 }
 
-// $XHE_NDIG=0: the Montgomery mod-n^2 kernels instead (A/B measurement)
-bool ndig_on() {
-  static const bool on = env_on("XHE_NDIG");
-  return on;
-}
+// The mod-n^2 digit kernels of 2048-bit keys (k_ndig_*):
 // in -> exponentiation -> out over chunks of up to kChunk elements; the
 // exponentiation runs grid-stride over at most 1024 blocks (32 element groups
 // each, one digit table per group slot)
@@ -848,12 +829,6 @@ void ndig_run(int64_t count, hipStream_t s, IN&& in, POW&& pw, OUT&& out) {
     pw(std::min<int>(pblocks, (int)((n + NdigWs<D>::GPB - 1) / NdigWs<D>::GPB)), off, n, st, tab);
     out(eblocks, off, n, st, rows);
   }
-}
-
-// $XHE_NODJN_PMD=0: the Montgomery k_nodjn_crt instead (A/B measurement)
-bool nodjn_pmd_on() {
-  static const bool on = env_on("XHE_NODJN_PMD");
-  return on;
 }
 
 // Private non-DJN encryption of 2048-bit keys in Montgomery digits: r mod
@@ -888,61 +863,49 @@ void encrypt_nodjn_pmd(const xhe_key* k, const uint32_t* m, const uint32_t* r, i
   }
 }
 
-// Public non-DJN encryption of 2048-bit keys by batch size: one 16-wave block
-// per element (k_nodjn_pub_wave) up to kPubWaveMax elements - the 4-lane digit
-// kernels take the same time for 1 element as for 8 k (one wave's chain of
-// products: 47.4 ms at 15, 48.9 ms at 8 k) - and the digit kernels beyond
-// (tools/dec_shapes.py --pub, profiles/r9/pub_small/: 6.7 ms up to 256
-// elements, one block a CU; 20.8 ms at 1 k, 40.4 vs 48.7 ms at 2 k, 79.6 vs
-// 48.9 ms at 4 k). $XHE_PUB_TPI (64 or 4) pins one path (A/B measurement).
-// Mirrored as xfl_amd._native.PUB_WAVE_MAX.
-constexpr int64_t kPubWaveMax = 2048;
-bool pub_wave(int64_t count) {
-  static const int pin = (int)env_int("XHE_PUB_TPI", 0);
-  return pin == 4 || pin == 64 ? pin == 64 : count <= kPubWaveMax;
-}
-
 template <class Sh>
 void encrypt_nodjn_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r, int64_t count, uint32_t* ct,
                         hipStream_t s) {
-  if constexpr (Sh::K == 2048) {
-    if (k->priv && nodjn_pmd_on()) {
-      encrypt_nodjn_pmd<Sh>(k, m, r, count, ct, s);
-      return;
-    }
-    if (!k->priv && pub_wave(count)) {
-      // (a pinned large batch: grid.x holds it, a block per element)
-      ProfScope ps("k_nodjn_pub_wave", s);
-      launch((k_nodjn_pub_wave<WaveN2::K_, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, m, r, k->rand_words, count, ct);
-      return;
-    }
-  }
-  if (k->priv) {
-    using MP2 = typename Sh::MP2;
-    // 2-lane batch shapes (3072 bits, 55 limbs per lane) spill in this
-    // variable-base exponentiation (9.7 k enc/s): run it in the 4-lane shape.
-    constexpr bool wide = MP2::TPI == 2;
-    using MPE = std::conditional_t<wide, typename Sh::MP2L, MP2>;
-    int64_t chunk = std::min<int64_t>(count, kChunk);
-    int pb = pow_grid<MPE>(chunk, 512);
-    int64_t groups = (int64_t)pb * 256 / MPE::TPI;
-    WsScope wsc(s);
-    uint32_t* ws = wsc.get<uint32_t>((size_t)2 * 18 * MPE::S4 * groups * sizeof(uint32_t));
-    uint32_t* rows = wsc.get<uint32_t>((size_t)2 * 2 * MP2::S4 * chunk * sizeof(uint32_t));
-    for (int64_t off = 0; off < count; off += chunk) {
-      int64_t n = std::min(chunk, count - off);
-      {
-        ProfScope ps("k_nodjn_crt", s);
-        const ModDev& mp = wide ? k->kd.p2L : k->kd.p2;
-        const ModDev& mq = wide ? k->kd.q2L : k->kd.q2;
-        launch((k_nodjn_crt<MPE, wide ? 1 : 0, MP2::S4>), dim3(pb, 2), dim3(256), s, k->kd, mp.N, mq.N,
-               m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, rows, ws);
+  switch (paths::enc_nodjn(Sh::K, k->priv, k->kd.ndig, count, pins())) {
+    case paths::EncNoDjn::PMD:
+      if constexpr (Sh::K == 2048) {
+        encrypt_nodjn_pmd<Sh>(k, m, r, count, ct, s);
+        return;
+      } else no_path("encrypt (k_dec_pmd_pow)");
+    case paths::EncNoDjn::PUB_WAVE:
+      if constexpr (Sh::K == 2048) {
+        // (a pinned large batch: grid.x holds it, a block per element)
+        ProfScope ps("k_nodjn_pub_wave", s);
+        launch((k_nodjn_pub_wave<WaveN2::K_, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, m, r, k->rand_words, count, ct);
+        return;
+      } else no_path("encrypt (k_nodjn_pub_wave)");
+    case paths::EncNoDjn::CRT: {
+      using MP2 = typename Sh::MP2;
+      // 2-lane batch shapes (3072 bits, 55 limbs per lane) spill in this
+      // variable-base exponentiation (9.7 k enc/s): run it in the 4-lane shape.
+      constexpr bool wide = MP2::TPI == 2;
+      using MPE = std::conditional_t<wide, typename Sh::MP2L, MP2>;
+      int64_t chunk = std::min<int64_t>(count, kChunk);
+      int pb = pow_grid<MPE>(chunk, 512);
+      int64_t groups = (int64_t)pb * 256 / MPE::TPI;
+      WsScope wsc(s);
+      uint32_t* ws = wsc.get<uint32_t>((size_t)2 * 18 * MPE::S4 * groups * sizeof(uint32_t));
+      uint32_t* rows = wsc.get<uint32_t>((size_t)2 * 2 * MP2::S4 * chunk * sizeof(uint32_t));
+      for (int64_t off = 0; off < count; off += chunk) {
+        int64_t n = std::min(chunk, count - off);
+        {
+          ProfScope ps("k_nodjn_crt", s);
+          const ModDev& mp = wide ? k->kd.p2L : k->kd.p2;
+          const ModDev& mq = wide ? k->kd.q2L : k->kd.q2;
+          launch((k_nodjn_crt<MPE, wide ? 1 : 0, MP2::S4>), dim3(pb, 2), dim3(256), s, k->kd, mp.N, mq.N,
+                 m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, rows, ws);
+        }
+        crt_enc_launch<Sh>(k, n, rows, ct + (size_t)off * k->n2w, s);
       }
-      crt_enc_launch<Sh>(k, n, rows, ct + (size_t)off * k->n2w, s);
+      return;
     }
-  } else {
-    if constexpr (Sh::K == 2048) {
-      if (k->kd.ndig && ndig_on()) {
+    case paths::EncNoDjn::NDIG:
+      if constexpr (Sh::K == 2048) {
         ndig_run(
             count, s,
             [&](int b, int64_t off, int64_t n, uint2* st) {
@@ -958,20 +921,24 @@ void encrypt_nodjn_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r, 
                      ct + (size_t)off * k->n2w, rows);
             });
         return;
+      } else no_path("encrypt (k_ndig_pow_n)");
+    case paths::EncNoDjn::PUB: {
+      using MN2 = typename Sh::MN2;
+      int64_t chunk = std::min<int64_t>(count, kChunk);
+      int pb = pow_grid<MN2>(chunk, 512);
+      int64_t groups = (int64_t)pb * 256 / MN2::TPI;
+      WsScope wsc(s);
+      uint32_t* ws = wsc.get<uint32_t>((size_t)18 * MN2::S4 * groups * sizeof(uint32_t));
+      for (int64_t off = 0; off < count; off += chunk) {
+        int64_t n = std::min(chunk, count - off);
+        ProfScope ps("k_nodjn_pub", s);
+        launch(k_nodjn_pub<MN2>, dim3(pb), dim3(256), s, k->kd, k->kd.n2.N, m + (size_t)off * k->nw,
+               r + (size_t)off * k->rand_words, k->rand_words, n, ct + (size_t)off * k->n2w, ws);
       }
+      return;
     }
-    using MN2 = typename Sh::MN2;
-    int64_t chunk = std::min<int64_t>(count, kChunk);
-    int pb = pow_grid<MN2>(chunk, 512);
-    int64_t groups = (int64_t)pb * 256 / MN2::TPI;
-    WsScope wsc(s);
-    uint32_t* ws = wsc.get<uint32_t>((size_t)18 * MN2::S4 * groups * sizeof(uint32_t));
-    for (int64_t off = 0; off < count; off += chunk) {
-      int64_t n = std::min(chunk, count - off);
-      ProfScope ps("k_nodjn_pub", s);
-      launch(k_nodjn_pub<MN2>, dim3(pb), dim3(256), s, k->kd, k->kd.n2.N, m + (size_t)off * k->nw,
-             r + (size_t)off * k->rand_words, k->rand_words, n, ct + (size_t)off * k->n2w, ws);
-    }
+    default:
+      no_path("encrypt");
   }
 }
 
@@ -982,53 +949,29 @@ const ModDev& n2h(const xhe_key* k) {
   else return k->kd.n2;
 }
 
-// Shape of the n^2 ciphertext ops by batch size: one 16-lane DPP row per
-// residue up to kN2RowMax elements (latency-bound: a few ciphertexts leave the
-// chip idle and each element's chain of dependent products sets the time),
-// 4 lanes beyond. $XHE_N2_TPI (4 or 16) pins one shape (A/B measurement).
-constexpr int64_t kN2RowMax = 4096;
-bool n2_row(int64_t count) {
-  static const int pin = (int)env_int("XHE_N2_TPI", 0);
-  return pin == 4 || pin == 16 ? pin == 16 : count <= kN2RowMax;
-}
-
-// Adds of a few elements run one 16-wave block per element (k_mulmod_wave,
-// 2048-bit keys) up to kWaveAddMax elements, with or without alignment
-// squarings (kWaveAddMinD: the plain product of the LR step's noise add, 15
-// elements, took 56 us in the 16-lane k_mulmod_n2). $XHE_ADD_WAVE=0 keeps
-// the lane shapes (A/B).
-constexpr int64_t kWaveAddMax = 256;
-constexpr int kWaveAddMinD = 0;
-bool add_wave_on() {
-  static const bool on = env_on("XHE_ADD_WAVE");
-  return on;
-}
-
-
-// Equal-exponent adds of 2048-bit ciphertexts in the 4-lane regime run the
-// one-product Barrett kernel (k_add_barrett); $XHE_ADD_BAR=0 keeps the
-// Montgomery pair (k_mulmod_n2) for the A/B.
-bool add_bar_on() {
-  static const bool on = env_on("XHE_ADD_BAR");
-  return on;
-}
+// The n^2 ciphertext ops below run in the shape their entry point chose
+// (paths::n2_shape): MN2 is Sh::MN2X for ROW16, else the batch shape.
 
 template <class Sh, class MN2 = typename Sh::MN2>
 void mulmod_impl(const xhe_key* k, const uint32_t* a, const int32_t* ea, const uint32_t* b, const int32_t* eb,
                  int64_t count, int dmax, uint32_t* out, int32_t* eout, hipStream_t s) {
-  if constexpr (Sh::K == 2048) {
-    if (count <= kWaveAddMax && dmax >= kWaveAddMinD && add_wave_on()) {
-      launch((k_mulmod_wave<WaveN2::K_, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, a, ea, b, eb, count, out, eout);
-      return;
-    }
-  }
-  if constexpr (Sh::K == 2048 && MN2::TPI == 4) {
-    if (dmax == 0 && add_bar_on()) {
-      ProfScope ps("k_add_barrett", s);
-      const int64_t blocks = (count + bar::EPB - 1) / bar::EPB;
-      launch(k_add_barrett, dim3((unsigned)blocks), dim3(bar::TPB), s, k->kd, a, ea, b, eb, count, out, eout);
-      return;
-    }
+  switch (paths::add(Sh::K, MN2::TPI, count, dmax, pins())) {
+    case paths::Add::WAVE:
+      if constexpr (Sh::K == 2048) {
+        launch((k_mulmod_wave<WaveN2::K_, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, a, ea, b, eb, count, out, eout);
+        return;
+      } else no_path("mulmod (k_mulmod_wave)");
+    case paths::Add::BARRETT:
+      if constexpr (Sh::K == 2048 && MN2::TPI == 4) {
+        ProfScope ps("k_add_barrett", s);
+        const int64_t blocks = (count + bar::EPB - 1) / bar::EPB;
+        launch(k_add_barrett, dim3((unsigned)blocks), dim3(bar::TPB), s, k->kd, a, ea, b, eb, count, out, eout);
+        return;
+      } else no_path("mulmod (k_add_barrett)");
+    case paths::Add::MONT:
+      break;
+    default:
+      no_path("mulmod");
   }
   int64_t chunk = std::min<int64_t>(count, kChunk);
   WsScope wsc(s);
@@ -1045,8 +988,8 @@ void mulmod_impl(const xhe_key* k, const uint32_t* a, const int32_t* ea, const u
 template <class Sh, class MN2 = typename Sh::MN2>
 void powmod_impl(const xhe_key* k, const uint32_t* c, const uint32_t* kw_, int kw, int kbits, int64_t count,
                  uint32_t* out, hipStream_t s) {
-  if constexpr (Sh::K == 2048 && MN2::TPI == 4) {
-    if (k->kd.ndig && ndig_on()) {
+  if (paths::powmod(Sh::K, MN2::TPI, k->kd.ndig, pins()) == paths::Pow::NDIG) {
+    if constexpr (Sh::K == 2048 && MN2::TPI == 4) {
       ndig_run(
           count, s,
           [&](int b, int64_t off, int64_t n, uint2* st) {
@@ -1061,7 +1004,7 @@ void powmod_impl(const xhe_key* k, const uint32_t* c, const uint32_t* kw_, int k
                    out + (size_t)off * k->n2w, rows);
           });
       return;
-    }
+    } else no_path("powmod (k_ndig_pow_k)");
   }
   int64_t chunk = std::min<int64_t>(count, kChunk);
   int pb = pow_grid<MN2>(chunk, 512);
@@ -1088,8 +1031,8 @@ int invert_impl(const xhe_key* k, const uint32_t* c, int64_t count, uint32_t* ou
     offs.push_back(tot);
     tot += (size_t)S4 * n;
   }
+  if (paths::invert(Sh::K, MN2::TPI, count) == paths::Invert::WTREE) {
   if constexpr (Sh::K == 2048 && MN2::TPI == 16) {  // (a 1024-thread block: the 16-lane 2048-bit shape's registers)
-  if (count <= 256) {
     // small batch: a product tree of whole-block products (dec_wave.hpp
     // k_wtree_*), one launch per level
     constexpr int KW = WaveN2::K_;
@@ -1126,7 +1069,7 @@ int invert_impl(const xhe_key* k, const uint32_t* c, int64_t count, uint32_t* ou
     launch((k_wtree_out<KW, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, inv, out);
     HIPCHK(hipStreamSynchronize(s));  // yinv is host memory of this frame
     return XHE_OK;
-  }
+  } else no_path("invert (k_wtree_*)");
   }
   // (freed synchronously on return; st_ is read by no kernel, kept so that the call allocates as it did)
   DevBuf st_, scr_, inv_, lv_;
@@ -1311,8 +1254,7 @@ void segprod_impl(const xhe_key* k, const uint32_t* c, const int32_t* d, int dma
   DevBuf rows, sq;
   // no alignment anywhere: the first level reads the ciphertext words itself
   // ($XHE_SUM_WORDS=0: the k_align_mont transpose first, A/B)
-  static const bool words_on = env_on("XHE_SUM_WORDS");
-  const bool direct = count > 0 && (dmax == 0 || !d) && words_on;
+  const bool direct = paths::segprod_first(count, dmax, d != nullptr, pins()) == paths::SegFirst::WORDS;
   if (!direct) {
     rows = DevBuf((size_t)S4 * std::max<int64_t>(count, 1) * 4, s, DevBuf::kAsync);
     sq = DevBuf((size_t)S4 * std::max<int64_t>(count, 1) * 4, s, DevBuf::kAsync);
@@ -1385,18 +1327,20 @@ void multiexp_impl(const xhe_key* k, const uint32_t* bases, int64_t nbases, cons
   sq = DevBuf((size_t)S4 * ncols * 4, s, DevBuf::kAsync);
   {
     ProfScope ps("k_mexp_horner", s);
-    bool wave = false;
-    if constexpr (Sh::K == 2048 && MN2::TPI == 16) {
-      // small batches: one 16-wave block per column (latency; k_mexp_horner_wave)
-      static const bool on = env_on("XHE_MEXP_WAVE");
-      if (on && ncols <= 4096) {
-        launch((k_mexp_horner_wave<WaveN2::K_, 16>), dim3((unsigned)ncols), dim3(1024), s, k->kd, P, nwin, c, ncols, out);
-        wave = true;
-      }
+    switch (paths::mexp_horner(Sh::K, MN2::TPI, ncols, pins())) {
+      case paths::Horner::WAVE:
+        // small batches: one 16-wave block per column (latency; k_mexp_horner_wave)
+        if constexpr (Sh::K == 2048 && MN2::TPI == 16) {
+          launch((k_mexp_horner_wave<WaveN2::K_, 16>), dim3((unsigned)ncols), dim3(1024), s, k->kd, P, nwin, c, ncols, out);
+          break;
+        } else no_path("multiexp (k_mexp_horner_wave)");
+      case paths::Horner::LANES:
+        launch(k_mexp_horner<MN2>, blocks(ncols), dim3(256), s, k->kd, n2h<MN2>(k).N, P, nwin, c, ncols,
+               sq.as<uint32_t>(), out);
+        break;
+      default:
+        no_path("multiexp");
     }
-    if (!wave)
-      launch(k_mexp_horner<MN2>, blocks(ncols), dim3(256), s, k->kd, n2h<MN2>(k).N, P, nwin, c, ncols,
-             sq.as<uint32_t>(), out);
   }
 }
 
@@ -1414,26 +1358,8 @@ void raw_encrypt_impl(const xhe_key* k, const uint32_t* m, int64_t count, uint32
   }
 }
 
-// Decrypt exponentiation shapes by batch size (latency- vs throughput-bound):
-// one 16-lane DPP row per residue up to kDecRowMax elements, 4 lanes up to
-// kDecQuadMax, one lane beyond (crossovers measured with tools/dec_shapes.py:
-// 16 lanes 6.0 ms flat to 1 k elements, 8.9 ms at 4 k, 15.8 ms at 8 k vs
-// 11.3/11.8/11.9 ms for 4 lanes; 4 lanes 20-21 ms at 16 k vs 36 ms for 1
-// lane, 40 ms at 32 k vs 37 ms). $XHE_DEC_TPI (1, 4 or 16) pins one shape.
-constexpr int64_t kDecRowMax = 5120;
-// One block of rns::NT = 384 threads (six waves; two blocks per CU by its
-// launch bounds) per residue (k_dec_rns, 2048-bit keys) up to kDecWaveMax
-// elements (tools/dec_shapes.py, profiles/r6: 1,024 elements
-// 5.68 ms vs 6.11 ms in 16 lanes, 1,536 8.34 vs 6.13 ms); $XHE_DEC_TPI=64
-// pins it.
-constexpr int64_t kDecWaveMax = 1024;
-constexpr int64_t kDecQuadMax = 28672;
-
-int dec_tpi_override() {
-  static const int t = (int)env_int("XHE_DEC_TPI", 0);
-  return (t == 1 || t == 4 || t == 16 || t == 64) ? t : 0;
-}
-
+// The decrypt exponentiation in the lane shape paths::decrypt chose (SHAPE 2:
+// MP2X, one 16-lane row per residue; 1: MP2L, 4 lanes; 0: the batch shape).
 template <class MP2S, int SHAPE, class MP2>
 void dec_pow_launch(const xhe_key* k, const uint32_t* ct, int64_t n, int64_t chunk, uint32_t* xrows,
                     hipStream_t s) {
@@ -1470,12 +1396,6 @@ void dec_pmd_launch(const xhe_key* k, const uint32_t* ct, int64_t n, int64_t chu
          (int)MP2::S4, xrows);
 }
 
-// $XHE_DEC_PMDX=0: the Montgomery decrypt shapes instead (A/B measurement)
-bool dec_pmdx_on() {
-  static const bool on = env_on("XHE_DEC_PMDX");
-  return on;
-}
-
 // 3072/4096-bit decrypt in Montgomery digits up to m_P (k_dec_pmdx_*, see
 // xhe_kernels.hpp): writes mrows [prime][2 S4][count] as k_dec_fin does
 template <class Sh>
@@ -1508,27 +1428,11 @@ void dec_pmdx_launch(const xhe_key* k, const uint32_t* ct, int64_t n, int64_t ch
   launch(k_words_to_rows<MP>, dim3((unsigned)((n * MP::TPI + 255) / 256), 2), dim3(256), s, words, NWH, n, mrows);
 }
 
-// $XHE_DEC_RNS=0: the small-batch 2048-bit decrypt on k_dec_wave (the
-// WaveMont product) instead of k_dec_rns (A/B measurement)
-bool dec_rns_on() {
-  static const bool on = env_on("XHE_DEC_RNS");
-  return on;
-}
-
 template <class Sh>
 void decrypt_impl(const xhe_key* k, const uint32_t* ct, int64_t count, uint32_t* m, hipStream_t s) {
   using MP2 = typename Sh::MP2;
   using MP = typename Sh::MP;
-  const int pin = dec_tpi_override();
-  // Multi-lane key sizes take the 4-lane shape for every larger batch: at 3072
-  // bits the 2-lane batch shape (55 limbs per lane) decrypted 25.5 k/s where
-  // 4096 bits in 4 lanes reach 133 k/s (profiles/r1/keysizes/).
-  constexpr bool wave_ok = Sh::K == 2048;
-  const int tpi = pin ? (pin == 64 && !wave_ok ? 16 : pin)
-                      : (wave_ok && count <= kDecWaveMax)          ? 64
-                      : count <= kDecRowMax                        ? 16
-                      : (count <= kDecQuadMax || MP2::TPI > 1) ? 4
-                                                                   : 1;
+  const paths::Dec path = paths::decrypt(Sh::K, MP2::TPI, k->kd.pmdx_dec, k->kd.rns, count, pins());
   int64_t chunk = std::min<int64_t>(count, kChunk);
   WsScope wsc(s);
   uint32_t* xrows = wsc.get<uint32_t>((size_t)2 * MP2::S4 * chunk * sizeof(uint32_t));
@@ -1536,32 +1440,46 @@ void decrypt_impl(const xhe_key* k, const uint32_t* ct, int64_t count, uint32_t*
   for (int64_t off = 0; off < count; off += chunk) {
     int64_t n = std::min(chunk, count - off);
     const uint32_t* cto = ct + (size_t)off * k->n2w;
-    if constexpr (Sh::K == 3072 || Sh::K == 4096 || Sh::K == 8192) {
-      if (k->kd.pmdx_dec && dec_pmdx_on() && (pin ? pin == 1 : tpi == 4)) {
-        // batches: digits (the 16-lane shape keeps the small ones)
-        dec_pmdx_launch<Sh>(k, cto, n, chunk, mrows, s);
-        const int cblocks = (int)((n * MP::TPI + 255) / 256);
-        launch(k_crt_dec<MP>, dim3(cblocks), dim3(256), s, k->kd, k->kd.p.N, n, mrows, m + (size_t)off * k->nw);
-        continue;
-      }
-    }
-    if (tpi == 64) {
-      if constexpr (wave_ok) {
-        static_assert(MP2::S == 74 && MP2::W == 28, "k_dec_wave / k_dec_rns share the MP2 limbs");
-        if (k->kd.rns && dec_rns_on()) {
+    const int blocks = (int)((n * MP::TPI + 255) / 256);
+    // the exponentiation into xrows (PMDX goes on to m_P itself: it writes mrows)
+    switch (path) {
+      case paths::Dec::PMDX:
+        if constexpr (Sh::K != 2048) {
+          dec_pmdx_launch<Sh>(k, cto, n, chunk, mrows, s);
+          launch(k_crt_dec<MP>, dim3(blocks), dim3(256), s, k->kd, k->kd.p.N, n, mrows, m + (size_t)off * k->nw);
+          continue;
+        } else no_path("decrypt (k_dec_pmdx_pow)");
+      case paths::Dec::RNS:
+        if constexpr (Sh::K == 2048) {
+          static_assert(MP2::S == 74 && MP2::W == 28, "k_dec_wave / k_dec_rns share the MP2 limbs");
           ProfScope ps("k_dec_rns", s);
           launch(k_dec_rns, dim3((unsigned)n, 2), dim3(rns::NT), s, k->kd, cto, n, (int)MP2::S4, xrows);
-        } else {
+        } else no_path("decrypt (k_dec_rns)");
+        break;
+      case paths::Dec::WAVE:
+        if constexpr (Sh::K == 2048) {
           ProfScope ps("k_dec_wave", s);
           launch((k_dec_wave<74, XHE_DEC_NWV>), dim3((unsigned)n, 2), dim3(64 * XHE_DEC_NWV), s, k->kd, cto, n,
                  (int)MP2::S4, xrows);
-        }
-      }
-    } else if (tpi == 16) dec_pow_launch<typename Sh::MP2X, 2, MP2>(k, cto, n, chunk, xrows, s);
-    else if (tpi == 4) dec_pow_launch<typename Sh::MP2L, 1, MP2>(k, cto, n, chunk, xrows, s);
-    else if constexpr (Sh::K == 2048) dec_pmd_launch<MP2>(k, cto, n, chunk, xrows, s);
-    else dec_pow_launch<MP2, 0, MP2>(k, cto, n, chunk, xrows, s);
-    int blocks = (int)((n * MP::TPI + 255) / 256);
+        } else no_path("decrypt (k_dec_wave)");
+        break;
+      case paths::Dec::ROW16:
+        dec_pow_launch<typename Sh::MP2X, 2, MP2>(k, cto, n, chunk, xrows, s);
+        break;
+      case paths::Dec::QUAD4:
+        dec_pow_launch<typename Sh::MP2L, 1, MP2>(k, cto, n, chunk, xrows, s);
+        break;
+      case paths::Dec::PMD1:
+        if constexpr (Sh::K == 2048) dec_pmd_launch<MP2>(k, cto, n, chunk, xrows, s);
+        else no_path("decrypt (k_dec_pmd_pow)");
+        break;
+      case paths::Dec::POW1:
+        if constexpr (Sh::K != 2048) dec_pow_launch<MP2, 0, MP2>(k, cto, n, chunk, xrows, s);
+        else no_path("decrypt (k_dec_pow, batch shape)");
+        break;
+      default:
+        no_path("decrypt");
+    }
     launch((k_dec_fin<MP2, MP>), dim3(blocks, 2), dim3(256), s, k->kd, k->kd.p.N, k->kd.q.N, n, xrows, mrows);
     launch(k_crt_dec<MP>, dim3(blocks), dim3(256), s, k->kd, k->kd.p.N, n, mrows, m + (size_t)off * k->nw);
   }
@@ -1589,7 +1507,7 @@ int xhe_segprod(const xhe_key* key, const uint32_t* c_dev, const int32_t* d_dev,
     for (int64_t i = 0; i < nseg; ++i)
       if (seg_begin[i + 1] < seg_begin[i]) return fail(XHE_EINVAL, "xhe_segprod: offsets must be non-decreasing");
     DevGuard dg(key->device);
-    const bool row = n2_row(count);
+    const bool row = paths::n2_shape(count, pins()) == paths::N2Shape::ROW16;
     hipStream_t hs = (hipStream_t)stream;
     with_shape(key->K, [&](auto sh) {
       using Sh = decltype(sh);
@@ -2327,7 +2245,7 @@ int xhe_mulmod(const xhe_key* key, const uint32_t* a_dev, const int32_t* ea_dev,
       return fail(XHE_EINVAL, "xhe_mulmod: bad argument");
     if (count <= 0) return XHE_OK;
     DevGuard dg(key->device);
-    const bool row = n2_row(count);
+    const bool row = paths::n2_shape(count, pins()) == paths::N2Shape::ROW16;
     hipStream_t hs = (hipStream_t)stream;
     return with_shape(key->K, [&](auto sh) -> int {
       using Sh = decltype(sh);
@@ -2350,7 +2268,7 @@ int xhe_powmod(const xhe_key* key, const uint32_t* c_dev, const uint32_t* k_dev,
       return fail(XHE_EINVAL, "xhe_powmod: bad argument");
     if (count <= 0) return XHE_OK;
     DevGuard dg(key->device);
-    const bool row = n2_row(count);
+    const bool row = paths::n2_shape(count, pins()) == paths::N2Shape::ROW16;
     hipStream_t hs = (hipStream_t)stream;
     with_shape(key->K, [&](auto sh) {
       using Sh = decltype(sh);
@@ -2366,7 +2284,7 @@ int xhe_invert(const xhe_key* key, const uint32_t* c_dev, int64_t count, uint32_
     if (!key || (count > 0 && (!c_dev || !out_dev))) return fail(XHE_EINVAL, "xhe_invert: null argument");
     if (count <= 0) return XHE_OK;
     DevGuard dg(key->device);
-    const bool row = n2_row(count);
+    const bool row = paths::n2_shape(count, pins()) == paths::N2Shape::ROW16;
     hipStream_t hs = (hipStream_t)stream;
     return with_shape(key->K, [&](auto sh) -> int {
       using Sh = decltype(sh);
@@ -2527,7 +2445,7 @@ int xhe_multiexp(const xhe_key* key, const uint32_t* bases_dev, int64_t nbases, 
     if (ncols * nterms > (int64_t)1 << 31 || nbases > (int64_t)1 << 30)
       return fail(XHE_EINVAL, "xhe_multiexp: problem too large for one call");
     DevGuard dg(key->device);
-    const bool row = n2_row(std::max(nbases, ncols));
+    const bool row = paths::n2_shape(std::max(nbases, ncols), pins()) == paths::N2Shape::ROW16;
     const int s4 = with_shape(key->K, [&](auto sh) -> int {
       using Sh = decltype(sh);
       return row ? Sh::MN2X::S4 : Sh::MN2::S4;

@@ -2642,21 +2642,6 @@ __global__ void __launch_bounds__(256, 2) k_tab_to_pmd(ModDev mp, const uint32_t
   }
 }
 
-// Montgomery product of two rows (host-side setup helper / unit tests):
-// out = x * y * R^-1 mod M, canonical.
-template <class MP2>
-__global__ void k_mont_rows(ModDev md, const uint32_t* x, const uint32_t* y, uint32_t* out, int64_t count) {
-  int64_t gidx = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MP2::TPI;
-  if (gidx >= count) return;
-  MP2 M;
-  M.init(md.N, md.n0inv);
-  uint32_t b[MP2::L];
-  M.load_row(b, x + (size_t)gidx * MP2::S4);
-  M.mul(b, ARow{y + (size_t)gidx * MP2::S4});
-  M.reduce_once(b);
-  M.store_row(b, out + (size_t)gidx * MP2::S4);
-}
-
 // ============================================================== decode
 // A magnitude read word by word from the bottom, kept as the four words ending
 // at its highest nonzero one (w4[3] = word hk) and the OR of every word below
