@@ -188,6 +188,18 @@ int xhe_scatter_rows(const uint32_t* src_dev, const int64_t* idx_dev, int64_t co
  * words, n2w <= 1023): the per-element input of xhe_wire_layout, so the
  * serialize payload is sized before the ciphertexts are downloaded. */
 int xhe_row_bits(const uint32_t* words_dev, int64_t count, int n2w, int16_t* bits_dev, void* stream);
+/* The receiving direction (Paillier.ciphertext_from, paillier.py:260-271):
+ * rows_dev[i][0..n2w) = the len_dev[i] little-endian bytes at bytes_dev[
+ * off_dev[i] ..], zero-extended to 4 n2w bytes (a longer len is cut to that) -
+ * the values of a payload's elements as xhe_wire_scan located them, straight
+ * into a resident array's rows. n2w a multiple of 4, at most 512; bytes_dev
+ * 4-byte and rows_dev 16-byte aligned (else XHE_EINVAL). off / len derive from
+ * bytes a remote party sent and are not trusted: whatever they hold, no load
+ * leaves [bytes_dev, bytes_dev + nbytes) - bytes outside read as zero, with no
+ * padding behind the buffer - and no store leaves the count rows. Needs no
+ * key and no workspace. */
+int xhe_wire_unpack(const uint8_t* bytes_dev, int64_t nbytes, const uint32_t* off_dev, const uint16_t* len_dev,
+                    int64_t count, int n2w, uint32_t* rows_dev, void* stream);
 /* Host only (no device): the constant blocks k_dec_rns reads for the prime P
  * (p_words: pw words) - the bases' block (shared_out: XHE_RNS_SHARED_WORDS)
  * and P's block (prime_out: XHE_RNS_PRIME_WORDS); for tests against
@@ -281,6 +293,25 @@ int xhe_wire_layout_part(const int16_t* bits, const int32_t* exps, int64_t lo, i
 int xhe_wire_layout_part_rows(const uint32_t* rows, const int32_t* exps, int64_t lo, int64_t hi, int64_t count,
                               int n2w, int64_t* elem_off);
 int xhe_wire_finish(int64_t count, const int64_t* elem_off, int framed, uint8_t* out, int64_t cap, int64_t* out_len);
+/* The index of a payload in the library's own layout (what xhe_wire_encode
+ * writes), for a decode on the device (xhe_wire_unpack): per element the byte
+ * offset of its value in data (off), the value's used length (vlen: top zero
+ * bytes trimmed, at most 4 n2w) and its exponent - the same scan as
+ * xhe_wire_decode's fast path, with the same rejections (negative values,
+ * values above n2w words), writing no words. Range by range: data[0..len) is
+ * the payload from its first byte (elem0 == 0: shape / ndim are set, the
+ * element count is their product) or from the boundary of element elem0
+ * (where the previous range's *next pointed); len < 2^32. last != 0: the
+ * range reaches the payload's end (the footer must close it exactly at len);
+ * else the scan stops at the first element that is not whole in the range.
+ * *found = whole elements of the range (entries 0..found-1 of off / vlen /
+ * exps), *next = offset in data of the first byte behind them. XHE_ENOTSUP at
+ * the first deviation from the own layout (the caller decodes with
+ * xhe_wire_decode, whose general machine accepts or rejects everything else);
+ * XHE_EOVERFLOW with *found set when cap is smaller (the first cap entries
+ * are written). Every off[k] + vlen[k] <= len. n2w <= 512. */
+int xhe_wire_scan(const uint8_t* data, int64_t len, int64_t elem0, int last, int n2w, uint32_t* off, uint16_t* vlen,
+                  int32_t* exps, int64_t cap, int64_t* found, int64_t* next, int64_t* shape, int* ndim);
 
 /* A zstd frame (RFC 8878, one frame, content size in the header) holding
  * src[0..n) as raw blocks, written by several host threads: what
@@ -298,6 +329,19 @@ int xhe_zstd_raw_frame(const uint8_t* src, int64_t n, uint8_t* dst, int64_t cap,
  * content size; XHE_ENOTSUP for any other frame (the caller then uses
  * libzstd), XHE_EOVERFLOW when cap is too small. */
 int xhe_zstd_raw_extract(const uint8_t* src, int64_t len, uint8_t* dst, int64_t cap, int64_t* out_len);
+/* The same for a part of the content, so a received payload is de-framed
+ * chunk by chunk into staging memory. probe: XHE_OK and *content_size for a
+ * frame in xhe_zstd_raw_frame's closed-form layout (raw blocks of 128 KiB, the
+ * last one shorter and flagged; every block header is checked), XHE_ENOTSUP
+ * for any other frame; nothing is extracted. extract_range: content bytes
+ * [lo, hi) of such a frame -> dst (hi - lo bytes), copied by several host
+ * threads; checks the frame header and the headers of the blocks it reads
+ * (XHE_ENOTSUP), XHE_EINVAL when hi exceeds the content size. */
+int xhe_zstd_raw_probe(const uint8_t* src, int64_t len, int64_t* content_size);
+int xhe_zstd_raw_extract_range(const uint8_t* src, int64_t len, int64_t lo, int64_t hi, uint8_t* dst);
+/* memcpy by several host threads (from 8 MiB up): unframed payload bytes
+ * into staging memory. */
+int xhe_host_memcpy(void* dst, const void* src, int64_t n);
 
 /* Touch every page of a fresh host buffer from several threads (host only),
  * so results copied in later do not take the first-touch faults on one

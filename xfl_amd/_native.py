@@ -90,6 +90,13 @@ SIGNATURES = {
     "xhe_wire_finish": (ctypes.c_int, [ctypes.c_int64, _vp, ctypes.c_int, _vp, ctypes.c_int64,
                                        ctypes.POINTER(ctypes.c_int64)]),
     "xhe_row_bits": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp]),
+    "xhe_wire_unpack": (ctypes.c_int, [_vp, ctypes.c_int64, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp]),
+    "xhe_wire_scan": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp,
+                                     ctypes.c_int64, ctypes.POINTER(ctypes.c_int64), ctypes.POINTER(ctypes.c_int64),
+                                     _vp, ctypes.POINTER(ctypes.c_int)]),
+    "xhe_zstd_raw_probe": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.POINTER(ctypes.c_int64)]),
+    "xhe_zstd_raw_extract_range": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int64, _vp]),
+    "xhe_host_memcpy": (ctypes.c_int, [_vp, _vp, ctypes.c_int64]),
     "xhe_rns_constants": (ctypes.c_int, [_vp, ctypes.c_int, _vp, _vp]),
     "xhe_wire_decode": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, ctypes.c_int64,
                                        ctypes.POINTER(ctypes.c_int64), _vp, ctypes.POINTER(ctypes.c_int)]),

@@ -169,6 +169,23 @@ def _raw_extract(data):
     return out
 
 
+def raw_frame_size(data):
+    """content size of a raw-block frame in compress()'s closed-form layout
+    (xhe_zstd_raw_probe: nothing is extracted - ciphertext_from's device path
+    de-frames it chunk by chunk), or None for any other frame"""
+    if len(data) < RAW_FRAME_MIN:
+        return None
+    from . import _native as nat
+    try:
+        L = nat.lib()
+    except Exception:
+        return None
+    n = ctypes.c_int64()
+    if L.xhe_zstd_raw_probe(data, len(data), ctypes.byref(n)) != nat.XHE_OK:
+        return None
+    return n.value
+
+
 def decompress(data: bytes) -> bytes:
     if len(data) >= RAW_FRAME_MIN:
         out = _raw_extract(data)

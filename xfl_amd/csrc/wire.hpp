@@ -816,11 +816,61 @@ std::string emitted(F&& f) {
 }
 
 // Fast path for the exact byte layout `encode` writes (what our peers send):
-// one linear scan, a memcpy per value, no pickle machine. Returns -1 at the
-// first deviation from that layout; decode() then runs the general machine,
-// which accepts (or rejects) every other form of the same object graph.
-inline int64_t decode_own(const uint8_t* p, int64_t len, int n2w, uint32_t* ct, int32_t* exps, int64_t cap_count,
-                          int64_t* shape, int* ndim) {
+// one linear scan, no pickle machine. The scan is written once and hands
+// every element's value to a sink: RowSink copies it into its row (decode_own,
+// the host decode), IndexSink records where it lies (xhe_wire_scan: the device
+// decode unpacks the rows from the payload's bytes in HBM). Any deviation from
+// that layout ends the scan with status -1; decode() then runs the general
+// machine, which accepts (or rejects) every other form of the same object
+// graph.
+//
+// The scan runs over a whole payload or range by range: a range starts at the
+// payload's first byte (elem0 == 0: header and shape are read) or at the
+// boundary of element elem0 (the `next` of the range before it). A range that
+// is not the `last` one ends at its first incomplete element: an element
+// counts as whole only with the two bytes behind it (the 'e' that may close
+// its block of 1000 and the byte that tells the list's end), so the footer's
+// three bytes always belong to the last range. The last range must end with
+// the footer, exactly at len.
+struct Scan {
+  int status = 0;     // 0: own layout so far, -1: not this layout
+  int64_t found = 0;  // whole elements of the range
+  int64_t next = 0;   // position behind them: the first incomplete element, or the list's end
+};
+
+// value -> row k of ct (rows beyond cap are counted, not written)
+struct RowSink {
+  uint32_t* ct;
+  int32_t* exps;
+  int64_t cap;
+  int n2w;
+  void put(int64_t k, const uint8_t*, const uint8_t* val, int64_t used, int32_t e) const {
+    if (k >= cap) return;
+    uint8_t* row = (uint8_t*)(ct + (size_t)k * n2w);
+    memcpy(row, val, (size_t)used);
+    memset(row + used, 0, (size_t)(4 * (int64_t)n2w - used));
+    exps[k] = e;
+  }
+};
+
+// value -> its byte offset in the range and its used length (top zero bytes
+// trimmed, at most 4 n2w: 2048 fits 16 bits)
+struct IndexSink {
+  uint32_t* off;
+  uint16_t* len;
+  int32_t* exps;
+  int64_t cap;
+  void put(int64_t k, const uint8_t* base, const uint8_t* val, int64_t used, int32_t e) const {
+    if (k >= cap) return;
+    off[k] = (uint32_t)(val - base);
+    len[k] = (uint16_t)used;
+    exps[k] = e;
+  }
+};
+
+template <class Sink>
+Scan scan_own(const uint8_t* p, int64_t len, int64_t elem0, bool last, int n2w, const Sink& sink, int64_t* shape,
+              int* ndim) {
   static const std::string A = emitted([](Writer& w) { emit_header_a(w); });
   static const std::string B = emitted([](Writer& w) { emit_header_b(w); });
   static const std::string CLS = emitted([](Writer& w) {
@@ -832,102 +882,163 @@ inline int64_t decode_own(const uint8_t* p, int64_t len, int n2w, uint32_t* ct, 
   static const std::string VAL = emitted([](Writer& w) { w.str("value"); w.put(0x94); });
   static const std::string EXP = emitted([](Writer& w) { w.str("exp"); w.put(0x94); });
   int64_t pos = 0;
+  bool ran_out = false;  // the last failed step wanted bytes beyond len
   auto lit = [&](const std::string& s) {
-    if (len - pos < (int64_t)s.size() || memcmp(p + pos, s.data(), s.size()) != 0) return false;
+    if (len - pos < (int64_t)s.size()) {
+      ran_out = true;
+      return false;
+    }
+    if (memcmp(p + pos, s.data(), s.size()) != 0) return false;
     pos += (int64_t)s.size();
     return true;
   };
   auto byte = [&](uint8_t b) {
-    if (pos < len && p[pos] == b) {
-      ++pos;
-      return true;
+    if (pos >= len) {
+      ran_out = true;
+      return false;
     }
-    return false;
+    if (p[pos] != b) return false;
+    ++pos;
+    return true;
   };
   auto le = [&](int k, uint64_t* v) {
-    if (len - pos < k) return false;
+    if (len - pos < k) {
+      ran_out = true;
+      return false;
+    }
     uint64_t x = 0;
     for (int i = 0; i < k; ++i) x |= (uint64_t)p[pos + i] << (8 * i);
     pos += k;
     *v = x;
     return true;
   };
-  if (!lit(A)) return -1;
-  int nd = 0;
-  while (pos < len && p[pos] != 't') {
-    if (nd >= 8) return -1;
-    uint64_t v;
-    uint8_t op = p[pos++];
-    if (op == 'K') {
-      if (!le(1, &v)) return -1;
-    } else if (op == 'J') {
-      if (!le(4, &v)) return -1;
-      v = (uint64_t)(int64_t)(int32_t)(uint32_t)v;
-    } else if (op == 0x8a) {
-      uint64_t k;
-      if (!le(1, &k) || k != 8 || !le(8, &v)) return -1;
-    } else {
-      return -1;
+  Scan r;
+  const Scan bad{-1, 0, 0};
+  if (elem0 == 0) {  // the header is read whole from the first range
+    if (!lit(A)) return bad;
+    int nd = 0;
+    while (pos < len && p[pos] != 't') {
+      if (nd >= 8) return bad;
+      uint64_t v;
+      uint8_t op = p[pos++];
+      if (op == 'K') {
+        if (!le(1, &v)) return bad;
+      } else if (op == 'J') {
+        if (!le(4, &v)) return bad;
+        v = (uint64_t)(int64_t)(int32_t)(uint32_t)v;
+      } else if (op == 0x8a) {
+        uint64_t k;
+        if (!le(1, &k) || k != 8 || !le(8, &v)) return bad;
+      } else {
+        return bad;
+      }
+      shape[nd++] = (int64_t)v;
     }
-    shape[nd++] = (int64_t)v;
+    if (!lit(B)) return bad;
+    *ndim = nd;
   }
-  if (!lit(B)) return -1;
-  int64_t i = 0;
   const int64_t wbytes = 4 * (int64_t)n2w;
-  while (true) {
+  // one element at pos: 1 = whole (val, used, e set; pos behind it and its
+  // block's 'e'), 0 = none here, `ended` tells why: the list's end, or bytes
+  // that ran out / deviate (ran_out tells which)
+  const uint8_t* val = nullptr;
+  int64_t used = 0, e = 0;
+  bool ended = elem0 > 0 && pos < len && p[pos] == 't';  // the range before read the list's last element
+  auto elem = [&](int64_t i) {
+    ran_out = false;
     if (i % 1000 == 0) {
-      if (pos < len && p[pos] == 't') break;  // end of the list (no element opens a block here)
-      if (!byte('(')) return -1;
+      if (pos < len && p[pos] == 't') {  // end of the list (no element opens a block here)
+        ended = true;
+        return false;
+      }
+      if (!byte('(')) return false;
     }
-    if (i == 0 ? !lit(CLS) : !(byte('h') && byte(1))) return -1;
-    if (!(byte(')') && byte(0x81) && byte('}') && byte('('))) return -1;
-    if (i == 0 ? !lit(VAL) : !(byte('h') && byte(2))) return -1;
+    static const uint8_t kPrefix[8] = {'h', 1, ')', 0x81, '}', '(', 'h', 2};  // every element but the first
+    if (i > 0 && len - pos >= 8) {
+      if (memcmp(p + pos, kPrefix, 8) != 0) return false;
+      pos += 8;
+    } else {  // the first element's strings; or bytes that may run out: one by one
+      if (i == 0 ? !lit(CLS) : !(byte('h') && byte(1))) return false;
+      if (!(byte(')') && byte(0x81) && byte('}') && byte('('))) return false;
+      if (i == 0 ? !lit(VAL) : !(byte('h') && byte(2))) return false;
+    }
     uint64_t nb;
     if (byte(0x8a)) {
-      if (!le(1, &nb)) return -1;
+      if (!le(1, &nb)) return false;
     } else if (byte(0x8b)) {
-      if (!le(4, &nb)) return -1;
+      if (!le(4, &nb)) return false;
     } else {
-      return -1;
+      return false;
     }
-    if ((int64_t)nb > len - pos) return -1;
-    const uint8_t* val = p + pos;
+    if ((int64_t)nb > len - pos) {
+      ran_out = true;
+      return false;
+    }
+    val = p + pos;
     pos += (int64_t)nb;
-    int64_t used = (int64_t)nb;
-    if (used > 0 && (val[used - 1] & 0x80)) return -1;  // negative: not a ciphertext
+    used = (int64_t)nb;
+    if (used > 0 && (val[used - 1] & 0x80)) return false;  // negative: not a ciphertext
     while (used > 0 && val[used - 1] == 0) --used;
-    if (used > wbytes) return -1;
-    if (i == 0 ? !lit(EXP) : !(byte('h') && byte(3))) return -1;
-    int64_t e;
+    if (used > wbytes) return false;  // value too large
+    if (i == 0 ? !lit(EXP) : !(byte('h') && byte(3))) return false;
     uint64_t v;
     if (byte('K')) {
-      if (!le(1, &v)) return -1;
+      if (!le(1, &v)) return false;
       e = (int64_t)v;
     } else if (byte('J')) {
-      if (!le(4, &v)) return -1;
+      if (!le(4, &v)) return false;
       e = (int64_t)(int32_t)(uint32_t)v;
     } else {
-      return -1;
+      return false;
     }
-    if (!(byte('u') && byte('b'))) return -1;
-    if (i < cap_count) {
-      uint8_t* row = (uint8_t*)(ct + (size_t)i * n2w);
-      memcpy(row, val, (size_t)used);
-      memset(row + used, 0, (size_t)(wbytes - used));
-      exps[i] = (int32_t)e;
+    if (!(byte('u') && byte('b'))) return false;
+    if (!last && len - pos < 2) {  // whole only with the two bytes that tell what follows
+      ran_out = true;
+      return false;
     }
-    ++i;
     const bool closes = pos < len && p[pos] == 'e';
     if (closes) ++pos;
-    if ((i % 1000 == 0) != closes) {  // a block of 1000 closes exactly at its end, or the list ends
-      if (!closes || !(pos < len && p[pos] == 't')) return -1;
-      break;
+    if (((i + 1) % 1000 == 0) != closes) {  // a block of 1000 closes exactly at its end, or the list ends
+      if (!closes || !(pos < len && p[pos] == 't')) return false;
+      ended = true;
     }
-    if (closes && i % 1000 != 0) break;
+    return true;
+  };
+  r.next = pos;
+  for (int64_t i = elem0; !ended;) {
+    const int64_t start = pos;
+    if (!elem(i)) {
+      if (ended) break;
+      if (ran_out && !last) return r;  // the first incomplete element: the next range starts there
+      return bad;
+    }
+    sink.put(i - elem0, p, val, used, (int32_t)e);
+    // The scan reads some 20 bytes per element, one cache line in nine, each
+    // found through the length before it: a chain of misses (65 ns per
+    // element measured on 2048-bit ciphertexts, 20 to 30 ns with this). Nearly every ciphertext of
+    // one key has the same length, so the end of the element kPre ahead - its
+    // exponent and the next header - is where this element's size predicts.
+    constexpr int64_t kPre = 8;
+    const int64_t ahead = pos + kPre * (pos - start);
+    if (ahead + 32 < len) {
+      __builtin_prefetch(p + ahead - 32);
+      __builtin_prefetch(p + ahead + 32);
+    }
+    ++i;
+    ++r.found;
+    r.next = pos;
   }
-  if (!(byte('t') && byte('b') && byte('.')) || pos != len) return -1;
-  *ndim = nd;
-  return i;
+  if (last) {
+    if (!(byte('t') && byte('b') && byte('.')) || pos != len) return bad;
+    r.next = pos;
+  }
+  return r;
+}
+
+inline int64_t decode_own(const uint8_t* p, int64_t len, int n2w, uint32_t* ct, int32_t* exps, int64_t cap_count,
+                          int64_t* shape, int* ndim) {
+  const Scan r = scan_own(p, len, 0, true, n2w, RowSink{ct, exps, cap_count, n2w}, shape, ndim);
+  return r.status < 0 ? -1 : r.found;
 }
 
 // Decodes into ct [count][n2w], exps [count]; shape/ndim of the array.

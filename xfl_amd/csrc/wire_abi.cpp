@@ -332,6 +332,103 @@ int xhe_wire_decode(const uint8_t* data, int64_t len, int n2w, uint32_t* ct, int
   });
 }
 
+int xhe_wire_scan(const uint8_t* data, int64_t len, int64_t elem0, int last, int n2w, uint32_t* off, uint16_t* vlen,
+                  int32_t* exps, int64_t cap, int64_t* found, int64_t* next, int64_t* shape, int* ndim) {
+  return guarded([&]() -> int {
+    if (!data || len <= 0 || len > (int64_t)UINT32_MAX || elem0 < 0 || n2w <= 0 || n2w > 512 || cap < 0 || !found ||
+        !next || (elem0 == 0 && (!shape || !ndim)) || (cap > 0 && (!off || !vlen || !exps)))
+      return xhe_fail(XHE_EINVAL, "xhe_wire_scan: bad argument");
+    *found = 0;
+    *next = 0;
+    const xhe::wire::Scan r =
+        xhe::wire::scan_own(data, len, elem0, last != 0, n2w, xhe::wire::IndexSink{off, vlen, exps, cap}, shape, ndim);
+    if (r.status < 0) return xhe_fail(XHE_ENOTSUP, "xhe_wire_scan: not the library's own layout");
+    *found = r.found;
+    *next = r.next;
+    if (r.found > cap) return xhe_fail(XHE_EOVERFLOW, "xhe_wire_scan: index arrays too small");
+    return XHE_OK;
+  });
+}
+
+namespace {
+// The frame header of xhe_zstd_raw_extract's frames: position of the first
+// block header and the content size; false for anything else.
+bool raw_frame_head(const uint8_t* src, int64_t len, int64_t* first, int64_t* content) {
+  if (len < 6 || src[0] != 0x28 || src[1] != 0xB5 || src[2] != 0x2F || src[3] != 0xFD) return false;
+  const uint8_t fhd = src[4];
+  const int fcs_flag = fhd >> 6, single = (fhd >> 5) & 1;
+  if ((fhd & 0x0F) != 0) return false;  // reserved bit, checksum or dictionary id
+  const int fcs_bytes = fcs_flag == 0 ? (single ? 1 : 0) : (1 << fcs_flag);
+  if (fcs_bytes == 0) return false;
+  int64_t pos = 5 + (single ? 0 : 1);
+  if (pos + fcs_bytes > len) return false;
+  uint64_t fcs = 0;
+  for (int k = 0; k < fcs_bytes; ++k) fcs |= (uint64_t)src[pos + k] << (8 * k);
+  if (fcs_bytes == 2) fcs += 256;
+  if (fcs > (uint64_t)INT64_MAX / 2) return false;
+  *first = pos + fcs_bytes;
+  *content = (int64_t)fcs;
+  return true;
+}
+// Block b of a frame in the closed-form layout (every block but the last
+// kZstdBlock bytes, raw, the last one flagged): its header is checked, its
+// payload's position returned (-1: not that layout, or outside src).
+int64_t raw_block_at(const uint8_t* src, int64_t len, int64_t first, int64_t content, int64_t b) {
+  const int64_t nb = content > 0 ? (content + kZstdBlock - 1) / kZstdBlock : 1;
+  const int64_t at = first + b * (kZstdBlock + 3);
+  const int64_t size = std::min<int64_t>(kZstdBlock, content - b * kZstdBlock);
+  if (b < 0 || b >= nb || at + 3 + size > len) return -1;
+  const uint32_t h = src[at] | ((uint32_t)src[at + 1] << 8) | ((uint32_t)src[at + 2] << 16);
+  if (h != ((uint32_t)(b == nb - 1) | ((uint32_t)size << 3))) return -1;
+  return at + 3;
+}
+}  // namespace
+
+int xhe_zstd_raw_probe(const uint8_t* src, int64_t len, int64_t* content_size) {
+  if (!src || len <= 0 || !content_size) return xhe_fail(XHE_EINVAL, "xhe_zstd_raw_probe: bad argument");
+  *content_size = -1;
+  int64_t first, content;
+  if (!raw_frame_head(src, len, &first, &content) || content < 1 ||
+      len != first + content + 3 * ((content + kZstdBlock - 1) / kZstdBlock))
+    return xhe_fail(XHE_ENOTSUP, "not a closed-form raw-block zstd frame");
+  const int64_t nb = (content + kZstdBlock - 1) / kZstdBlock;
+  for (int64_t b = 0; b < nb; ++b)
+    if (raw_block_at(src, len, first, content, b) < 0)
+      return xhe_fail(XHE_ENOTSUP, "not a closed-form raw-block zstd frame");
+  *content_size = content;
+  return XHE_OK;
+}
+
+int xhe_zstd_raw_extract_range(const uint8_t* src, int64_t len, int64_t lo, int64_t hi, uint8_t* dst) {
+  if (!src || len <= 0 || !dst || lo < 0 || hi < lo)
+    return xhe_fail(XHE_EINVAL, "xhe_zstd_raw_extract_range: bad argument");
+  int64_t first, content;
+  if (!raw_frame_head(src, len, &first, &content) || content < 1)
+    return xhe_fail(XHE_ENOTSUP, "not a closed-form raw-block zstd frame");
+  if (hi > content) return xhe_fail(XHE_EINVAL, "xhe_zstd_raw_extract_range: range beyond the content");
+  if (hi == lo) return XHE_OK;
+  // the headers of the blocks the range touches are checked before any copy
+  const int64_t b0 = lo / kZstdBlock, b1 = (hi - 1) / kZstdBlock;
+  for (int64_t b = b0; b <= b1; ++b)
+    if (raw_block_at(src, len, first, content, b) < 0)
+      return xhe_fail(XHE_ENOTSUP, "not a closed-form raw-block zstd frame");
+  const int64_t nb = b1 - b0 + 1;
+  const int T = (int)std::min<int64_t>(nb, hi - lo >= (8 << 20) ? codec_threads() : 1);
+  xhe::wire::run_parallel(T, [&](int t) {
+    for (int64_t b = b0 + nb * t / T; b < b0 + nb * (t + 1) / T; ++b) {
+      const int64_t a = std::max(lo, b * kZstdBlock), z = std::min(hi, (b + 1) * kZstdBlock);
+      memcpy(dst + (a - lo), src + first + b * (kZstdBlock + 3) + 3 + (a - b * kZstdBlock), (size_t)(z - a));
+    }
+  });
+  return XHE_OK;
+}
+
+int xhe_host_memcpy(void* dst, const void* src, int64_t n) {
+  if (n < 0 || (n > 0 && (!dst || !src))) return xhe_fail(XHE_EINVAL, "xhe_host_memcpy: bad argument");
+  xhe_host_copy(dst, src, n);
+  return XHE_OK;
+}
+
 const char* xhe_last_error(void) { return g_err.c_str(); }
 const char* xhe_version(void) { return "xhe 0.2 gfx950"; }
 

@@ -28,6 +28,7 @@
 #include "barrett_dev.hpp"
 #include "rns_dev.hpp"
 #include "enc_obf_dev.hpp"
+#include "wire_unpack.hpp"
 
 using namespace xhe;
 
@@ -1835,6 +1836,26 @@ __global__ void k_move_rows(const uint32_t* __restrict__ src, const int64_t* __r
   }
 }
 
+// rows[i] = the len[i] little-endian bytes at bytes[off[i] ..] of a received
+// payload, zero-extended to n2w words (xhe_wire_unpack; the receiving side of
+// Paillier.ciphertext_from, paillier.py:260-271). Flat over the count * n2w/4
+// quads, grid-stride: consecutive lanes store consecutive 16 B of one row
+// (n2w = 192 too, which no power-of-two lane group per row would serve) and
+// read consecutive, overlapping dwords of one value. The per-quad work, with
+// its clamps against hostile off / len, is wireu::unpack_quad.
+__global__ void k_wire_unpack(const uint8_t* __restrict__ bytes, int64_t nbytes, const uint32_t* __restrict__ off,
+                              const uint16_t* __restrict__ len, int64_t count, int n2w, uint32_t* __restrict__ rows) {
+  const int qpr = n2w >> 2;
+  const int64_t tot = count * qpr;
+  for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < tot; t += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t i = t / qpr;
+    const int q = (int)(t - i * qpr);
+    uint32_t w[4];
+    xhe::wireu::unpack_quad(bytes, nbytes, off[i], len[i], n2w, q, w);
+    reinterpret_cast<uint4*>(rows)[t] = make_uint4(w[0], w[1], w[2], w[3]);  // t < count * n2w/4: inside the rows
+  }
+}
+
 // bit length of each row's value (little-endian words, row-major): what the
 // wire layout of Paillier.serialize needs per element (its LONG1/LONG4 byte
 // count, paillier.py:244-258), so the host can size the payload before the
@@ -2561,6 +2582,22 @@ int xhe_scatter_rows(const uint32_t* src_dev, const int64_t* idx_dev, int64_t co
     const int64_t tot = count * words;
     const unsigned blocks = (unsigned)std::min<int64_t>((tot + 255) / 256, 65536);
     launch(k_move_rows<true>, dim3(blocks), dim3(256), (hipStream_t)stream, src_dev, idx_dev, count, words, dst_dev);
+    return XHE_OK;
+  });
+}
+
+int xhe_wire_unpack(const uint8_t* bytes_dev, int64_t nbytes, const uint32_t* off_dev, const uint16_t* len_dev,
+                    int64_t count, int n2w, uint32_t* rows_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (count < 0 || nbytes < 0 || n2w <= 0 || n2w > 512 || n2w % 4) return fail(XHE_EINVAL, "xhe_wire_unpack: bad size");
+    if (count == 0) return XHE_OK;
+    if (!bytes_dev || !off_dev || !len_dev || !rows_dev) return fail(XHE_EINVAL, "xhe_wire_unpack: null argument");
+    if (((uintptr_t)bytes_dev & 3) || ((uintptr_t)rows_dev & 15))
+      return fail(XHE_EINVAL, "xhe_wire_unpack: bytes_dev must be 4-byte and rows_dev 16-byte aligned");
+    const int64_t tot = count * (n2w / 4);
+    const unsigned blocks = (unsigned)std::min<int64_t>((tot + 255) / 256, 65536);
+    launch(k_wire_unpack, dim3(blocks), dim3(256), (hipStream_t)stream, bytes_dev, nbytes, off_dev, len_dev, count,
+           n2w, rows_dev);
     return XHE_OK;
   });
 }

@@ -254,13 +254,22 @@ class Paillier(object):
     @staticmethod
     def ciphertext_from(context: PaillierContext, data: bytes, compression: bool = True):
         """paillier.py:260-271 -> PaillierArray (context may be None, as in
-        label_trainer.py:258; pass the key to decrypt)."""
-        from ..compat import decompress, loads
+        label_trainer.py:258; pass the key to decrypt). Large payloads in the
+        library's own layout are decoded into HBM (wire.decode_device): the
+        array comes back resident, its host copy made on first host access."""
+        from ..compat import decompress, loads, raw_frame_size
+        from . import wire
         from .array import PaillierArray
+        if context is not None and wire.WIRE_DEV and len(data) >= 16 * wire.DEV_DECODE_MIN:
+            content = raw_frame_size(data) if compression else None
+            if compression and content is None:  # any other frame: decompressed on the host, as before
+                data, compression = decompress(data), False
+            back = Paillier._ciphertext_from_device(context, wire._Source(data, content))
+            if back is not None:
+                return back
         if compression:
             data = decompress(data)
         try:  # native decode of the ciphertext-array format, straight into words
-            from . import wire
             w, e, shape = wire.decode_words(data, ops.n2w_of(context) if context is not None else None)
             return PaillierArray.from_buffers(context, w, e, shape)
         except ValueError:
@@ -271,6 +280,32 @@ class Paillier(object):
             return PaillierCiphertext(context, int(x.value), x.exp)
 
         return PaillierArray(np.vectorize(f, otypes=[PaillierCiphertext])(unpickled), context=context)
+
+    @staticmethod
+    def _ciphertext_from_device(context, src):
+        """ciphertext_from's device path: the payload `src` (wire._Source) ->
+        a resident PaillierArray, or None for everything the host path decodes
+        (fewer than wire.DEV_DECODE_MIN elements, another pickle form, host-
+        buffer mode, a result above the residency budget, bytes that turn out
+        truncated or corrupt)."""
+        from . import wire
+        from .array import PaillierArray
+        n2w = ops.n2w_of(context)
+        if src.size < 16 * wire.DEV_DECODE_MIN:  # an element is 16 bytes at least
+            return None
+        shape = wire.peek_shape(src, n2w)
+        if shape is None:
+            return None
+        count = int(np.prod(shape, dtype=np.int64)) if shape else 1
+        if count < wire.DEV_DECODE_MIN:
+            return None
+        dev = resident.device_for(context, count=count, elem_bytes=4 * n2w)
+        if dev is None:
+            return None
+        out = wire.decode_device(src, n2w, dev, shape)
+        if out is None:
+            return None
+        return PaillierArray.from_device(context, *out)
 
     @classmethod
     def encrypt(cls, context: PaillierContext, data: Union[int, float, np.ndarray], precision: Optional[int] = None,

@@ -6,6 +6,10 @@ by XFL peers (numpy 1.x or 2.x); decoding accepts CPython's pickles of that
 graph, including the reference's gmpy2 values. Host-only: no device needed.
 """
 import ctypes
+import os
+import sys
+import threading
+import time
 
 import numpy as np
 
@@ -64,19 +68,40 @@ PIPE_MIN = 1 << 16    # device arrays from this many rows serialize through the 
 PIPE_CHUNK = 1 << 17  # rows per D2H chunk (64 MB at 2048 bits)
 # rows per encryption launch of a pipelined Paillier.encrypt (resident.encrypt_floats);
 # $XHE_ENC_SUB overrides it (A/B measurement)
-ENC_SUB = int(__import__("os").environ.get("XHE_ENC_SUB", 1 << 18))
+ENC_SUB = int(os.environ.get("XHE_ENC_SUB", 1 << 18))
 _stage = {}           # (device, n2w) -> two pinned ([PIPE_CHUNK, n2w] words, [PIPE_CHUNK] bits), kept for the process
-_copy_streams = {}    # device -> the pipeline's copy stream
-_stage_lock = __import__("threading").Lock()
-_TRACE = __import__("os").environ.get("XHE_PIPE_TRACE", "0") not in ("", "0")  # per-chunk timings on stderr  # one pipeline at a time uses the pinned buffers
+_copy_streams = {}    # device -> the pipelines' copy stream
+# one pipeline at a time (serialize's or ciphertext_from's) uses the pinned
+# buffers; _stage and _copy_streams get their entries only under it
+_stage_lock = threading.Lock()
+_TRACE = os.environ.get("XHE_PIPE_TRACE", "0") not in ("", "0")  # per-chunk timings on stderr
+# $XHE_WIRE_DEV (read once): 0 keeps Paillier.ciphertext_from on the host
+# decode (A/B runs against decode_device)
+WIRE_DEV = os.environ.get("XHE_WIRE_DEV", "1").strip() != "0"
+# payloads from this many elements decode on the device (decode_device)
+DEV_DECODE_MIN = PIPE_MIN
+DEV_CHUNK = 1 << 26   # payload bytes per H2D chunk of decode_device, at most (and what the pinned pair holds)
+_STAGE_MIN_ROWS = 256  # the pinned pair's least size: a received chunk holds whole elements and their index
 
 
 def _copy_stream(dev):
+    """the copy stream of `dev` (call under _stage_lock)"""
     import torch
     s = _copy_streams.get(dev)
     if s is None:
         s = _copy_streams[dev] = torch.cuda.Stream(device=dev)
     return s
+
+
+def _stage_pair(dev, n2w, rows):
+    """the two pinned (words, bits) buffers of (dev, n2w), of at least `rows`
+    rows (call under _stage_lock)"""
+    import torch
+    st = _stage.get((dev, n2w))
+    if st is None or st[0][0].shape[0] < rows:
+        st = _stage[(dev, n2w)] = [(torch.empty((rows, n2w), dtype=torch.int32, pin_memory=True),
+                                    torch.empty(rows, dtype=torch.int16, pin_memory=True)) for _ in range(2)]
+    return st
 
 
 def encode_device(d, exps, shape, compression, dev):
@@ -132,11 +157,7 @@ def _pipeline(d, ex, count, n2w, dev, framed, off, maxlen, optr, marks):
     shared by every call); returns the payload's real size"""
     import torch
     L = nat.lib()
-    rows = min(PIPE_CHUNK, count)
-    st = _stage.get((dev, n2w))
-    if st is None or st[0][0].shape[0] < rows:
-        st = _stage[(dev, n2w)] = [(torch.empty((rows, n2w), dtype=torch.int32, pin_memory=True),
-                                    torch.empty(rows, dtype=torch.int16, pin_memory=True)) for _ in range(2)]
+    st = _stage_pair(dev, n2w, min(PIPE_CHUNK, count))
     # the bit lengths the encryption computed behind each piece (else the host
     # reads them off the rows' top words)
     bits_d = getattr(d, "_xhe_bits", None)
@@ -161,34 +182,184 @@ def _pipeline(d, ex, count, n2w, dev, framed, off, maxlen, optr, marks):
             evs[k % 2] = torch.cuda.Event()
             evs[k % 2].record(cs)
     trace = _TRACE and []
-    t0 = __import__("time").perf_counter()
+    t0 = time.perf_counter()
     try:
         issue(0)
         for k, (lo, hi) in enumerate(chunks):
             if k + 1 < len(chunks):
                 issue(k + 1)  # its buffer held chunk k - 1, written in the previous iteration
             evs[k % 2].synchronize()
-            t1 = __import__("time").perf_counter()
+            t1 = time.perf_counter()
             rp = ctypes.c_void_p(st[k % 2][0].data_ptr())
             if bits_d is not None:
                 nat.check(L.xhe_wire_layout_part(ctypes.c_void_p(st[k % 2][1].data_ptr()), _vp(ex), lo, hi, count,
                                                  n2w, _vp(off)), "wire layout")
             else:
                 nat.check(L.xhe_wire_layout_part_rows(rp, _vp(ex), lo, hi, count, n2w, _vp(off)), "wire layout")
-            t2 = __import__("time").perf_counter()
+            t2 = time.perf_counter()
             nat.check(L.xhe_wire_rows(rp, _vp(ex), lo, hi, count, n2w, _vp(off), int(framed), optr, maxlen.value),
                       "wire rows")
             if trace is not False:
-                t3 = __import__("time").perf_counter()
+                t3 = time.perf_counter()
                 trace.append((k, round((t1 - t0) * 1e3, 2), round((t2 - t1) * 1e3, 2), round((t3 - t2) * 1e3, 2)))
         if trace:
-            import sys
             print("pipeline (chunk, ready_ms, layout_ms, rows_ms):", trace, file=sys.stderr, flush=True)
     finally:
         cs.synchronize()  # no copy still landing in the shared pinned buffers (an error mid-way)
     size = ctypes.c_int64()
     nat.check(L.xhe_wire_finish(count, _vp(off), int(framed), optr, maxlen.value, ctypes.byref(size)), "wire finish")
     return size.value
+
+
+class _Source:
+    """The content bytes of a received payload: the bytes themselves, or the
+    content of a closed-form raw-block zstd frame (compat.raw_frame_size),
+    read range by range straight out of the frame."""
+
+    def __init__(self, data, content=None):
+        self.data = data
+        self.framed = content is not None
+        self.size = len(data) if content is None else int(content)
+
+    def read(self, lo, hi, dst):
+        """content bytes [lo, hi) -> the memory at address dst; False when the
+        frame is not what its probe saw"""
+        L = nat.lib()
+        if self.framed:
+            return L.xhe_zstd_raw_extract_range(self.data, len(self.data), lo, hi, ctypes.c_void_p(dst)) == nat.XHE_OK
+        src = ctypes.cast(self.data, ctypes.c_void_p).value + lo  # (the address only: data outlives the call)
+        return L.xhe_host_memcpy(ctypes.c_void_p(dst), ctypes.c_void_p(src), hi - lo) == nat.XHE_OK
+
+
+def peek_shape(src, n2w):
+    """the shape in the header of a payload in the library's own layout
+    (xhe_wire_scan of its first bytes), or None for any other payload"""
+    n = min(src.size, 512)  # the header with eight 8-byte dimensions is below 200 bytes
+    if n < 2:
+        return None
+    head = np.empty(n, dtype=np.uint8)
+    if not src.read(0, n, head.ctypes.data):
+        return None
+    found, nxt, ndim = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+    shape = np.zeros(8, dtype=np.int64)
+    rc = nat.lib().xhe_wire_scan(_vp(head), n, 0, int(n == src.size), n2w, None, None, None, 0, ctypes.byref(found),
+                                 ctypes.byref(nxt), _vp(shape), ctypes.byref(ndim))
+    if rc not in (nat.XHE_OK, nat.XHE_EOVERFLOW):
+        return None
+    return tuple(int(s) for s in shape[:ndim.value])
+
+
+def decode_device(src, n2w, dev, shape):
+    """decode_words of a payload in the library's own layout, into HBM: ->
+    (int32 tensor [count, n2w] on `dev`, int32 exponents, shape), or None when
+    the bytes are not that layout after all (a foreign, truncated or corrupt
+    payload: the caller decodes on the host, which accepts or rejects it).
+    `src` is a _Source, `shape` its peek_shape. The mirror image of
+    encode_device, chunk by chunk: host threads copy (or de-frame) the chunk's
+    bytes into a pinned buffer; the host scans it for whole elements
+    (xhe_wire_scan: value offsets, lengths, exponents - no words are copied);
+    bytes and index go up in one copy on the copy stream; xhe_wire_unpack, on
+    the drop-in stream behind that copy's event, writes those elements' rows
+    of the result. The next chunk starts at the first incomplete element. The
+    [count, n2w] words never exist on the host. Returns when the host work is
+    done: the last launch may still be queued, as with every resident result."""
+    count = 1
+    for s in shape:
+        count *= s
+    # an element is 16 bytes at least: a header that promises more is not worth a tensor
+    if count < 1 or min(shape) < 0 or count * 16 > src.size or n2w % 4 or n2w > _MAX_WORDS:
+        return None
+    with _stage_lock:
+        return _recv_pipeline(src, n2w, dev, shape, count)
+
+
+def _recv_pipeline(src, n2w, dev, shape, count):
+    """decode_device's chunk loop (under _stage_lock). A pinned buffer and its
+    device twin hold [offsets: 4 cap][lengths: 2 cap][chunk bytes]."""
+    import torch
+
+    from . import resident
+    L = nat.lib()
+    st = _stage_pair(dev, n2w, max(min(PIPE_CHUNK, count), _STAGE_MIN_ROWS))
+    pins = [s[0].view(torch.uint8).reshape(-1) for s in st]
+    hosts = [p.numpy() for p in pins]
+    cap = min(int(st[0][0].shape[0]), count)        # elements one chunk may hold
+    o_len = 4 * cap
+    o_bytes = (6 * cap + 15) & ~15
+    chunk = min(DEV_CHUNK, int(pins[0].shape[0]) - o_bytes, src.size + 15) & ~15
+    exps = np.empty(count, dtype=np.int32)
+    cs = _copy_stream(dev)
+    main = resident.stream(dev)
+    with resident._On(dev):
+        d = torch.empty((count, n2w), dtype=torch.int32, device=f"cuda:{dev}")
+        twins = [torch.empty(o_bytes + chunk, dtype=torch.uint8, device=f"cuda:{dev}") for _ in range(2)]
+        # the twins' blocks may come from tensors freed with kernels still queued
+        # on the drop-in stream: the copy stream starts behind those
+        ready = torch.cuda.Event()
+        ready.record(main)
+        cs.wait_event(ready)
+    copied, unpacked = [None, None], [None, None]
+    found, nxt, ndim = ctypes.c_int64(), ctypes.c_int64(), ctypes.c_int()
+    shp = np.zeros(8, dtype=np.int64)
+    trace = _TRACE and []
+    pos = e0 = k = 0
+    ok = False
+    try:
+        while True:
+            b = k % 2
+            t0 = time.perf_counter()
+            if copied[b] is not None:
+                copied[b].synchronize()  # chunk k - 2 has left the pinned buffer
+            t1 = time.perf_counter()
+            n = min(chunk, src.size - pos)
+            last = pos + n == src.size
+            base = hosts[b].ctypes.data
+            if not src.read(pos, pos + n, base + o_bytes):
+                break
+            t2 = time.perf_counter()
+            want = min(cap, count - e0)
+            rc = L.xhe_wire_scan(ctypes.c_void_p(base + o_bytes), n, e0, int(last), n2w, ctypes.c_void_p(base),
+                                 ctypes.c_void_p(base + o_len), ctypes.c_void_p(exps.ctypes.data + 4 * e0), want,
+                                 ctypes.byref(found), ctypes.byref(nxt), _vp(shp), ctypes.byref(ndim))
+            # a deviation, more elements than the header's shape (or the index)
+            # holds, or an element that no chunk holds whole
+            if rc != nat.XHE_OK or (not last and nxt.value == 0):
+                break
+            t3 = time.perf_counter()
+            m = found.value
+            if m:
+                with torch.cuda.device(dev):
+                    with torch.cuda.stream(cs):
+                        if unpacked[b] is not None:
+                            cs.wait_event(unpacked[b])  # chunk k - 2's kernel has read the twin
+                        twins[b][:o_bytes + n].copy_(pins[b][:o_bytes + n], non_blocking=True)
+                        copied[b] = torch.cuda.Event()
+                        copied[b].record(cs)
+                    main.wait_event(copied[b])
+                    tw = twins[b].data_ptr()
+                    nat.check(L.xhe_wire_unpack(ctypes.c_void_p(tw + o_bytes), n, ctypes.c_void_p(tw),
+                                                ctypes.c_void_p(tw + o_len), m, n2w,
+                                                ctypes.c_void_p(d.data_ptr() + 4 * n2w * e0),
+                                                ctypes.c_void_p(main.cuda_stream)), "wire unpack")
+                    unpacked[b] = torch.cuda.Event()
+                    unpacked[b].record(main)
+            if trace is not False:
+                t4 = time.perf_counter()
+                trace.append((k, m, *(round((y - x) * 1e3, 2) for x, y in ((t0, t1), (t1, t2), (t2, t3), (t3, t4)))))
+            e0 += m
+            pos += nxt.value
+            if last:
+                ok = e0 == count
+                break
+            k += 1
+        if trace:
+            print("recv pipeline (chunk, elements, ready_ms, stage_ms, scan_ms, issue_ms):", trace, file=sys.stderr,
+                  flush=True)
+    finally:
+        cs.synchronize()  # no copy still reads the shared pinned buffers
+    if not ok:
+        return None  # (the partial tensor goes back to the allocator on its own stream)
+    return d, exps, tuple(shape)
 
 
 def decode(data, n2w=None):
