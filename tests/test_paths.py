@@ -333,19 +333,30 @@ ROWS["decrypt"] = [
 ]
 
 
-@pytest.fixture(scope="module")
-def answers(tmp_path_factory):
-    """{input line: printed answer} of one run of the check program over every row"""
-    exe = str(tmp_path_factory.mktemp("paths") / "paths_check")
+def build_paths_check(folder):
+    """tests/native/paths_check.cpp compiled into `folder` -> the program's path
+    (also used by tests/test_pinned_paths_host.py)"""
+    exe = os.path.join(str(folder), "paths_check")
     subprocess.run(["g++", "-O1", "-std=c++17", "-Wall", "-Wextra", "-Werror",
                     os.path.join(HERE, "native", "paths_check.cpp"), "-o", exe], check=True)
-    lines = [line for rows in ROWS.values() for line, _ in rows]
+    return exe
+
+
+def ask_paths_check(exe, lines):
+    """{input line: printed answer} of one run of the check program over `lines`"""
     assert len(set(lines)) == len(lines), "a row is listed twice"
     r = subprocess.run([exe], input="\n".join(lines) + "\n", capture_output=True, text=True, timeout=60)
     assert r.returncode == 0, r.stderr
     out = r.stdout.splitlines()
     assert len(out) == len(lines), r.stdout
     return dict(zip(lines, out))
+
+
+@pytest.fixture(scope="module")
+def answers(tmp_path_factory):
+    """{input line: printed answer} of one run of the check program over every row"""
+    exe = build_paths_check(tmp_path_factory.mktemp("paths"))
+    return ask_paths_check(exe, [line for rows in ROWS.values() for line, _ in rows])
 
 
 @pytest.mark.parametrize("op", sorted(ROWS))
