@@ -5,7 +5,12 @@ Device-resident operands, wall time of the call + synchronize, median of 5.
 Prints one JSON line.
 
     XHE_DEC_TPI=16 python tools/dec_shapes.py [sizes...]
-    XHE_ENC_TPI=0 python tools/dec_shapes.py --enc [sizes...]
+    XHE_ENC_TPI=0 python tools/dec_shapes.py --enc [--short] [sizes...]
+
+--enc encrypts plaintexts with random 30-bit words in every word: general
+plaintexts for k_djn_pmd. --short makes them what the float encodings produce,
++-s with s below 2^27 (a negative one stored as n - s), signs alternating: every
+wave takes the kernel's short-plaintext entry.
 
 --pub: xhe_encrypt on a PUBLIC non-DJN 2048-bit key (the obfuscator r^n of a
 party that received the key, Paillier.encrypt(public_context, ...) of the
@@ -35,7 +40,7 @@ import time
 import numpy as np
 
 HERE_ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-FLAGS = ("--enc", "--pub", "--matmul")
+FLAGS = ("--enc", "--pub", "--matmul", "--short")
 OPTS = ("--ab", "--out", "--root", "--reps", "--rounds")
 
 
@@ -120,7 +125,7 @@ def sweep_matmul(sizes, reps):
     return out
 
 
-def sweep_dec_enc(enc, sizes):
+def sweep_dec_enc(enc, sizes, short=False):
     import torch
 
     from bench import make_key
@@ -139,8 +144,15 @@ def sweep_dec_enc(enc, sizes):
     out = {"op": "encrypt" if enc else "decrypt",
            "tpi": os.environ.get("XHE_ENC_TPI" if enc else "XHE_DEC_TPI", "auto")}
     if enc:
-        m.random_(0, 1 << 30)
-        m[:, -1] = 0
+        if short:
+            srng = np.random.default_rng(2)
+            mags = srng.integers(1, 1 << 27, N)
+            vals = [int(v) if i & 1 == 0 else n - int(v) for i, v in enumerate(mags)]
+            m = torch.from_numpy(nat.ints_to_words(vals, dk.nw).view(np.int32)).cuda()
+            out["plaintexts"] = "short"
+        else:
+            m.random_(0, 1 << 30)
+            m[:, -1] = 0
         r = torch.randint(0, 1 << 30, (N, dk.rand_words), dtype=torch.int32, device="cuda")
     for k in sizes:
         ts = []
@@ -212,7 +224,7 @@ def main():
     elif "--matmul" in flags:
         out = sweep_matmul(sizes, min(reps, 5))
     else:
-        out = sweep_dec_enc("--enc" in flags, sizes)
+        out = sweep_dec_enc("--enc" in flags, sizes, "--short" in flags)
     print(json.dumps(out))
 
 

@@ -662,20 +662,147 @@ class LogDigits(MontDigits):
         assert t < 2 * P2 and (t * self.R * self.R - v) % P2 == 0
         return t - P2 if t >= P2 else t
 
+    # -- the ends of k_djn_pmd (pdigit_dev.hpp "Short plaintexts", "The exit
+    # through the digits"): the short-plaintext entry of the log sum and the
+    # exit that folds the sum in on the way to the canonical residue.
+    SHORT_L = 4  # limbs of a short plaintext's magnitude: s < 2^(28 * 4)
 
-def red_rows(lo, hi, Nl, n0inv, ctr):
+    def ms_const(self, Q):
+        """Q R^2 2^(28 L) mod P (KeyDev::ms_p / ms_q)"""
+        return Q % self.P * pow(self.R, 2, self.P) % self.P * (1 << (W * self.SHORT_L)) % self.P
+
+    def classify_short(self, m, n, nw=64):
+        """pmd_short_classify on the nw words of m: (s, negative) for a short
+        plaintext - m = s < 2^(28 L), or 0 < n - m = s < 2^(28 L) - and None for
+        a general one. Word by word as the kernel decides it: the words of m
+        above the low four all zero, or the nw-word difference n - m (a borrow
+        chain over every word) without a borrow out and zero above the low
+        four; s is the low four words and must stay below 2^(28 L)."""
+        assert 0 <= m < 1 << (32 * nw) and 0 < n < 1 << (32 * nw)
+        Bs = 1 << (W * self.SHORT_L)
+        lw = -(-W * self.SHORT_L // 32)  # the low words: 4
+        lo_mask = (1 << (32 * lw)) - 1
+        if m >> (32 * lw) == 0 and m & lo_mask < Bs:
+            return m, False
+        d, br = [], 0
+        for k in range(nw):
+            x = ((n >> (32 * k)) & 0xFFFFFFFF) - ((m >> (32 * k)) & 0xFFFFFFFF) - br
+            d.append(x & 0xFFFFFFFF)
+            br = 1 if x < 0 else 0
+        s = sum(w << (32 * k) for k, w in enumerate(d[:lw]))
+        if br == 0 and not any(d[lw:]) and 0 < s < Bs:
+            return s, True
+        return None
+
+    def short_log(self, s, neg, ms, ctr):
+        """pmd_lam_short: T = s ms on K + L lazy columns, L Montgomery steps by P
+        (they divide by 2^(28 L)), v = s Q R^2 mod P < 2P; muhat = v or 2P - v.
+        Returns (muhat words, v)."""
+        k, L = self.k, self.SHORT_L
+        assert 0 <= s < 1 << (W * L) and 0 <= ms < self.P
+        sl, ml = limbs(s, L), limbs(ms, k)
+        T = [0] * (k + L)
+        for i in range(L):
+            for j in range(k):
+                T[i + j] += sl[i] * ml[j]
+            ctr.mads += k
+        ctr.max_col = max(ctr.max_col, max(T))
+        for i in range(L):
+            q = (T[i] * self.n0inv) & MASK
+            for j in range(k):
+                T[i + j] += q * self.Pl[j]
+            ctr.mads += k
+            assert T[i] & MASK == 0
+            T[i + 1] += T[i] >> W
+            ctr.max_col = max(ctr.max_col, max(T))
+        v = _norm_value(T[L:])
+        assert v < 2 * self.P and (v << (W * L)) % self.P == s * ms % self.P
+        muhat = 2 * self.P - v if neg else v
+        assert 0 <= muhat <= 2 * self.P
+        return self.words(muhat), v
+
+    def exit_fused(self, state, ctr, ranges=None):
+        """pmd_exit: the canonical residue (R a + P c)(1 + P L) R^-2 mod P^2 from
+        the state after the last product, 5 k^2 + k mads:
+            u = REDC(a), quotient digits m1 kept          (u <= P)
+            t = REDC(c + u Lhat)                          (t < 2P + 4)
+            w = t + (R - 1 - m1) + E                      (w < 2R, top limb loose)
+            z = REDC(w), reduced below P                  (z < P + 3 before)
+            u = P: u <- 0, z <- (z + 1) mod P
+            x = u + P z
+        ranges: a dict that receives the largest u/P, t - 2P, w/R, z - P seen, and
+        the reduced z of a state whose u reached P."""
+        k, P, R = self.k, self.P, self.R
+        a, c, s = state
+        Lh = sum(w << (32 * i) for i, w in enumerate(s))
+        assert Lh < R, "log sum outgrew K limbs"
+        m1 = []
+        u = _norm_value(normalize(red_rows(limbs_loose(a, k), [0] * k, self.Pl, self.n0inv, ctr, digits=m1), k))
+        assert u <= P and u * R == a + value(m1) * P
+        # operand scanning over the limbs of Lhat on the columns of c
+        ul, ll = limbs(u, k), limbs(Lh, k)
+        T = limbs_loose(c, k)
+        for i in range(k):
+            x0 = T[0] + ll[i] * ul[0]
+            m = (x0 * self.n0inv) & MASK
+            x0 += m * self.Pl[0]
+            assert x0 & MASK == 0
+            for j in range(1, k):
+                T[j - 1] = T[j] + ll[i] * ul[j] + m * self.Pl[j]
+            T[k - 1] = 0
+            T[0] += x0 >> W
+            ctr.mads += 2 * k + 1
+            ctr.max_col = max(ctr.max_col, x0, max(T))
+        t = _norm_value(T)
+        assert t < 2 * P + 4 and (t * R - c - u * Lh) % P == 0
+        # w = t + (MASK - m1_i + E_i) limb by limb, the top limb keeps the carry
+        tl, wl, cy = limbs(t, k), [], 0
+        for i in range(k):
+            x = tl[i] + (MASK - m1[i]) + self.El[i] + cy
+            wl.append(x & MASK if i + 1 < k else x)
+            cy = x >> W
+        w = _norm_value(wl)
+        assert w < 2 * R and wl[-1] < 1 << 32
+        z = _norm_value(normalize(red_rows(wl, [0] * k, self.Pl, self.n0inv, ctr), k))
+        assert z < P + 3 and (z * R - w) % P == 0
+        if ranges is not None:
+            for key, val in (("u_over_P", u / P), ("t_minus_2P", t - 2 * P), ("w_over_R", w / R), ("z_minus_P", z - P)):
+                ranges[key] = max(ranges.get(key, float("-inf")), val)
+            if u >= P:
+                ranges["z_at_u_fix"] = z % P  # what the u = P correction increments
+        if z >= P:
+            z -= P
+        if u >= P:
+            u -= P
+            z = z + 1 - P if z + 1 >= P else z + 1
+        # x = u + P z: k^2 mads on 2k lazy columns
+        zl, T = limbs(z, k), limbs(u, k) + [0] * k
+        for i in range(k):
+            for j in range(k):
+                T[i + j] += zl[j] * self.Pl[i]
+            ctr.mads += k
+        ctr.max_col = max(ctr.max_col, max(T))
+        x = _norm_value(normalize(T, 2 * k))
+        assert x == u + P * z and x < P * P
+        return x
+
+
+def red_rows(lo, hi, Nl, n0inv, ctr, digits=None):
     """Mont::red_rows: L rows T <- (T + m N) / 2^W on the lazy columns T = lo
     (L values, limbs or an unmasked top limb), limb i of `hi` written to the top
     column at the end of row i (step1_red: T[L-1] = hi_i after the row's blocks
     consumed the old top). Returns the L columns of (lo + hi 2^(W L) + q N) /
     2^(W L); every column is recorded in ctr.max_col (the kernel holds them in
-    64 bits and adds products below 2^(2W): they must stay below 2^63)."""
+    64 bits and adds products below 2^(2W): they must stay below 2^63).
+    digits: a list that receives the L quotient digits (red_rows_q)."""
     L = len(lo)
     assert len(hi) == L and len(Nl) == L
     T = list(lo)
     x0 = T[0]
     m = (x0 * n0inv) & MASK
     for i in range(L):
+        if digits is not None:
+            digits.append(m)
         x0 += m * Nl[0]
         assert x0 & MASK == 0
         for j in range(1, L):

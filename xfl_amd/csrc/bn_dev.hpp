@@ -629,6 +629,44 @@ struct Mont {
 #pragma unroll
     for (int r = 0; r < (S & 3); ++r) step1_red(Np, R, T, comp4(cur, r), m, x0);
   }
+  // red_rows with a zero high half that also hands out the quotient digits q
+  // (T + q N = 2^(W S) T'), four rows at a time: qs.put4(i, digits i .. i + 3),
+  // the digits past S - 1 of the last call zero.
+  template <class QS>
+  XHE_DEV void red_rows_q(uint64_t (&T)[L], const QS& qs) const {
+    const uint32_t* Np = np();
+    NRes R;
+    load_res(Np, R);
+    uint64_t x0 = T[0];
+    uint32_t m = ((uint32_t)x0 * n0inv) & MASK;
+    int i = 0;
+    for (; i + 4 <= S; i += 4) {
+      uint4 d;
+      __builtin_amdgcn_sched_barrier(0);
+      d.x = m;
+      step1_red(Np, R, T, 0u, m, x0);
+      __builtin_amdgcn_sched_barrier(0);
+      d.y = m;
+      step1_red(Np, R, T, 0u, m, x0);
+      __builtin_amdgcn_sched_barrier(0);
+      d.z = m;
+      step1_red(Np, R, T, 0u, m, x0);
+      __builtin_amdgcn_sched_barrier(0);
+      d.w = m;
+      step1_red(Np, R, T, 0u, m, x0);
+      __builtin_amdgcn_sched_barrier(0);
+      qs.put4(i, d);
+    }
+    if constexpr ((S & 3) != 0) {
+      uint32_t d[4] = {0u, 0u, 0u, 0u};
+#pragma unroll
+      for (int r = 0; r < (S & 3); ++r) {
+        d[r] = m;
+        step1_red(Np, R, T, 0u, m, x0);
+      }
+      qs.put4(i, make_uint4(d[0], d[1], d[2], d[3]));
+    }
+  }
 
   // One column of the product: T <- (T + a_i*b + m*N) / 2^W, software-
   // pipelined: on entry x0 = a_i*b[0] + T[0] and m (its Montgomery digit) are

@@ -353,6 +353,7 @@ constexpr RowF nprime[2] = {&KeyDev::p2_nprime, &KeyDev::q2_nprime}, rns[2] = {&
                nR2C[2] = {&KeyDev::nR2C_p2X, &KeyDev::nR2C_q2X}, m1_words[2] = {&KeyDev::pm1_words, &KeyDev::qm1_words},
                inv_lim[2] = {&KeyDev::pinv_lim, &KeyDev::qinv_lim}, hR[2] = {&KeyDev::hpR, &KeyDev::hqR},
                topc[2] = {&KeyDev::topc_p, &KeyDev::topc_q}, mu[2] = {&KeyDev::mu_p, &KeyDev::mu_q},
+               ms[2] = {&KeyDev::ms_p, &KeyDev::ms_q},
                e_words[2] = {&KeyDev::ep_words, &KeyDev::eq_words},
                x_kn2[2] = {&KeyDev::x_kn2_p, &KeyDev::x_kn2_q}, x_rmn[2] = {&KeyDev::x_rmn_p, &KeyDev::x_rmn_q},
                x_topc[2] = {&KeyDev::x_topc_p, &KeyDev::x_topc_q}, x_fold[2] = {&KeyDev::x_fold_p, &KeyDev::x_fold_q},
@@ -506,8 +507,8 @@ inline void prime2_constants(KeyImage& im, const KeySpec& s, const Prime (&pr)[2
 
 // mod p / q (decrypt): the moduli, the exponents P - 1, P^-1 mod R, hp R,
 // the CRT's q^-1 R (context.py:43), and the one-lane digit kernels' MASK + E_i
-// (2048; k_djn_pmd, k_dec_pmd) and k_djn_pmd's plaintext factor (2048-bit DJN
-// keys). Leaves hp, hq in pr[].h.
+// (2048; k_djn_pmd, k_dec_pmd) and k_djn_pmd's plaintext factors mu and ms
+// (2048-bit DJN keys). Leaves hp, hq in pr[].h.
 inline void decrypt_constants(KeyImage& im, const KeySpec& s, const BigU& n, Prime (&pr)[2]) {
   const ModSpec& s1 = s.mp;
   const BigU T = s1.R();
@@ -540,6 +541,13 @@ inline void decrypt_constants(KeyImage& im, const KeySpec& s, const BigU& n, Pri
     for (int i = 0; i < 2; ++i) {
       const BigU &X = pr[i].X, RX = mod(s.pmd.R(), X), R2 = mulmod(RX, RX, X);
       im.put_limbs(mulmod(mod(pr[i].Y, X), mulmod(R2, R2, X), X), s.pmd, pq::mu[i]);
+    }
+  // and its short-plaintext factor Q R^2 B mod P, B = 2^(28 * 4): s ms / B (four
+  // Montgomery steps by P) is s Q R^2 mod P, the log digit of 1 + n s
+  if (s.K == 2048 && s.djn)
+    for (int i = 0; i < 2; ++i) {
+      const BigU &X = pr[i].X, RX = mod(s.pmd.R(), X), R2 = mulmod(RX, RX, X);
+      im.put_limbs(mulmod(mulmod(mod(pr[i].Y, X), R2, X), mod(pow2((size_t)s.pmd.W * 4), X), X), s.pmd, pq::ms[i]);
     }
 }
 

@@ -81,10 +81,14 @@ struct KeyDev {
   // and MASK + ((1 - R) mod P) limbs per prime; mu_p = Q R^4 mod P and mu_q =
   // P R^4 mod Q (R = 2^(28*37), Mont<37, 28, 1> limbs; DJN keys): the factor
   // that turns a plaintext m into its log digit Q m R^2 mod P (1 + n m =
-  // 1 + P (Q m); pdigit_dev.hpp "The plaintext as a logarithm")
+  // 1 + P (Q m); pdigit_dev.hpp "The plaintext as a logarithm"); ms_p = Q R^2
+  // B mod P and ms_q = P R^2 B mod Q, B = 2^(28*4) (the same limbs; DJN keys):
+  // the factor of a short plaintext +-s, s < B, whose log digit is +-s ms / B
+  // by four Montgomery steps (pdigit_dev.hpp "Short plaintexts")
   int pmd;
   const uint32_t *topc_p, *topc_q;
   const uint32_t *mu_p, *mu_q;
+  const uint32_t *ms_p, *ms_q;
   // ---- Montgomery digits mod n^2 (PMDX, 2048-bit keys, public or private):
   // n as 80 limbs of 27 bits (R = 2^2160), ceil(R/n) n^2 (160 limbs), R - n,
   // the digits of R^2 mod n^2 and of 1 (80 pairs each), MASK + E_i

@@ -43,17 +43,15 @@
 //
 // - the product above with f = 0 (`mul_row`: 4 K^2 = 5,476 mads, the f a
 // mads gone) and one multi-word addition. Two states multiply by the general
-// product on (a, c) and the sum of their L. After the last product
-// x R^2 = R a + P (c + R a L): c_f = c + REDC(a Lhat) with the rows storing
-// lhat = l R^2 mod P = f y^-1 mod P (canonical, below P; k_tab_to_pmd), and
-// (a, c_f) is the pair form again (`finish`, then to_mont2).
+// product on (a, c) and the sum of their L. The rows store lhat = l R^2 mod P =
+// f y^-1 mod P (canonical, below P; k_tab_to_pmd) and the sum is held in that
+// scaling, Lhat = L R^2 mod P; the exit (below) folds it in.
 // Lhat is a plain sum, never reduced: nwin canonical log digits and the
-// plaintext's muhat < 2P (below), so below (nwin + 2) P, and nwin <= 1024 (a
-// window of one bit) with R/P >= 2^12 keeps it below R = 2^1036: LW = 33
-// words, K limbs, and a Lhat < P (1 + 2P/R) R keeps REDC(a Lhat) below a + P <
-// 2.001 P.
-// Ranges: a', c' as above (c' < R + 4P), c_f < R + 7P, inside what to_mont2
-// takes. Columns of the row product: 2K products plus carries.
+// plaintext's muhat <= 2P (below), so Lhat < (nwin + 2) P + 1, and nwin <= 1024
+// (a window of one bit) with R/P >= 2^12 keeps it below R = 2^1036: LW = 33
+// words, K limbs.
+// Ranges: a', c' as above (a' < P (1 + 2P/R), c' < R + 4P). Columns of the row
+// product: 2K products plus carries.
 //
 // The plaintext as a logarithm (k_djn_pmd). With n = P Q, 1 + n m = 1 + P (Q
 // m) (mod P^2) is itself of the form 1 + P l: multiplying the obfuscator h^a by
@@ -61,14 +59,52 @@
 //
 //     (1 + P L)(1 + P Q m) = 1 + P (L + Q m)   (mod P^2).
 //
-// In the sum's scaling that is muhat = Q m R^2 mod P: t = REDC(m) = m R^-1 mod
-// P (pmd_redc_words on the 2K limbs of m; any m below 2^2048 is below R P), and
-// muhat = MontMul(t, Q R^4 mod P) < 2P (pmd_lam_plain; K^2 + 2 K^2 + K mads).
-// It is the start value of the sum; `finish` then returns the pair of (1 + n
-// m) h^a at no further cost, and after to_mont2 one REDC on the 2K limbs of
-// P^2 (zero high half, (2K)^2 mads) and a reduce_once give the canonical
-// residue - in place of two 2K-limb Montgomery products (4 (2K)^2 mads).
-// (Model: tools/pdigit_model.py LogDigits.)
+// In the sum's scaling that is muhat = Q m R^2 mod P, the start value of the
+// sum. General entry: t = REDC(m) = m R^-1 mod P (pmd_redc_words on the 2K
+// limbs of m; any m below 2^2048 is below R P), and muhat = MontMul(t, Q R^4
+// mod P) < 2P (pmd_lam_plain; K^2 + 2 K^2 + K mads).
+//
+// Short plaintexts. What the encodings write for a float is +-s with a small
+// s, the negative one stored as n - s. Let B = 2^(W L), L = 4 limbs (112 bits;
+// every three-word magnitude). m is short when m = s < B, or 0 < n - m = s < B;
+// since n = P Q = 0 (mod P), Q (n - s) = -Q s (mod P), so muhat = +-s (Q R^2
+// mod P). With the key constant ms = Q R^2 B mod P (canonical, K limbs) the
+// product T = s ms has K + L limbs, and L Montgomery steps by P - they divide
+// by B, not by R - leave v = (T + q P) / B = s Q R^2 (mod P) with T < B P and q <
+// B, so v < 2P. muhat = v for the positive sign; for the negative one s > 0, v
+// is no multiple of P (s < B < P, Q and R units), 0 < v < 2P, and muhat = 2P - v
+// lies in (0, 2P): 0 <= muhat <= 2P in all, 2 L K = 296 mads (pmd_lam_short)
+// against 4,144. Every other value - m = B, m = n - B, m >= n, multiples of P or
+// Q among them - is general. The test reads all 2K W / 32 words of m
+// (pmd_short_classify): the words above the low four zero, or the whole
+// borrow chain n - m ending without a borrow and zero above the low four; a
+// wave takes the short entry only when every lane that runs the prologue holds
+// a short plaintext, so no wave runs both entries.
+//
+// The exit through the digits (pmd_exit). After the last product (and the tree
+// of a lane group) x R^2 = (R a + P c)(1 + P L), Lhat = L R^2 mod P < R, a < P
+// (1 + 2P/R), c < R + 4P, and the canonical x mod P^2 = x0 + P x1 is wanted. With
+// REDC(T) = (T + m P) / R:
+//     u = REDC(a), quotient digits m1 kept: a = R u - m1 P exactly, u = a R^-1 =
+//         x (mod P), and u < (a + R P) / R < P + 1, so u <= P.
+//     (R a + P c)(1 + P L) = R a + P (c + R a L) = R^2 u + P (c - R m1 + R a L)
+//         (mod P^2), and R a L = R^2 u L = u Lhat (mod P): x1 = R^-2 (c + u Lhat)
+//         - R^-1 m1 (mod P).
+//     t = REDC(c + u Lhat): Lhat streamed as the product's operand (K^2 mads)
+//         with c as the accumulators' start value, K^2 for the reduction; c + u
+//         Lhat < R + 4P + P R, so t < 2P + 1 + 4P/R < 2P + 4.
+//     w = t + (R - 1 - m1) + E, E = (1 - R) mod P: w = t - m1 (mod P), the same
+//         MASK - m1_i + E_i entry (topc) as in a row product; w < 2R, the top
+//         limb keeps the carry.
+//     z = REDC(w) = x1 (mod P), z < (2R + R P) / R = P + 2; z - P if z >= P.
+//     u = P (x0 = 0): u <- 0 and z <- (z + 1) mod P, the residue's P moved up.
+//     x = u + P z (K^2 mads), canonical, below P^2: 2K normalised limbs.
+// 5 K^2 + K = 6,882 mads against 2 K^2 + K (the sum folded into c), K^2 (back
+// to the 2K-limb Montgomery form) and (2K)^2 (its REDC) = 9,620 before, and
+// only P is needed: the three reductions are block-form rows of Mont<K, 28, 1>
+// (bn_dev.hpp red_rows, red_rows_q), no modulus P^2. Every column is below
+// 2^63: the product's are 2K products of 2^56 on a start value below 2^29.
+// (Model: tools/pdigit_model.py LogDigits; tests/test_pdigit_ends_model.py.)
 #pragma once
 #include "bn_dev.hpp"
 
@@ -525,41 +561,25 @@ struct PMD {
     lam_add<4 * LQ>(slot, o);
   }
 
-  // The finish: c <- c + REDC(a Lhat), Lhat the log sum (< R: K limbs). Its
-  // limbs go into the e quads of the slot and stream through one Montgomery
-  // product mod P (2 K^2 + K mads); a stays, so (a, c) is what to_mont2 takes.
-  XHE_DEV void finish(const uint32_t (&a)[K], uint32_t (&c)[K], uint32_t* slot, const uint32_t* Pl) const {
+  // The log sum (< R: K limbs) unpacked into the e quads of the slot, limb i at
+  // slot[(i / 4) * 256 + i % 4], zero beyond K: the streamed operand of the
+  // exit's product u Lhat (pmd_exit).
+  XHE_DEV static void lam_to_limbs(uint32_t* slot) {
     constexpr int LQ = (LW + 3) / 4;
-    {
-      uint32_t s[4 * LQ + 1];
+    uint32_t s[4 * LQ + 1];
 #pragma unroll
-      for (int q = 0; q < LQ; ++q) {
-        const uint4 v = *reinterpret_cast<const uint4*>(slot + (EQ + q) * 256);
-        s[4 * q] = v.x, s[4 * q + 1] = v.y, s[4 * q + 2] = v.z, s[4 * q + 3] = v.w;
-      }
-      s[4 * LQ] = 0u;
-      auto limb = [&](int i) -> uint32_t {
-        const int bit = W * i, k = bit >> 5, sh = bit & 31;
-        return i < K ? (__builtin_amdgcn_alignbit(k + 1 < LW ? s[k + 1] : 0u, s[k], sh) & MASK) : 0u;
-      };
-#pragma unroll
-      for (int q = 0; q < EQ; ++q)
-        *reinterpret_cast<uint4*>(slot + q * 256) = make_uint4(limb(4 * q), limb(4 * q + 1), limb(4 * q + 2), limb(4 * q + 3));
+    for (int q = 0; q < LQ; ++q) {
+      const uint4 v = *reinterpret_cast<const uint4*>(slot + (EQ + q) * 256);
+      s[4 * q] = v.x, s[4 * q + 1] = v.y, s[4 * q + 2] = v.z, s[4 * q + 3] = v.w;
     }
-    __builtin_amdgcn_sched_barrier(0);
-    uint32_t t[K];
+    s[4 * LQ] = 0u;
+    auto limb = [&](int i) -> uint32_t {
+      const int bit = W * i, k = bit >> 5, sh = bit & 31;
+      return i < K ? (__builtin_amdgcn_alignbit(k + 1 < LW ? s[k + 1] : 0u, s[k], sh) & MASK) : 0u;
+    };
 #pragma unroll
-    for (int j = 0; j < K; ++j) t[j] = a[j];
-    Mont<K, W, 1> MN;
-    MN.init(Pl, n0inv);
-    MN.mul(t, PmdLdsQ{slot});  // REDC(a Lhat) < a + P
-    uint32_t cy = 0;
-#pragma unroll
-    for (int j = 0; j < K; ++j) {
-      const uint32_t x = c[j] + t[j] + cy;
-      c[j] = j + 1 < K ? (x & MASK) : x;
-      cy = j + 1 < K ? (x >> W) : 0u;
-    }
+    for (int q = 0; q < EQ; ++q)
+      *reinterpret_cast<uint4*>(slot + q * 256) = make_uint4(limb(4 * q), limb(4 * q + 1), limb(4 * q + 2), limb(4 * q + 3));
   }
 
   // carry-normalise into W-bit limbs; the top limb keeps the final carry
@@ -652,25 +672,12 @@ XHE_DEV void pmd_redc_words(const Mont<K, 28, 1>& MN, uint32_t* slot, const uint
   MN.redc_wide(t, PmdLdsQ{slot});
 }
 
-// The plaintext as a logarithm (header: "The plaintext as a logarithm"): the
-// start value of a lane's log sum, muhat = Q m R^2 mod P (< 2P), in the LW
-// words of the slot's sum quads. m: nw little-endian words, any value (below
-// 2^(32 nw) <= 2^(28 * 2K) and below R P: 2K limbs, one REDC by P
-// (pmd_redc_words) - t = m R^-1 mod P < 2P); mu: Q R^4 mod P as K limbs (a
-// uniform row), multiplied in by one Montgomery product mod P. Runs before the
-// lane's state exists (the registers of a, c, T1, T2 are free, and so are the e
-// quads of the slot): K^2 + 2 K^2 + K mads.
+// K normalised limbs (a value below 2^(32 LW)) packed into the LW words of the
+// slot's sum quads: the start value of a lane's log sum
 template <int K>
-XHE_DEV void pmd_lam_plain(const PMD<K>& M, uint32_t* slot, const uint32_t* __restrict__ mw, int nw,
-                           const uint32_t* mu, const uint32_t* Pl) {
+XHE_DEV void pmd_lam_store(uint32_t* slot, const uint32_t (&t)[K]) {
   using D = PMD<K>;
   constexpr int LQ = (D::LW + 3) / 4;
-  Mont<K, 28, 1> MN;
-  MN.init(Pl, M.n0inv);
-  uint32_t t[K];
-  pmd_redc_words<K>(MN, slot, mw, nw, t);
-  __builtin_amdgcn_sched_barrier(0);
-  MN.mul(t, ARow{mu});  // Q m R^2 mod P, < 2P: normalised limbs
   uint32_t s[4 * LQ];
 #pragma unroll
   for (int k = 0; k < 4 * LQ; ++k) {
@@ -683,6 +690,110 @@ XHE_DEV void pmd_lam_plain(const PMD<K>& M, uint32_t* slot, const uint32_t* __re
 #pragma unroll
   for (int q = 0; q < LQ; ++q)
     *reinterpret_cast<uint4*>(slot + (D::EQ + q) * 256) = make_uint4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
+}
+
+// The plaintext as a logarithm (header: "The plaintext as a logarithm"): the
+// start value of a lane's log sum, muhat = Q m R^2 mod P (< 2P), in the LW
+// words of the slot's sum quads. m: nw little-endian words, any value (below
+// 2^(32 nw) <= 2^(28 * 2K) and below R P: 2K limbs, one REDC by P
+// (pmd_redc_words) - t = m R^-1 mod P < 2P); mu: Q R^4 mod P as K limbs (a
+// uniform row), multiplied in by one Montgomery product mod P. Runs before the
+// lane's state exists (the registers of a, c, T1, T2 are free, and so are the e
+// quads of the slot): K^2 + 2 K^2 + K mads. The general entry; short
+// plaintexts take pmd_lam_short.
+template <int K>
+XHE_DEV void pmd_lam_plain(const PMD<K>& M, uint32_t* slot, const uint32_t* __restrict__ mw, int nw,
+                           const uint32_t* mu, const uint32_t* Pl) {
+  Mont<K, 28, 1> MN;
+  MN.init(Pl, M.n0inv);
+  uint32_t t[K];
+  pmd_redc_words<K>(MN, slot, mw, nw, t);
+  __builtin_amdgcn_sched_barrier(0);
+  MN.mul(t, ARow{mu});  // Q m R^2 mod P, < 2P: normalised limbs
+  pmd_lam_store<K>(slot, t);
+}
+
+// ---- short plaintexts (header: "Short plaintexts")
+// Classifies the plaintext m (nw little-endian words, nw <= PMD_MW) against n
+// (nwords: n as nw words, a uniform row): true, with the magnitude s (four
+// words, below 2^(28 * 4)) and the sign, when m = s < B or 0 < n - m = s < B
+// with B = 2^(28 * 4); false for every other value (m = B, m = n - B, m >= n
+// among them). The words of m above the low four must all be zero, or the
+// nw-word difference n - m - a borrow chain over every word - must end without
+// a borrow and be zero above the low four.
+constexpr int kPmdShortLimbs = 4;
+template <int K>
+XHE_DEV bool pmd_short_classify(const uint32_t* __restrict__ mw, int nw, const uint32_t* __restrict__ nwords,
+                                uint32_t (&s)[4], bool& neg) {
+  constexpr int MW = (28 * 2 * K) / 32;  // whole words in 2K limbs: 64 at K = 37
+  static_assert(kPmdShortLimbs * 28 > 96 && kPmdShortLimbs * 28 <= 128, "the magnitude ends in the fourth word");
+  constexpr uint32_t TOP = 1u << (kPmdShortLimbs * 28 - 96);  // bound of the fourth word
+  uint32_t lo[4], d[4], hz = 0u, hd = 0u, br = 0u;
+#pragma unroll
+  for (int k = 0; k < MW; ++k) {
+    const uint32_t m = word_or0(mw, k, nw), n = word_or0(nwords, k, nw);
+    const uint64_t x = (uint64_t)n - (uint64_t)m - (uint64_t)br;
+    br = (uint32_t)(x >> 63);
+    if (k < 4) {
+      lo[k] = m;
+      d[k] = (uint32_t)x;
+    } else {
+      hz |= m;
+      hd |= (uint32_t)x;
+    }
+  }
+  const bool pos = hz == 0u && lo[3] < TOP;
+  neg = !pos && br == 0u && hd == 0u && d[3] < TOP && (d[0] | d[1] | d[2] | d[3]) != 0u;
+#pragma unroll
+  for (int k = 0; k < 4; ++k) s[k] = pos ? lo[k] : d[k];
+  return pos || neg;
+}
+
+// The start value of the log sum for a short plaintext +-s (pmd_short_classify):
+// T = s ms on K + 4 lazy columns (ms = Q R^2 B mod P, a uniform row of K limbs),
+// four Montgomery steps by P (they divide by B = 2^(28 * 4)), v = s Q R^2 mod P
+// below 2P (T < B P and the quotient below B), and muhat = v, or 2P - v for the
+// negative sign (s > 0 there, so 0 < v < 2P and muhat likewise): 0 <= muhat <=
+// 2P in the sum quads of the slot. 8 K mads.
+template <int K>
+XHE_DEV void pmd_lam_short(const PMD<K>& M, uint32_t* slot, const uint32_t (&sw)[4], bool neg,
+                           const uint32_t* __restrict__ ms) {
+  constexpr int L = kPmdShortLimbs;
+  constexpr uint32_t MASK = PMD<K>::MASK;
+  const uint32_t sl[L] = {sw[0] & MASK, ((sw[0] >> 28) | (sw[1] << 4)) & MASK, ((sw[1] >> 24) | (sw[2] << 8)) & MASK,
+                          ((sw[2] >> 20) | (sw[3] << 12)) & MASK};
+  uint64_t T[K + L];
+#pragma unroll
+  for (int j = 0; j < K + L; ++j) T[j] = 0;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const uint32_t mj = ms[j];
+#pragma unroll
+    for (int i = 0; i < L; ++i) T[i + j] = mad64s(sl[i], mj, T[i + j]);
+  }
+#pragma unroll
+  for (int i = 0; i < L; ++i) {
+    const uint32_t q = ((uint32_t)T[i] * M.n0inv) & MASK;
+#pragma unroll
+    for (int j = 0; j < K; ++j) T[i + j] = mad64s(q, M.p[j], T[i + j]);
+    T[i + 1] += T[i] >> 28;
+  }
+  uint32_t v[K];
+  uint64_t cy = 0;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const uint64_t x = T[L + j] + cy;
+    v[j] = (uint32_t)x & MASK;
+    cy = x >> 28;
+  }
+  int64_t br = 0;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const int64_t x = (int64_t)(2u * M.p[j]) - (int64_t)v[j] + br;
+    v[j] = neg ? ((uint32_t)x & MASK) : v[j];
+    br = x >> 28;
+  }
+  pmd_lam_store<K>(slot, v);
 }
 
 // r - s (K limbs each, both < 2^(28K)); returns the borrow out (1 if r < s)
@@ -739,6 +850,107 @@ XHE_DEV void pmd_mod_small(const PMD<K>& M, uint32_t (&m)[K]) {
   }
 #pragma unroll
   for (int t = 0; t < 3; ++t) pmd_csub<K>(M, m);
+}
+
+// ---- the exit through the digits (header: "The exit through the digits")
+// The sink of the first reduction's quotient digits m1: (MASK - m1_i) + E_i =
+// topc[i] - m1_i, four at a time into the e quads of the lane's slot (free
+// after the last row product; words 37..39 of the last quad are not read back)
+struct PmdTopcSink {
+  uint32_t* slot;
+  const uint32_t* topc;  // K words MASK + E_i, padded to a multiple of 4 (LDS)
+  XHE_DEV void put4(int i, const uint4& m) const {
+    const uint4 tc = *reinterpret_cast<const uint4*>(topc + i);
+    *reinterpret_cast<uint4*>(slot + (i >> 2) * 256) = make_uint4(tc.x - m.x, tc.y - m.y, tc.z - m.z, tc.w - m.w);
+  }
+};
+
+// The canonical residue x = (R a + P c)(1 + P L) R^-2 mod P^2 (< P^2, 2K
+// normalised limbs) from the state after the last product - a < P (1 + 2P/R),
+// c < R + 4P, Lhat = L R^2 mod P < R in the sum quads of the slot:
+//     u = REDC(a), its quotient digits m1 kept                  (u <= P)
+//     t = REDC(c + u Lhat), Lhat streamed from the slot         (t < 2P + 4)
+//     w = t + (R - 1 - m1) + E    (topc - m1, as a row product) (w < 2R)
+//     z = REDC(w), then z - P if z >= P                         (z < P + 3)
+//     u = P:  u <- 0, z <- (z + 1) mod P
+//     x = u + P z
+// 5 K^2 + K mads; the three reductions are block-form rows of Mont<K, 28, 1>
+// on P (Pl: P as a uniform row). topc: the block's K words MASK + E_i.
+template <int K>
+XHE_DEV void pmd_exit(const PMD<K>& M, const uint32_t (&a)[K], const uint32_t (&c)[K], uint32_t* slot,
+                      const uint32_t* topc, const uint32_t* Pl, uint32_t (&x)[2 * K]) {
+  using D = PMD<K>;
+  constexpr uint32_t MASK = D::MASK;
+  Mont<K, 28, 1> MN;
+  MN.init(Pl, M.n0inv);
+  uint32_t u[K], z[K];
+  {
+    uint64_t T[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) T[j] = a[j];
+    MN.red_rows_q(T, PmdTopcSink{slot, topc});
+    MN.normalize(T, u);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  {
+    uint32_t wv[K];  // topc_i - m1_i < 2^29
+#pragma unroll
+    for (int q = 0; q < D::EQ; ++q) {
+      const uint4 v = *reinterpret_cast<const uint4*>(slot + q * 256);
+      if (4 * q < K) wv[4 * q] = v.x;
+      if (4 * q + 1 < K) wv[4 * q + 1] = v.y;
+      if (4 * q + 2 < K) wv[4 * q + 2] = v.z;
+      if (4 * q + 3 < K) wv[4 * q + 3] = v.w;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    D::lam_to_limbs(slot);
+    __builtin_amdgcn_sched_barrier(0);
+    uint64_t T[K];
+#pragma unroll
+    for (int j = 0; j < K; ++j) T[j] = c[j];
+    MN.run(T, u, PmdLdsQ{slot});  // (c + u Lhat + q P) / R
+    MN.normalize(T, z);            // t
+    uint32_t cy = 0;
+#pragma unroll
+    for (int j = 0; j < K; ++j) {  // w, the top limb keeps the carry (< 2^29)
+      const uint32_t v = z[j] + wv[j] + cy;
+      T[j] = j + 1 < K ? (v & MASK) : v;
+      cy = v >> 28;
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    MN.red_rows(T, AZero{});
+    MN.normalize(T, z);
+  }
+  __builtin_amdgcn_sched_barrier(0);
+  pmd_csub<K>(M, z);
+  const bool up = pmd_csub<K>(M, u);  // u = P: the residue's low digit is 0 and one more P
+  uint32_t cy = up ? 1u : 0u;
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    const uint32_t v = z[j] + cy;
+    z[j] = v & MASK;
+    cy = v >> 28;
+  }
+  pmd_csub<K>(M, z);
+  __builtin_amdgcn_sched_barrier(0);
+  uint64_t T[2 * K];
+#pragma unroll
+  for (int j = 0; j < K; ++j) {
+    T[j] = u[j];
+    T[K + j] = 0;
+  }
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+#pragma unroll
+    for (int j = 0; j < K; ++j) T[i + j] = mad64s(z[j], M.p[i], T[i + j]);
+  }
+  uint64_t c2 = 0;
+#pragma unroll
+  for (int j = 0; j < 2 * K; ++j) {
+    const uint64_t v = T[j] + c2;
+    x[j] = (uint32_t)v & MASK;
+    c2 = v >> 28;
+  }
 }
 
 // Table-row conversion: a reduced residue X = x R^2 mod P^2 (< P^2, 2K limbs:

@@ -703,7 +703,7 @@ void encrypt_impl(const xhe_key* k, const uint32_t* m, const uint32_t* r, int64_
           const int G = paths::pmd_split(n, pins());
           const dim3 grid((unsigned)((n * G + 127) / 128), 2);
           auto run = [&](auto kern) {
-            launch(kern, grid, dim3(128), s, k->kd, k->kd.p.N, k->kd.q.N, k->kd.p2.N, k->kd.q2.N,
+            launch(kern, grid, dim3(128), s, k->kd, k->kd.p.N, k->kd.q.N,
                    m + (size_t)off * k->nw, r + (size_t)off * k->rand_words, k->rand_words, n, ws);
           };
           if (G == 16) run(k_djn_pmd<MP2, 37, Sh::RW, 16>);

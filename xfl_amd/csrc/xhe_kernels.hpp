@@ -605,16 +605,18 @@ __global__ void __launch_bounds__(128, 2) k_djn_pow_lds(KeyDev key, const uint32
 // first digit e < P and its log digit lhat < P (k_tab_to_pmd; pdigit_dev.hpp
 // "Additive second digit"), packed 32 + 32 words. Per prime and element: the
 // log sum starts from the plaintext - 1 + n m = 1 + P (Q m), so (1 + n m) is
-// the log digit muhat = Q m R^2 mod P (pmd_lam_plain: a REDC of m by P and one
-// Montgomery product mod P by the key's Q R^4, before the state exists); the
+// the log digit muhat = Q m R^2 mod P, before the state exists: for a short
+// plaintext +-s, s < 2^112 (every float encoding), +-s (Q R^2 2^112 mod P) /
+// 2^112 by a 4 x K product and four Montgomery steps (pmd_lam_short, decided
+// per wave), else a REDC of m by P and one Montgomery product mod P by the
+// key's Q R^4 (pmd_lam_plain); the
 // first window's row is the start value (e, 0), its lhat added to the sum;
 // each further window's row is fetched in one visit - e by LDS-DMA into the
 // wave's image and unpacked into limbs, lhat into registers and added to the
 // lane's log sum, which lives in the upper quads of the lane's slot - and e is
-// multiplied in (nwin - 1 row products, 4 K^2 mads each); the sum is folded
-// into c (PMD::finish), the result goes back to the 74-limb Montgomery form (R
-// a + P c = (1 + n m) h^a R^2 mod P^2, to_mont2) and one REDC mod P^2 on a
-// zero high half (S^2 mads) leaves it. The stored residue is the canonical one
+// multiplied in (nwin - 1 row products, 4 K^2 mads each); the exit goes through
+// the digits (pmd_exit: three reductions by P and two K x K products, 5 K^2 + K
+// mads, the log sum folded in on the way) to the canonical residue
 // djn_prime_lds writes. Output rows as k_djn_pow_lds (MP2 limbs, [prime][2
 // S4][count]) for k_crt_enc_w.
 //
@@ -632,8 +634,7 @@ __global__ void __launch_bounds__(128, 2) k_djn_pow_lds(KeyDev key, const uint32
 // needs no tree step to arrive where the finish reads it.
 template <class MP2, int KP, int RW, int G = 1>
 __global__ void __launch_bounds__(128, 2) k_djn_pmd(KeyDev key, const uint32_t* __restrict__ Pp,
-                                                    const uint32_t* __restrict__ Pq, const uint32_t* __restrict__ Np2,
-                                                    const uint32_t* __restrict__ Nq2,
+                                                    const uint32_t* __restrict__ Pq,
                                                     const uint32_t* __restrict__ m_words,
                                                     const uint32_t* __restrict__ a_words, int aw, int64_t count,
                                                     uint32_t* __restrict__ ws) {
@@ -682,10 +683,22 @@ __global__ void __launch_bounds__(128, 2) k_djn_pmd(KeyDev key, const uint32_t* 
   // finishes, and one that always has a window) takes muhat = Q m R^2 mod P,
   // the logarithm of 1 + n m; the other lanes start from zero. The state (a,
   // c) and the products' accumulators are not live yet.
-  if (G == 1 || g == 0)
-    pmd_lam_plain<KP>(M, slot, m_words + (size_t)e * key.nw, key.nw, prime ? key.mu_q : key.mu_p, prime ? Pq : Pp);
-  else
+  // A wave whose plaintexts are all short (+-s, s < 2^112: what the float
+  // encodings produce) takes the short entry, 8 K mads; one general plaintext
+  // among the lanes that run the prologue sends the whole wave through the
+  // general entry - no wave runs both.
+  if (G == 1 || g == 0) {
+    const uint32_t* mw = m_words + (size_t)e * key.nw;
+    uint32_t sw[4];
+    bool neg;
+    const bool is_short = pmd_short_classify<KP>(mw, key.nw, key.n_words, sw, neg);
+    if (__builtin_amdgcn_ballot_w64(!is_short) == 0ull)  // over the lanes inside this branch
+      pmd_lam_short<KP>(M, slot, sw, neg, prime ? key.ms_q : key.ms_p);
+    else
+      pmd_lam_plain<KP>(M, slot, mw, key.nw, prime ? key.mu_q : key.mu_p, prime ? Pq : Pp);
+  } else {
     D::lam_zero(slot);
+  }
   __builtin_amdgcn_sched_barrier(0);
   uint32_t a[KP], c[KP];
   if (G == 1 || g < key.nwin) {
@@ -728,15 +741,12 @@ __global__ void __launch_bounds__(128, 2) k_djn_pmd(KeyDev key, const uint32_t* 
     }
     if (g != 0) return;
   }
-  M.finish(a, c, slot, prime ? Pq : Pp);  // the log sum folded into c: the pair form of (1 + n m) h^a
-  __builtin_amdgcn_sched_barrier(0);
+  // out through the digits: the log sum folded in on the way to the canonical
+  // residue (1 + n m) h^a mod P^2 (pmd_exit; only P, no modulus P^2)
   uint32_t b[MP2::L];
-  M.to_mont2(a, c, b);  // (1 + n m) h^a R^2 mod P^2, unreduced (< 2^15 P^2 < R^2 P^2, top limb < 2^17)
+  pmd_exit<KP>(M, a, c, slot, topc, prime ? Pq : Pp, b);
   __builtin_amdgcn_sched_barrier(0);
-  MP2 N;
-  N.init(prime ? Nq2 : Np2, prime ? key.q2.n0inv : key.p2.n0inv);
-  N.redc_wide(b, AZero{});  // out of Montgomery form: (1 + n m) h^a mod P^2 (< 2 P^2)
-  N.reduce_once(b);
+  MP2 N;  // for the row layout of the store alone
   // the element index formed again from the thread index: held in registers
   // from the prologue to here, it spilled in the lane-group kernels
   const int64_t eo = ((int64_t)blockIdx.x * blockDim.x + (uint32_t)opaque_i((int)threadIdx.x)) / G;
@@ -1312,8 +1322,8 @@ __global__ void __launch_bounds__(128, 2) k_dec_pmd_out(KeyDev key, const uint32
 }
 
 // Private non-DJN encryption, last step: (1 + n m) r^(e_P) mod P^2 from the
-// digits of r^(e_P) (k_dec_pmd_pow), as k_djn_pmd finishes: R a + P c is the
-// 74-limb Montgomery form, and the product with the plain 1 + n m leaves it.
+// digits of r^(e_P) (k_dec_pmd_pow): R a + P c is the 74-limb Montgomery form
+// (to_mont2), and the product with the plain 1 + n m leaves it.
 // Rows as k_crt_enc reads them ([prime][2 S4][count]).
 template <class MP2, int KP>
 __global__ void __launch_bounds__(128, 2) k_nodjn_pmd_out(KeyDev key, const uint32_t* __restrict__ Pp,
