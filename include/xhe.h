@@ -141,6 +141,19 @@ int xhe_mulmod(const xhe_key* key, const uint32_t* a_dev, const int32_t* ea_dev,
  * out = c^k mod n^2, k per element (kw words, k < 2^kbits). */
 int xhe_powmod(const xhe_key* key, const uint32_t* c_dev, const uint32_t* k_dev, int kw, int kbits, int64_t count,
                uint32_t* out_dev, void* stream);
+/* Ciphertext packing (SecureBoost+'s cipher compressing; the drop-in's
+ * (c0 * 2^s + c1) * 2^s + ... in one launch chain, no window tables):
+ * out[j] = prod_{t<k} c[j*k+t]^(2^(shift_bits*(k-1-t))) mod n^2 for j < ceil(count/k);
+ * an element index >= count counts as 1 (the raw encryption of 0), so a short
+ * last group is left-aligned in the same k-slot layout. The plaintext of
+ * out[j] is sum_t x[j*k+t] * 2^(shift_bits*(k-1-t)): embed's layout with k
+ * times the slots, which xhe_umbed decodes. Needs no private key.
+ * k >= 1, shift_bits >= 1, k*shift_bits <= bitlen(n) - 2 (else XHE_EINVAL);
+ * XHE_EINVAL when out overlaps c. One lane group per output walks
+ * (k-1)*shift_bits dependent squarings: a call's time is the chain's, not the
+ * batch's. Timed as "k_pack" under xhe_profile. */
+int xhe_pack(const xhe_key* key, const uint32_t* c_dev, int64_t count, int k, int shift_bits, uint32_t* out_dev,
+             void* stream);
 /* utils.invert over n^2 (utils.py:71-76) for a batch: out = c^-1 mod n^2
  * (product-tree batch inversion). XHE_ENOINV when some c has no inverse. */
 int xhe_invert(const xhe_key* key, const uint32_t* c_dev, int64_t count, uint32_t* out_dev, void* stream);
@@ -213,6 +226,8 @@ int xhe_multiexp_host(const xhe_key* key, const uint32_t* bases, int64_t nbases,
                       int kw, int kbits, int64_t ncols, int64_t nterms, int win_bits, uint32_t* out);
 int xhe_segprod_host(const xhe_key* key, const uint32_t* c, const int32_t* d, int dmax, int64_t count,
                      const int64_t* seg_begin, int64_t nseg, uint32_t* out);
+/* xhe_pack: count ciphertexts in, ceil(count/k) out. */
+int xhe_pack_host(const xhe_key* key, const uint32_t* c, int64_t count, int k, int shift_bits, uint32_t* out);
 int xhe_mulmod_host(const xhe_key* key, const uint32_t* a, const int32_t* ea, const uint32_t* b, const int32_t* eb,
                     int64_t count, int dmax, uint32_t* out, int32_t* eout);
 /* c^k (or (c^-1)^k when invert_first: the negative-scalar branch). */

@@ -54,6 +54,8 @@ SIGNATURES = {
                                               _vp, _vp, _vp]),
     "xhe_mulmod": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
     "xhe_powmod": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, _vp, _vp]),
+    "xhe_pack": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, _vp]),
+    "xhe_pack_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp]),
     "xhe_invert": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp]),
     "xhe_mulmod_host": (ctypes.c_int, [_vp, _vp, _vp, _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp]),
     "xhe_powmod_host": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64, ctypes.c_int,

@@ -182,6 +182,34 @@ inline Pow powmod(int K, int lanes, bool ndig, const Pins& pins) {
   return K == 2048 && lanes == 4 && ndig && pins.ndig ? Pow::NDIG : Pow::MONT;
 }
 
+// Ciphertext packing (xhe_pack): one lane group per output walks a chain of
+// (k - 1) shift_bits dependent squarings, so the launch takes the chain's
+// time whatever the batch and the wider shape wins for longer than in the
+// other n^2 ops. The 16-lane row serves up to kPackRowMax outputs, the batch
+// shape beyond - at 2048 bits in Montgomery digits (k_ndig_pack) where powmod
+// would take them. $XHE_N2_TPI (4 or 16) pins the shape, $XHE_NDIG=0 the
+// Montgomery-limb kernel (k_pack_n2).
+// k = 7, shift_bits = 256 at 2048 bits (tools/bench_pack.py --shapes,
+// profiles/r21/pack_shapes.json and pack_shapes_sweep.json), 16 lanes vs the
+// 4-lane digits vs 4-lane Montgomery limbs: 512 outputs 18.7 / 28.2 / 45.0 ms,
+// 2,341 18.9 / 28.1 / 44.9 ms, 4,096 18.9 / 28.2 / 45.2 ms, 16,384 54.9 /
+// 48.9 / 45.6 ms. The 16-lane time steps up right behind 4,096 outputs (256
+// blocks, one a CU: 5,120 - 8,192 outputs 30.0 vs 28.5 ms in digits; 12,288
+// 42.8 vs 49.2 ms; 32,768 105 vs 50 ms), so the crossover stays where
+// kN2RowMax has it.
+struct Pack {
+  N2Shape shape;
+  Pow arith;  // NDIG: k_ndig_in / k_ndig_pack / k_ndig_out; MONT: k_pack_n2
+};
+constexpr int64_t kPackRowMax = kN2RowMax;
+
+// lanes: the batch n^2 shape's lanes per residue (Shape::MN2::TPI)
+inline Pack pack(int K, int lanes, bool ndig, int64_t ngroups, const Pins& pins) {
+  const N2Shape shape =
+      (pins.n2_tpi ? pins.n2_tpi == 16 : ngroups <= kPackRowMax) ? N2Shape::ROW16 : N2Shape::LANES4;
+  return {shape, shape == N2Shape::LANES4 ? powmod(K, lanes, ndig, pins) : Pow::MONT};
+}
+
 enum class Invert {
   WTREE,  // 2048, 16 lanes: a product tree of whole-block products (k_wtree_*), one launch per level
   TREE,   // k_tree_up / k_tree_down in lanes

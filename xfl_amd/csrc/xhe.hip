@@ -1020,6 +1020,44 @@ void powmod_impl(const xhe_key* k, const uint32_t* c, const uint32_t* kw_, int k
   }
 }
 
+// Ciphertext packing (xhe_pack): groups of kk ciphertexts folded by Horner.
+// MONT: one launch of k_pack_n2 (no workspace). NDIG: digits of every input,
+// the fold per group, digits -> words per output, over chunks of groups whose
+// inputs fit kChunk elements.
+template <class Sh, class MN2 = typename Sh::MN2>
+void pack_impl(const xhe_key* k, paths::Pow arith, const uint32_t* c, int64_t count, int kk, int shift, uint32_t* out,
+               hipStream_t s) {
+  const int64_t ngroups = (count + kk - 1) / kk;
+  if (arith == paths::Pow::NDIG) {
+    if constexpr (Sh::K == 2048 && MN2::TPI == 4) {
+      using D = ND2048;
+      constexpr int GPB = NdigWs<D>::GPB;
+      const int64_t gchunk = std::min<int64_t>(ngroups, std::max<int64_t>(1, kChunk / kk));
+      WsScope wsc(s);
+      uint2* st = wsc.get<uint2>((size_t)D::K * gchunk * kk * sizeof(uint2));
+      uint2* sto = wsc.get<uint2>((size_t)D::K * gchunk * sizeof(uint2));
+      uint32_t* rows = wsc.get<uint32_t>((size_t)2 * D::MN::S4 * gchunk * sizeof(uint32_t));
+      for (int64_t g0 = 0; g0 < ngroups; g0 += gchunk) {
+        const int64_t ng = std::min(gchunk, ngroups - g0);
+        const int64_t e0 = g0 * kk, n = std::min<int64_t>(ng * kk, count - e0);
+        launch((k_ndig_in<D, true>), dim3((unsigned)((n * D::TPI + 127) / 128)), dim3(128), s, k->kd,
+               c + (size_t)e0 * k->n2w, k->n2w, n, st);
+        {
+          ProfScope ps("k_pack", s);
+          launch(k_ndig_pack<D>, dim3((unsigned)std::min<int64_t>((ng + GPB - 1) / GPB, 1024)), dim3(128), s, k->kd, n,
+                 kk, shift, ng, st, sto);
+        }
+        launch((k_ndig_out<D, false>), dim3((unsigned)((ng * D::TPI + 127) / 128)), dim3(128), s, k->kd, sto, nullptr,
+               ng, out + (size_t)g0 * k->n2w, rows);
+      }
+      return;
+    } else no_path("pack (k_ndig_pack)");
+  }
+  const int blocks = (int)std::min<int64_t>((ngroups * MN2::TPI + 255) / 256, 1 << 16);
+  ProfScope ps("k_pack", s);
+  launch(k_pack_n2<MN2>, dim3(blocks), dim3(256), s, k->kd, n2h<MN2>(k).N, c, count, kk, shift, ngroups, out);
+}
+
 // Batch inversion mod n^2 via a product tree (Montgomery's trick in parallel).
 template <class Sh, class MN2 = typename Sh::MN2>
 int invert_impl(const xhe_key* k, const uint32_t* c, int64_t count, uint32_t* out, hipStream_t s) {
@@ -2296,6 +2334,57 @@ int xhe_powmod(const xhe_key* key, const uint32_t* c_dev, const uint32_t* k_dev,
       if (row) powmod_impl<Sh, typename Sh::MN2X>(key, c_dev, k_dev, kw, kbits, count, out_dev, hs);
       else powmod_impl<Sh>(key, c_dev, k_dev, kw, kbits, count, out_dev, hs);
     });
+    return XHE_OK;
+  });
+}
+
+namespace {
+// k >= 1, shift_bits >= 1 and k * shift_bits <= bitlen(n) - 2: the packed
+// plaintext keeps the sign bit xhe_umbed reads
+int pack_args(const xhe_key* key, const void* c, int64_t count, int k, int shift_bits, const void* out,
+              const char* who) {
+  if (!key || count < 0 || (count > 0 && (!c || !out))) return fail(XHE_EINVAL, std::string(who) + ": bad argument");
+  if (k < 1 || shift_bits < 1 || (int64_t)k * shift_bits > key->n_bits - 2)
+    return fail(XHE_EINVAL, std::string(who) + ": k >= 1, shift_bits >= 1 and k * shift_bits <= bitlen(n) - 2 required");
+  return XHE_OK;
+}
+}  // namespace
+
+int xhe_pack(const xhe_key* key, const uint32_t* c_dev, int64_t count, int k, int shift_bits, uint32_t* out_dev,
+             void* stream) {
+  return guarded([&]() -> int {
+    if (int rc = pack_args(key, c_dev, count, k, shift_bits, out_dev, "xhe_pack")) return rc;
+    if (count == 0) return XHE_OK;
+    const int64_t ngroups = (count + k - 1) / k;
+    if (out_dev < c_dev + (size_t)count * key->n2w && c_dev < out_dev + (size_t)ngroups * key->n2w)
+      return fail(XHE_EINVAL, "xhe_pack: out overlaps c");
+    DevGuard dg(key->device);
+    hipStream_t hs = (hipStream_t)stream;
+    with_shape(key->K, [&](auto sh) {
+      using Sh = decltype(sh);
+      const paths::Pack plan = paths::pack(Sh::K, Sh::MN2::TPI, key->kd.ndig, ngroups, pins());
+      if (plan.shape == paths::N2Shape::ROW16)
+        pack_impl<Sh, typename Sh::MN2X>(key, plan.arith, c_dev, count, k, shift_bits, out_dev, hs);
+      else pack_impl<Sh>(key, plan.arith, c_dev, count, k, shift_bits, out_dev, hs);
+    });
+    return XHE_OK;
+  });
+}
+
+int xhe_pack_host(const xhe_key* key, const uint32_t* c, int64_t count, int k, int shift_bits, uint32_t* out) {
+  return guarded([&]() -> int {
+    if (int rc = pack_args(key, c, count, k, shift_bits, out, "xhe_pack_host")) return rc;
+    if (count == 0) return XHE_OK;
+    DevGuard dg(key->device);
+    const int64_t ngroups = (count + k - 1) / k;
+    const size_t cb = (size_t)key->n2w * 4;
+    Stream st;
+    DevBuf dc((size_t)count * cb, st.s), dout((size_t)ngroups * cb, st.s);
+    HIPCHK(hipMemcpyAsync(dc.p, c, (size_t)count * cb, hipMemcpyHostToDevice, st.s));
+    int rc = xhe_pack(key, dc.as<uint32_t>(), count, k, shift_bits, dout.as<uint32_t>(), st.s);
+    if (rc != XHE_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)ngroups * cb, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
     return XHE_OK;
   });
 }

@@ -1859,6 +1859,50 @@ __global__ void __launch_bounds__(256, 2) k_powmod_n2(KeyDev key, const uint32_t
   }
 }
 
+// Ciphertext packing: out[j] = prod_{t<kk} c[j kk + t]^(2^(shift (kk-1-t)))
+// mod n^2 by Horner - per further element `shift` squarings and one product;
+// an element index >= count counts as 1 (the squarings stay, the product is
+// skipped). One lane group per output, grid-stride, words in and words out.
+// Nearly all of it is squarings, whose operand goes through LDS (SqLds); an
+// element enters Montgomery form by its own R2 product while the running
+// value waits in the same LDS slot. No global workspace.
+template <class MN2>
+__global__ void __launch_bounds__(256, 2) k_pack_n2(KeyDev key, const uint32_t* __restrict__ Nn2,
+                                                    const uint32_t* __restrict__ c, int64_t count, int kk, int shift,
+                                                    int64_t ngroups, uint32_t* __restrict__ out) {
+  const int64_t G_total = (int64_t)gridDim.x * blockDim.x / MN2::TPI;
+  const int64_t gid0 = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MN2::TPI;
+  __shared__ __attribute__((aligned(16))) uint32_t sq_img[4][SqLds<MN2>::WORDS_PER_WAVE];  // 256-thread blocks
+  const SqLds<MN2> L(sq_img[(threadIdx.x >> 6) & 3]);
+  for (int64_t j = gid0; j < ngroups; j += G_total) {
+    MN2 M;
+    M.init(Nn2, n2dev<MN2>(key).n0inv);
+    uint32_t b[MN2::L];
+    M.load_row(b, n2dev<MN2>(key).R1);  // Montgomery one
+    M.reduce_once(b);
+#pragma unroll 1
+    for (int t = 0; t < kk; ++t) {
+      if (t) {
+#pragma unroll 1
+        for (int s = 0; s < shift; ++s) {
+          L.put(b);
+          M.mul(b, L);
+        }
+      }
+      const int64_t e = j * kk + t;
+      if (e < count) {
+        L.put(b);
+        M.load_words(b, c + (size_t)e * key.n2w, key.n2w);
+        M.mul(b, ARow{n2dev<MN2>(key).R2});
+        M.mul(b, L);
+      }
+    }
+    M.mul(b, AOne{});
+    M.reduce_once(b);
+    M.store_words(b, out + (size_t)j * key.n2w, key.n2w);
+  }
+}
+
 // Public-key DJN encryption (paillier.py:210-212,283): (1 + n m) h^a mod n^2
 // with the fixed-base table of h mod n^2.
 template <class MN2, int RW>
@@ -2064,6 +2108,52 @@ __global__ void __launch_bounds__(128, 2) k_ndig_pow_k(KeyDev key, const uint32_
     const uint32_t* ke = k + (size_t)e * kw;
     pmdx_pow_window4(X, a, c, nwin, [&](int w) { return nibble(ke, kw, w); }, key.nd_d1, tab, gs, ops, GPB, topc);
     ndig_st_store<D>(a, c, st, count, e);
+  }
+}
+
+// Ciphertext packing in digits (k_pack_n2's Horner chain): group j folds the
+// digit states st[j kk .. j kk + kk) (count of them, from k_ndig_in) into
+// sto[j] (ngroups of them, for k_ndig_out) - per further element `shift`
+// squarings and one product with that element's digits, brought from its st
+// row to the LDS operand; an element index >= count skips the product.
+template <class D>
+__global__ void __launch_bounds__(128, 2) k_ndig_pack(KeyDev key, int64_t count, int kk, int shift, int64_t ngroups,
+                                                      const uint2* __restrict__ st, uint2* __restrict__ sto) {
+  constexpr int GPB = NdigWs<D>::GPB, L = D::L;
+  __shared__ uint2 ops_all[D::K * GPB];
+  __shared__ __attribute__((aligned(16))) uint32_t topc[D::K];
+  for (int i = threadIdx.x; i < D::K; i += blockDim.x) topc[i] = key.nd_topc[i];
+  __syncthreads();
+  const int gs = (int)gridDim.x * GPB;
+  const int gid0 = (int)blockIdx.x * GPB + (int)threadIdx.x / D::TPI;
+  uint2* ops = ops_all + threadIdx.x / D::TPI;
+  const OpLds op{ops, GPB};
+  const int g = D::G::g();
+  for (int64_t j = gid0; j < ngroups; j += gs) {
+    D X;
+    X.init(key.nd.N, key.nd.n0inv);
+    uint32_t a[L], c[L];
+    ndig_st_load<D>(a, c, st, count, j * kk);
+#pragma unroll 1
+    for (int t = 1; t < kk; ++t) {
+#pragma unroll 1
+      for (int s = 0; s < shift; ++s) {
+        pmdx_park<D>(a, c, ops, GPB);
+        wave_sync_mem_();
+        X.template run<true>(a, c, op, topc);
+        wave_sync_mem_();
+      }
+      const int64_t e = j * kk + t;
+      if (e < count) {
+        const uint2* p = pmdx_launder(st) + e;
+#pragma unroll
+        for (int i = 0; i < L; ++i) ops[(g * L + i) * GPB] = p[(size_t)(g * L + i) * count];
+        wave_sync_mem_();
+        X.template run<false>(a, c, op, topc);
+        wave_sync_mem_();
+      }
+    }
+    ndig_st_store<D>(a, c, sto, ngroups, j);
   }
 }
 

@@ -243,6 +243,24 @@ def powmod_words(ctx, cw, kw_, kbits, invert_first=False, num_cores=-1):
     return out
 
 
+def pack_words(ctx, cw, k, shift_bits, num_cores=-1):
+    """Groups of k ciphertexts folded into one (xhe_pack_host): [count, n2w]
+    words -> [ceil(count / k), n2w]. Shards split at multiples of k, so every
+    group is folded on one device."""
+    cw = _u32(cw)
+    n = cw.shape[0]
+    ng = -(-n // k)
+    out = nat.empty((ng, cw.shape[1]), np.uint32)
+    if n == 0:
+        return out
+
+    def body(dk, lo, hi):  # a range of groups
+        nat.check(nat.lib().xhe_pack_host(dk.handle, _vp(cw, lo * k), min(hi * k, n) - lo * k, int(k),
+                                          int(shift_bits), _vp(out, lo)), "pack")
+    sharded(ctx, ng, body, num_cores)
+    return out
+
+
 def raw_mul_words(ctx, cw, kabs, neg, num_cores=-1):
     """PaillierCiphertext._raw_mul (paillier.py:156-187) for encoded scalars
     given as |k| with a sign: a positive k gives c^k; a negative scalar

@@ -694,6 +694,19 @@ def powmod(dk, c, kw_, kbits, invert_first=False):
     return out
 
 
+def pack(dk, c, k, shift_bits):
+    """device ct [n, n2w] -> device [ceil(n / k), n2w]: groups of k folded into
+    one ciphertext, element t of a group shifted up by shift_bits * (k - 1 - t)
+    plaintext bits (xhe_pack)"""
+    torch = _torch()
+    dev = dk.device
+    n = c.shape[0]
+    with _On(dev):
+        out = torch.empty((-(-n // k), dk.n2w), dtype=torch.int32, device=f"cuda:{dev}")
+    nat.check(nat.lib().xhe_pack(dk.handle, _dp(c), n, int(k), int(shift_bits), _dp(out), _sp(dev)), "pack")
+    return out
+
+
 def segprod(dk, c, d, seg):
     """out[s] = prod_{i in segment s} c_i^(2^d_i) mod n^2 (device c; host d
     int32 and int64 offsets) -> device [nseg, n2w]"""

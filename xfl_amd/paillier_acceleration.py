@@ -21,6 +21,14 @@ decryption they feed (xhe_embed_f64 / xhe_umbed, include/xhe.h):
       kept as its float64 columns; Paillier.encrypt packs them on the device
   decrypt_umbed(context, data, num, interval, precison, num_cores): umbed of
       Paillier.decrypt(..., out_origin=True), unpacked behind the decryption
+
+And one pair packs ciphertexts themselves (opt-in, both parties run this
+library; xhe_pack): a grad/hess plaintext uses num * log2(interval) = 256
+bits, so a party holding only the public key can fold k of them into one
+  pack_factor(n, num, interval) -> k (7 at 2048 bits)
+  pack_ciphertexts(arr, num, interval, k) -> ceil(count / k) ciphertexts
+  decrypt_unpack(context, packed, count, num, interval, precison, k) ->
+      decrypt_umbed's floats of the count ciphertexts that were packed
 """
 from typing import List
 
@@ -156,6 +164,105 @@ def decrypt_umbed(context, data, num: int, interval: int = (1 << 128), precison:
         return [f32[j] for j in range(num)]
     vals = Paillier.decrypt(context, data, num_cores=num_cores, out_origin=True)
     return [np.array(col, dtype=np.float32) for col in umbed(vals, num, interval, precison)]
+
+
+def pack_factor(n: int, num: int = 2, interval: int = (1 << 128)) -> int:
+    """How many ciphertexts of `num` slots pack_ciphertexts folds into one
+    under the modulus n: the largest k with k * num * log2(interval) <=
+    bitlen(n) - 2 (one bit below xhe_umbed's geometry, so the packed value
+    keeps the sign rule of a single one); 0 when the device does not unpack
+    this slot width at all (packed_geometry refuses k = 1)."""
+    if packed_geometry(n, num, interval, 0) is None:
+        return 0
+    return (int(n).bit_length() - 2) // (num * (interval.bit_length() - 1))
+
+
+def _pack_k(n, num, interval, k):
+    kmax = pack_factor(n, num, interval)
+    if kmax < 1:
+        raise ValueError("pack: this (num, interval) is not a device packing geometry for the key")
+    if k is None:
+        return kmax
+    if not isinstance(k, (int, np.integer)) or isinstance(k, bool) or not 1 <= k <= kmax:
+        raise ValueError(f"pack: k must be in [1, {kmax}] for this key, num and interval")
+    return int(k)
+
+
+def pack_ciphertexts(arr, num: int = 2, interval: int = (1 << 128), k: int = None):
+    """Fold every k consecutive ciphertexts of a 1-D array into one (cipher
+    compressing): with s = num * log2(interval) plaintext bits per input,
+    out[j] = ((c[jk]^(2^s) * c[jk+1])^(2^s) * ...) mod n^2, whose plaintext
+    sum_t x[jk+t] * 2^(s (k-1-t)) is embed's layout with num * k slots; a short
+    last group is filled with encryptions of 0. k defaults to
+    pack_factor(n, num, interval). Needs only the public key; every input must
+    be at exponent 0 (embed_packed's). Returns a PaillierArray of ceil(count /
+    k) ciphertexts at exponent 0, in HBM when the input is; decrypt_unpack is
+    the receiving side.
+
+    One call walks (k - 1) * s dependent squarings per output whatever the
+    batch: pack everything a message carries in one call."""
+    from .paillier import PaillierCiphertext, ops, resident
+    from .paillier.array import PaillierArray
+    if isinstance(arr, np.ndarray) and arr.dtype == object and arr.ndim == 1 and \
+            all(isinstance(c, PaillierCiphertext) for c in arr):
+        arr = PaillierArray(arr)
+    if not isinstance(arr, PaillierArray):
+        raise TypeError("pack_ciphertexts takes a PaillierArray or an object array of PaillierCiphertext")
+    if arr.ndim != 1:
+        raise ValueError("pack_ciphertexts takes a 1-D array")
+    context = arr.context
+    if context is None:
+        raise ValueError("ciphertext array without a context: pass one to Paillier.ciphertext_from")
+    k = _pack_k(context.n, num, interval, k)
+    if arr._has_na():
+        raise ValueError("pack_ciphertexts: missing entries cannot be packed")
+    if arr.exponents.any():
+        raise ValueError("pack_ciphertexts: every ciphertext must be at exponent 0")
+    shift = num * (interval.bit_length() - 1)
+    ng = -(-arr.size // k)
+    exps = np.zeros(ng, dtype=np.int32)
+    arr = arr._aligned_words(ops.n2w_of(context))
+    if not arr.size:
+        return PaillierArray.from_buffers(context, np.zeros((0, ops.n2w_of(context)), dtype=np.uint32), exps)
+    dev = resident.device_for(context)
+    if arr._resident_on(dev):
+        return PaillierArray.from_device(context, resident.pack(context.device_key(dev), arr._dw(dev), k, shift), exps)
+    return PaillierArray.from_buffers(context, ops.pack_words(context, arr.words, k, shift), exps)
+
+
+def unpack_columns(cols, count: int, num: int, k: int):
+    """decrypt_unpack's index mapping: cols[t * num + i][j] (the num * k digit
+    columns of the packed plaintexts) -> out[i][j * k + t], cut to count."""
+    cols = np.asarray(cols)
+    ng = cols.shape[1]
+    if cols.shape[0] != num * k or not (ng - 1) * k < count <= ng * k:
+        raise ValueError("unpack: column count or element count does not match the packing")
+    # [t, i, j] -> [i, j, t]
+    return [np.ascontiguousarray(c.reshape(-1)[:count]) for c in cols.reshape(k, num, ng).transpose(1, 2, 0)]
+
+
+def decrypt_unpack(context, packed, count: int, num: int = 2, interval: int = (1 << 128), precison: int = 64,
+                   k: int = None, num_cores: int = -1):
+    """The receiving side of pack_ciphertexts: `num` float32 arrays of length
+    count, equal bit for bit to decrypt_umbed(context, original, num, interval,
+    precison) of the ciphertexts that were packed whenever every original
+    plaintext is the exact sum of its num centred digits - the condition under
+    which the reference's umbed loses nothing. It is decrypt_umbed(context,
+    packed, num * k, ...) with column t * num + i, row j moved to output i,
+    element j * k + t: ceil(count / k) decryptions instead of count.
+
+    Overflow: a bin sum that outgrows its slot is silently dropped by the
+    reference's umbed; here it spills into the neighbouring element's slot.
+    The slots must hold the sums (as SecureBoost's choice of interval
+    assumes)."""
+    k = _pack_k(context.n, num, interval, k)
+    count = int(count)
+    if count < 0 or len(packed) != -(-count // k):
+        raise ValueError("decrypt_unpack: count does not match the packed array")
+    if count == 0:
+        return [np.zeros(0, dtype=np.float32) for _ in range(num)]
+    cols = decrypt_umbed(context, packed, num * k, interval, precison, num_cores)
+    return unpack_columns(cols, count, num, k)
 
 
 def _centred_digits(x, num: int, interval: int):
