@@ -10,6 +10,20 @@
  * Return value: 0 on success, negative XHE_E* on failure; xhe_last_error()
  * gives the thread-local message. A key handle is immutable after creation
  * and may be shared between threads; calls on distinct streams are reentrant.
+ *
+ * Ciphertext operands: the seven entry points that read ciphertext words -
+ * xhe_decrypt, xhe_mulmod, xhe_powmod, xhe_pack, xhe_invert, xhe_segprod and
+ * xhe_multiexp (and their _host variants) - accept ANY value in [0, 2^(32 n2w))
+ * in an operand row, not only residues below n^2: a received payload is not
+ * reduced on its way into a device array (xhe_wire_decode, xhe_wire_scan and
+ * xhe_wire_unpack reject or cut only what is wider than n2w words). The result
+ * is the one for the operand mod n^2, word for word what Python's integers
+ * give for the unreduced value (pow(c, k, n^2), a * b % n^2, pow(c, -1, n^2),
+ * the decryption of c mod n^2), on every kernel path and key size, and every
+ * output is below n^2. How far a value can exceed n^2 depends on the key:
+ * floor((2^(32 n2w) - 1) / n^2) is 1 to 4 for an n of key_bits bits and 63 for
+ * n = 2^(key_bits - 3) + 1. The plaintext and obfuscator inputs keep their own
+ * bounds: m < n for xhe_encrypt, X < n^2 for xhe_encrypt_obf.
  */
 #ifndef XHE_H
 #define XHE_H
@@ -64,6 +78,7 @@ int xhe_rand(const xhe_key* key, const uint8_t* seed32, uint64_t nonce, int64_t 
 
 /* Paillier._encrypt_single + PaillierCiphertext.obfuscate (paillier.py:273-287,
  * 189-232): ct = (1 + n*m) * X mod n^2 with X from rand (NULL = no obfuscation).
+ * m: nw words per element, m < n.
  * The kernel shape follows the key and the batch size. A public non-DJN
  * 2048-bit key (X = r^n mod n^2, the obfuscator of a party that received the
  * key: linear_regression/trainer.py:145-154,197-200) runs one 1,024-thread
@@ -91,7 +106,11 @@ int xhe_obf_fill(const xhe_key* key, const uint32_t* rand_dev, int64_t count, ui
 int xhe_encrypt_obf(const xhe_key* key, const uint32_t* m_dev, uint32_t* obf_dev, int64_t count, int wipe,
                     uint32_t* ct_dev, void* stream);
 
-/* Paillier._decrypt_single arithmetic (paillier.py:341-366): ct -> encoded m. */
+/* Paillier._decrypt_single arithmetic (paillier.py:341-366): ct -> encoded m.
+ * ct: any value below 2^(32 n2w); m is the decryption of ct mod n^2 (what the
+ * reference's powmod(c, p - 1, p^2) and powmod(c, q - 1, q^2) give for the
+ * unreduced c), m < n. A ct that shares a factor with n has no meaningful
+ * plaintext; the call still succeeds. */
 int xhe_decrypt(const xhe_key* key, const uint32_t* ct_dev, int64_t count, uint32_t* m_dev, void* stream);
 
 /* PaillierEncoder.decode_single + astype(np.float32) (encoder.py:56-64,
@@ -134,11 +153,13 @@ int xhe_umbed(const xhe_key* key, const uint32_t* m_dev, int64_t count, int num,
  * ea/eb may be NULL (all 0). dmax >= max |ea - eb| bounds the squarings.
  * As in the reference, a gap d with 2^d >= min_value_for_negative (d >=
  * ~bitlen(n) - 1) takes _raw_mul's negative branch: that operand is raised to
- * 2^d - n instead (paillier.py:79-86, 173-187; same plaintext, other bits). */
+ * 2^d - n instead (paillier.py:79-86, 173-187; same plaintext, other bits).
+ * a, b: any values below 2^(32 n2w), taken mod n^2 (units or not); out < n^2. */
 int xhe_mulmod(const xhe_key* key, const uint32_t* a_dev, const int32_t* ea_dev, const uint32_t* b_dev,
                const int32_t* eb_dev, int64_t count, int dmax, uint32_t* out_dev, int32_t* eout_dev, void* stream);
 /* PaillierCiphertext._raw_mul positive branch (paillier.py:156-187):
- * out = c^k mod n^2, k per element (kw words, k < 2^kbits). */
+ * out = c^k mod n^2, k per element (kw words, k < 2^kbits). c: any value
+ * below 2^(32 n2w), taken mod n^2; k = 0 gives 1 for every c. out < n^2. */
 int xhe_powmod(const xhe_key* key, const uint32_t* c_dev, const uint32_t* k_dev, int kw, int kbits, int64_t count,
                uint32_t* out_dev, void* stream);
 /* Ciphertext packing (SecureBoost+'s cipher compressing; the drop-in's
@@ -151,11 +172,14 @@ int xhe_powmod(const xhe_key* key, const uint32_t* c_dev, const uint32_t* k_dev,
  * k >= 1, shift_bits >= 1, k*shift_bits <= bitlen(n) - 2 (else XHE_EINVAL);
  * XHE_EINVAL when out overlaps c. One lane group per output walks
  * (k-1)*shift_bits dependent squarings: a call's time is the chain's, not the
- * batch's. Timed as "k_pack" under xhe_profile. */
+ * batch's. Timed as "k_pack" under xhe_profile. c: any values below
+ * 2^(32 n2w), taken mod n^2; out < n^2. */
 int xhe_pack(const xhe_key* key, const uint32_t* c_dev, int64_t count, int k, int shift_bits, uint32_t* out_dev,
              void* stream);
 /* utils.invert over n^2 (utils.py:71-76) for a batch: out = c^-1 mod n^2
- * (product-tree batch inversion). XHE_ENOINV when some c has no inverse. */
+ * (product-tree batch inversion). c: any values below 2^(32 n2w), taken mod
+ * n^2. XHE_ENOINV when some c mod n^2 has no inverse (it shares a factor with
+ * n, or is 0), whether c itself lies below n^2 or not. */
 int xhe_invert(const xhe_key* key, const uint32_t* c_dev, int64_t count, uint32_t* out_dev, void* stream);
 
 /* Homomorphic sum per segment (np.sum / pandas groupby('bin').sum() over
@@ -168,7 +192,8 @@ int xhe_invert(const xhe_key* key, const uint32_t* c_dev, int64_t count, uint32_
  * pairwise adds while every gap is below the negative-branch threshold
  * (see xhe_mulmod); past it the reference's bits depend on the addition tree,
  * and the caller pre-aligns those elements (xfl_amd/paillier/ops.py
- * segment_sums_words). */
+ * segment_sums_words). c: any values below 2^(32 n2w), taken mod n^2, on both
+ * first levels (with and without the exponent array); out < n^2. */
 int xhe_segprod(const xhe_key* key, const uint32_t* c_dev, const int32_t* d_dev, int dmax, int64_t count,
                 const int64_t* seg_begin, int64_t nseg, uint32_t* out_dev, void* stream);
 
@@ -181,7 +206,8 @@ int xhe_segprod(const xhe_key* key, const uint32_t* c_dev, const int32_t* d_dev,
  * with the caller folding signs (base = c or c^-1, xhe_invert) and exponent
  * alignment (k << (e - e_min)) into idx/k. k: kw words per term, < 2^kbits.
  * Straus windows of win_bits (0 = chosen to minimise products) with per-base
- * tables shared by all columns. */
+ * tables shared by all columns. bases: any values below 2^(32 n2w), taken mod
+ * n^2; out < n^2. */
 int xhe_multiexp(const xhe_key* key, const uint32_t* bases_dev, int64_t nbases, const int32_t* idx_dev,
                  const uint32_t* k_dev, int kw, int kbits, int64_t ncols, int64_t nterms, int win_bits,
                  uint32_t* out_dev, void* stream);

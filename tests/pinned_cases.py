@@ -25,7 +25,11 @@ CASES, per case:
           parameter after ':' (powmod:53 = 53-bit exponents, powmod:full =
           exponents up to n - 1; multiexp:24 = 24 bases, its count the
           columns). segprod* counts are input elements: `checked` adds up the
-          lengths of the segments compared.
+          lengths of the segments compared. A name with `_wide` is the same
+          operation on operands at and above n^2 (wide_operands below, from
+          tests/wide_cases.py: include/xhe.h promises the result for the
+          operand mod n^2), listed in every case that runs its narrow twin,
+          at that case's counts.
   paths   [(line, decision)] or [(line, decision, default line)]: input lines
           of tests/native/paths_check.cpp without switches. With the case's
           env appended the planner must answer `decision`; the same line
@@ -88,8 +92,15 @@ _D3 = "decrypt K=3072 lanes=2 pmdx_dec=1 rns=0"
 _D4 = "decrypt K=4096 lanes=4 pmdx_dec=1 rns=0"
 _D8 = "decrypt K=8192 lanes=16 pmdx_dec=1 rns=0"
 _PUB2 = "enc_nodjn K=2048 priv=0 ndig=1"
-_DEC2 = ("decrypt_golden", "decrypt_arb")
-_N2OPS = ("add_eq", "add_gap", "powmod:53", "powmod:full", "powmod_inv:53", "powmod_inv:full", "segprod", "segprod_eq")
+_DEC2 = ("decrypt_golden", "decrypt_arb", "decrypt_arb_wide")
+_DECX = ("decrypt_golden", "decrypt_arb_wide")  # 3072 bits and up
+_N2OPS = ("add_eq", "add_gap", "powmod:53", "powmod:full", "powmod_inv:53", "powmod_inv:full", "segprod", "segprod_eq",
+          "add_eq_wide", "add_gap_wide", "powmod_wide:53", "powmod_inv_wide:53", "segprod_wide", "segprod_eq_wide")
+# narrow operation -> its twin on operands at and above n^2
+WIDE_TWIN = {"add_eq": "add_eq_wide", "add_gap": "add_gap_wide", "powmod:53": "powmod_wide:53",
+             "powmod_inv:53": "powmod_inv_wide:53", "invert": "invert_wide", "segprod": "segprod_wide",
+             "segprod_eq": "segprod_eq_wide", "segprod_nod": "segprod_nod_wide", "multiexp:24": "multiexp_wide:24",
+             "decrypt_arb": "decrypt_arb_wide"}
 
 
 def _ops(names, counts):
@@ -125,34 +136,34 @@ CASES = [
      "paths": [(f"{_D2} count=1100", "RNS")],
      "labels": [(op, 1100, lab, n) for op in _DEC2 for lab, n in (("k_dec_rns", ">0"), ("k_dec_pow", 0))]},
     {"name": "dec-tpi4-3072", "env": {"XHE_DEC_TPI": "4"}, "key": ("3072", "priv_djn"),
-     "ops": [("decrypt_golden", (1, 15, 65))],
+     "ops": _ops(_DECX, (1, 15, 65)),
      "paths": [(f"{_D3} count=1", "QUAD4"), (f"{_D3} count=65", "QUAD4")]},
     {"name": "dec-tpi4-4096", "env": {"XHE_DEC_TPI": "4"}, "key": ("4096", "priv_djn"),
-     "ops": [("decrypt_golden", (1, 15, 65))],
+     "ops": _ops(_DECX, (1, 15, 65)),
      "paths": [(f"{_D4} count=1", "QUAD4"), (f"{_D4} count=65", "QUAD4")]},
     {"name": "dec-tpi4-8192", "env": {"XHE_DEC_TPI": "4"}, "key": ("8192", "priv_djn"),
-     "ops": [("decrypt_golden", (1, 5))],
+     "ops": _ops(_DECX, (1, 5)),
      "paths": [(f"{_D8} count=1", "QUAD4"), (f"{_D8} count=5", "QUAD4")]},
     {"name": "dec-tpi16-3072", "env": {"XHE_DEC_TPI": "16"}, "key": ("3072", "priv_djn"),
-     "ops": [("decrypt_golden", (1, 15, 17, 5121))],
+     "ops": _ops(_DECX, (1, 15, 17, 5121)),
      "paths": [(f"{_D3} count=5121", "ROW16")]},
     {"name": "dec-tpi16-4096", "env": {"XHE_DEC_TPI": "16"}, "key": ("4096", "priv_djn"),
-     "ops": [("decrypt_golden", (1, 15, 17, 5121))],
+     "ops": _ops(_DECX, (1, 15, 17, 5121)),
      "paths": [(f"{_D4} count=5121", "ROW16")]},
     {"name": "dec-tpi16-8192", "env": {"XHE_DEC_TPI": "16"}, "key": ("8192", "priv_djn"),
-     "ops": [("decrypt_golden", (1, 5))],
+     "ops": _ops(_DECX, (1, 5)),
      "paths": [(f"{_D8} count=1", "ROW16"), (f"{_D8} count=5", "ROW16")], "confirms_default": True},
     {"name": "dec-tpi1-8192", "env": {"XHE_DEC_TPI": "1"}, "key": ("8192", "priv_djn"),
-     "ops": [("decrypt_golden", (1, 5))],
+     "ops": _ops(_DECX, (1, 5)),
      "paths": [(f"{_D8} count=1", "PMDX"), (f"{_D8} count=5", "PMDX")]},
     {"name": "dec-tpi1-pmdx0-3072", "env": {"XHE_DEC_TPI": "1", "XHE_DEC_PMDX": "0"}, "key": ("3072", "priv_djn"),
-     "ops": [("decrypt_golden", (1, 15, 129))],
+     "ops": _ops(_DECX, (1, 15, 129)),
      "paths": [(f"{_D3} count=1", "POW1"), (f"{_D3} count=129", "POW1")]},
     {"name": "dec-tpi1-pmdx0-4096", "env": {"XHE_DEC_TPI": "1", "XHE_DEC_PMDX": "0"}, "key": ("4096", "priv_djn"),
-     "ops": [("decrypt_golden", (1, 15, 65))],
+     "ops": _ops(_DECX, (1, 15, 65)),
      "paths": [(f"{_D4} count=1", "POW1"), (f"{_D4} count=65", "POW1")]},
     {"name": "dec-tpi1-pmdx0-8192", "env": {"XHE_DEC_TPI": "1", "XHE_DEC_PMDX": "0"}, "key": ("8192", "priv_djn"),
-     "ops": [("decrypt_golden", (1, 5))],
+     "ops": _ops(_DECX, (1, 5)),
      "paths": [(f"{_D8} count=1", "POW1"), (f"{_D8} count=5", "POW1")]},
     # ------------------------------------------------- encrypt, 2048 bits
     {"name": "enc-ndigpub0", "env": {"XHE_NDIG_PUB": "0"}, "key": ("2048-djn", "pub_djn"),
@@ -166,7 +177,8 @@ CASES = [
      "labels": [("encrypt", 257, "k_nodjn_crt", 1)]},
     {"name": "enc-ndig0-lanes4", "env": {"XHE_NDIG": "0", "XHE_PUB_TPI": "4", "XHE_N2_TPI": "4"},
      "key": ("2048-nodjn", "pub_nodjn"),
-     "ops": [("encrypt", (1, 65))] + _ops(("powmod:53", "powmod:full", "powmod_inv:53", "powmod_inv:full"), (1, 65)),
+     "ops": [("encrypt", (1, 65))] + _ops(("powmod:53", "powmod:full", "powmod_inv:53", "powmod_inv:full",
+                                           "powmod_wide:53", "powmod_inv_wide:53"), (1, 65)),
      "paths": [(f"{_PUB2} count=1", "PUB"), (f"{_PUB2} count=65", "PUB"), ("n2 count=65", "LANES4"),
                ("powmod K=2048 lanes=4 ndig=1", "MONT")],
      "labels": [("encrypt", 65, "k_nodjn_pub", 1), ("encrypt", 65, "k_nodjn_pub_wave", 0),
@@ -182,7 +194,8 @@ CASES = [
      "labels": [("encrypt", 2049, "k_nodjn_pub_wave", 1), ("encrypt", 2049, "k_nodjn_pub", 0)]},
     # ------------------------------------------------------ mod n^2 operations
     {"name": "n2-lanes4-2048", "env": {"XHE_N2_TPI": "4", "XHE_ADD_WAVE": "0"}, "key": ("2048-nodjn", "pub_nodjn"),
-     "ops": _ops(_N2OPS, (1, 33, 65)) + [("invert", (1, 2, 3, 65)), ("multiexp:24", (5,))],
+     "ops": _ops(_N2OPS, (1, 33, 65)) + _ops(("invert", "invert_wide"), (1, 2, 3, 65))
+            + _ops(("multiexp:24", "multiexp_wide:24"), (5,)),
      "paths": [("n2 count=1", "LANES4"), ("n2 count=65", "LANES4"),
                ("add K=2048 lanes=4 count=33 dmax=0", "BARRETT"), ("add K=2048 lanes=4 count=33 dmax=3", "MONT"),
                ("powmod K=2048 lanes=4 ndig=1", "NDIG", "powmod K=2048 lanes=16 ndig=1"),
@@ -194,31 +207,33 @@ CASES = [
     # exponent's width does not depend on the block edge, which the 53-bit powers run at every count)
     {"name": "n2-lanes4-3072", "env": {"XHE_N2_TPI": "4", "XHE_ADD_WAVE": "0"}, "key": ("3072", "pub_nodjn"),
      "ops": _ops([op for op in _N2OPS if not op.endswith(":full")], (1, 33, 65))
-            + [("powmod:full", (65,)), ("powmod_inv:full", (33,)), ("invert", (1, 2, 3, 65)), ("multiexp:24", (5,))],
+            + [("powmod:full", (65,)), ("powmod_inv:full", (33,))] + _ops(("invert", "invert_wide"), (1, 2, 3, 65))
+            + _ops(("multiexp:24", "multiexp_wide:24"), (5,)),
      "paths": [("n2 count=1", "LANES4"), ("n2 count=33", "LANES4"), ("n2 count=65", "LANES4")]},
     {"name": "n2-lanes4-addbar0", "env": {"XHE_N2_TPI": "4", "XHE_ADD_WAVE": "0", "XHE_ADD_BAR": "0"},
      "key": ("2048-nodjn", "pub_nodjn"),
-     "ops": [("add_eq", (1, 33, 65))],
+     "ops": _ops(("add_eq", "add_eq_wide"), (1, 33, 65)),
      "paths": [("n2 count=65", "LANES4"), ("add K=2048 lanes=4 count=33 dmax=0", "MONT")],
      "labels": [("add_eq", c, "k_add_barrett", 0) for c in (1, 33, 65)]},
     {"name": "add-wave0", "env": {"XHE_ADD_WAVE": "0"}, "key": ("2048-nodjn", "pub_nodjn"),
-     "ops": _ops(("add_eq", "add_gap"), (1, 17, 256)),
+     "ops": _ops(("add_eq", "add_gap", "add_eq_wide", "add_gap_wide"), (1, 17, 256)),
      "paths": [("add K=2048 lanes=16 count=1 dmax=0", "MONT"), ("add K=2048 lanes=16 count=17 dmax=3", "MONT"),
                ("add K=2048 lanes=16 count=256 dmax=0", "MONT")],
      "labels": [("add_eq", 17, "k_add_barrett", 0)]},
     {"name": "sum-words0", "env": {"XHE_SUM_WORDS": "0"}, "key": ("2048-nodjn", "pub_nodjn"),
-     "ops": _ops(("segprod_eq", "segprod_nod"), (60,)),
+     "ops": _ops(("segprod_eq", "segprod_nod", "segprod_eq_wide", "segprod_nod_wide"), (60,)),
      "paths": [("segprod count=60 dmax=0 has_d=1", "ALIGN"), ("segprod count=60 dmax=0 has_d=0", "ALIGN")]},
     {"name": "sum-words0-lanes4", "env": {"XHE_SUM_WORDS": "0", "XHE_N2_TPI": "4"}, "key": ("2048-nodjn", "pub_nodjn"),
-     "ops": _ops(("segprod_eq", "segprod_nod"), (60, 65)),
+     "ops": _ops(("segprod_eq", "segprod_nod", "segprod_eq_wide", "segprod_nod_wide"), (60, 65)),
      "paths": [("n2 count=60", "LANES4"), ("segprod count=60 dmax=0 has_d=1", "ALIGN"),
                ("segprod count=65 dmax=0 has_d=0", "ALIGN")]},
     {"name": "mexp-wave0", "env": {"XHE_MEXP_WAVE": "0"}, "key": ("2048-nodjn", "pub_nodjn"),
-     "ops": [("multiexp:24", (5,)), ("multiexp:300", (3,))],
+     "ops": [("multiexp:24", (5,)), ("multiexp:300", (3,)), ("multiexp_wide:24", (5,))],
      "paths": [("horner K=2048 lanes=16 ncols=5", "LANES"), ("horner K=2048 lanes=16 ncols=3", "LANES")],
      "labels": [("multiexp:24", 5, "k_mexp_horner", 1)]},
     {"name": "n2-row16-4200", "env": {"XHE_N2_TPI": "16"}, "key": ("2048-nodjn", "pub_nodjn"),
-     "ops": _ops(("add_eq", "add_gap", "powmod:53", "powmod:full", "powmod_inv:53", "invert"), (4200,)),
+     "ops": _ops(("add_eq", "add_gap", "powmod:53", "powmod:full", "powmod_inv:53", "invert", "add_eq_wide",
+                  "add_gap_wide", "powmod_wide:53", "powmod_inv_wide:53", "invert_wide"), (4200,)),
      "paths": [("n2 count=4200", "ROW16"),
                ("add K=2048 lanes=16 count=4200 dmax=0", "MONT", "add K=2048 lanes=4 count=4200 dmax=0"),
                ("powmod K=2048 lanes=16 ndig=1", "MONT", "powmod K=2048 lanes=4 ndig=1")],
@@ -289,6 +304,20 @@ def _tile(w, count, start=0):
     return np.ascontiguousarray(np.tile(w, (-(-count // w.shape[0]), 1))[:count])
 
 
+def wide_operands(K, n, d, what, units):
+    """d operands of a key, 3 in 4 of them at or above n^2 (tests/wide_cases.py
+    wide / units_wide), residues below n^2 between them. Row 1 is the largest
+    one: _tile's rolling start makes it the operand of a batch of one."""
+    from tests import wide_cases as W
+    rng = random.Random(f"pinned-{K}-{what}-wide")
+    ws = (W.units_wide if units else W.wide)(n, 2 * K // 32, d - d // 4, rng)
+    low = [n * n - 1, 1, n + 1] + [rng.randrange(2, n * n) | 1 for _ in range(d)]
+    low = [c for c in low if not units or math.gcd(c, n) == 1][:d // 4]
+    out = low[:1] + W.mixed(ws, low[1:])
+    assert len(set(out)) == len(out) == d
+    return out
+
+
 def _pad(edge, draw, d):
     """d values: the first edge, a random one, the other edges, random ones"""
     return (edge[:1] + [draw()] + edge[1:] + [draw() for _ in range(d)])[:d]
@@ -357,6 +386,9 @@ class Child:
         tot, cnt = ctypes.c_double(), ctypes.c_int64()
         self.nat.check(self.nat.lib().xhe_profile_read(label.encode(), ctypes.byref(tot), ctypes.byref(cnt)))
         return cnt.value
+
+    def wide(self, what, units=True):
+        return wide_operands(self.K, self.n, self.d, what, units)
 
     def units(self, count, rng):
         """count residues mod n^2 coprime to n: tests/test_gpu_add_barrett.py's edges that are, then random ones"""
@@ -433,23 +465,36 @@ class Child:
         cw, mw = self.vec(op, self._golden)
         self.report(op, count, self.dk.decrypt_words(_tile(cw, count, count)), _tile(mw, count, count))
 
+    def _arbitrary_wide(self):
+        """any key size: units at and above n^2, the oracle on the unreduced value"""
+        cs = self.wide("arb")
+        ok = self.O.derive_private(self.p, self.q, self.h)
+        ms = [self.O.decrypt_raw(ok, c) for c in cs]
+        assert ms[1] == self.O.decrypt_raw(ok, cs[1] % self.n2) and cs[1] >= self.n2
+        return self.words(cs, self.dk.n2w), self.words(ms, self.dk.nw)
+
+    def op_decrypt_arb_wide(self, op, count, arg):
+        cw, mw = self.vec(op, self._arbitrary_wide)
+        self.report(op, count, self.dk.decrypt_words(_tile(cw, count, count)), _tile(mw, count, count))
+
     def op_decrypt_arb(self, op, count, arg):
         cw, mw = self.vec(op, self._arbitrary)
         self.report(op, count, self.dk.decrypt_words(_tile(cw, count, count)), _tile(mw, count, count))
 
     # ---- mod n^2
-    def _add_vectors(self, gaps):
+    def _add_vectors(self, gaps, wide=False):
         from tests.test_gpu_add_barrett import _edge
         n2, d = self.n2, self.d
         rng = self.rng(f"add-{gaps}")
-        e = []
-        for x in _edge(n2):  # operands stay below n^2: include/xhe.h promises nothing beyond for xhe_mulmod
-            if x % n2 not in e:
-                e.append(x % n2)
+        e = [x for x in _edge(n2) if x < 1 << (32 * self.dk.n2w)]  # (up to 2^4096 - 1: above n^2 at 2048 bits)
         pairs = [(n2 - 1, n2 - 1), (0, n2 - 1), (1, n2 - 2), (n2 // 2, n2 - 1)]
         pairs += [(e[i], e[(5 * i + 3) % len(e)]) for i in range(len(e))]
         pairs += [(rng.randrange(n2), rng.randrange(n2)) for _ in range(d)]
         pairs = pairs[:d - 2] + [(rng.randrange(n2), rng.randrange(n2)) for _ in range(2)]
+        if wide:  # both sides, the left one, the right one at or above n^2
+            x, y = self.wide(f"add-{gaps}-a", units=False), self.wide(f"add-{gaps}-b", units=False)
+            pairs = [(x[i] if i % 3 != 2 else pairs[i][0], y[(5 * i + 3) % d] if i % 3 != 1 else pairs[i][1])
+                     for i in range(d)]
         a, b = [x for x, _ in pairs], [y for _, y in pairs]
         if gaps:
             ea = ([0, -3, 0, -1, -2, -3, -1, 0] + [rng.randrange(-3, 1) for _ in range(d)])[:d]
@@ -464,9 +509,9 @@ class Child:
         w = self.dk.n2w
         return self.words(a, w), self.words(b, w), i32(ea), i32(eb), self.words(want, w)
 
-    def _add(self, op, count, gaps):
+    def _add(self, op, count, gaps, wide=False):
         from xfl_amd.paillier import resident
-        aw, bw, ea, eb, want = self.vec(op, lambda: self._add_vectors(gaps))
+        aw, bw, ea, eb, want = self.vec(op, lambda: self._add_vectors(gaps, wide))
         t = lambda v: _tile(v, count, count)  # noqa: E731
         out = resident.mulmod(self.dk, self.up(t(aw)), t(ea).reshape(-1), self.up(t(bw)), t(eb).reshape(-1),
                               3 if gaps else 0)
@@ -478,17 +523,23 @@ class Child:
     def op_add_gap(self, op, count, arg):
         self._add(op, count, True)
 
-    def _pow_vectors(self, width, inverted):
-        cs, ks, kbits, want = self.vec(f"pow-{width}", lambda: self._pow_ints(width))
+    def op_add_eq_wide(self, op, count, arg):
+        self._add(op, count, False, True)
+
+    def op_add_gap_wide(self, op, count, arg):
+        self._add(op, count, True, True)
+
+    def _pow_vectors(self, width, inverted, wide=False):
+        cs, ks, kbits, want = self.vec(f"pow-{width}-{wide}", lambda: self._pow_ints(width, wide))
         if inverted:
             want = [pow(x, -1, self.n2) for x in want]  # (c^-1)^k
         w = self.dk.n2w
         return self.words(cs, w), self.words(ks, (kbits + 31) // 32), kbits, self.words(want, w)
 
-    def _pow_ints(self, width):
+    def _pow_ints(self, width, wide=False):
         n, n2, d = self.n, self.n2, self.d
         rng = self.rng(f"powmod-{width}")
-        cs = self.units(d, rng)
+        cs = self.wide("powmod") if wide else self.units(d, rng)
         if width == "full":  # tests/test_gpu_ndig.py's exponent edges; k = n - 1 is the full-width one
             kbits = n.bit_length()
             ks = _pad([n - 1, 0, 1, (1 << 53) - 1, 15, 16], lambda: rng.randrange(n), d)
@@ -498,9 +549,9 @@ class Child:
             ks = _pad([top, 0, 1, 15, 16, 1 << (kbits - 1)], lambda: rng.getrandbits(kbits), d)
         return cs, ks, kbits, [pow(c, k, n2) for c, k in zip(cs, ks)]
 
-    def _powmod(self, op, count, width, inverted):
+    def _powmod(self, op, count, width, inverted, wide=False):
         from xfl_amd.paillier import resident
-        cw, kw, kbits, want = self.vec(op, lambda: self._pow_vectors(width, inverted))
+        cw, kw, kbits, want = self.vec(op, lambda: self._pow_vectors(width, inverted, wide))
         out = resident.powmod(self.dk, self.up(_tile(cw, count, count)), _tile(kw, count, count), kbits,
                               invert_first=inverted)
         self.report(op, count, self.down(out), _tile(want, count, count))
@@ -511,15 +562,24 @@ class Child:
     def op_powmod_inv(self, op, count, arg):
         self._powmod(op, count, arg, True)
 
-    def op_invert(self, op, count, arg):
+    def op_powmod_wide(self, op, count, arg):
+        self._powmod(op, count, arg, False, True)
+
+    def op_powmod_inv_wide(self, op, count, arg):
+        self._powmod(op, count, arg, True, True)
+
+    def op_invert(self, op, count, arg, wide=False):
         from xfl_amd.paillier import resident
 
         def make():
-            cs = self.units(self.d, self.rng("invert"))
+            cs = self.wide("invert") if wide else self.units(self.d, self.rng("invert"))
             return self.words(cs, self.dk.n2w), self.words([pow(c, -1, self.n2) for c in cs], self.dk.n2w)
         cw, want = self.vec(op, make)
         out = resident.invert(self.dk, self.up(_tile(cw, count, count)))
         self.report(op, count, self.down(out), _tile(want, count, count))
+
+    def op_invert_wide(self, op, count, arg):
+        self.op_invert(op, count, arg, True)
 
     def _segprod(self, op, count, d, dmax, has_d):
         """out[s] = prod c_i^(2^d_i) over an empty segment, one of length 1 and
@@ -530,7 +590,10 @@ class Child:
 
         from xfl_amd.paillier import resident
         nat, dk, n2 = self.nat, self.dk, self.n2
-        cs = self.vec("segprod-units", lambda: self.units(self.d, self.rng("segprod")))
+        if op.partition(":")[0].endswith("_wide"):
+            cs = self.vec("segprod-wide", lambda: self.wide("segprod", units=False))
+        else:
+            cs = self.vec("segprod-units", lambda: self.units(self.d, self.rng("segprod")))
         cs = [cs[(count + i) % len(cs)] for i in range(count)]
         seg = np.asarray([0, 0] + sorted({1, 1 + (count - 1) // 3, count}), dtype=np.int64)
         assert seg[-1] == count and (seg[2] - seg[1]) == 1
@@ -561,11 +624,19 @@ class Child:
     def op_segprod_nod(self, op, count, arg):  # no exponent array
         self._segprod(op, count, [0] * count, 0, False)
 
-    def op_multiexp(self, op, ncols, arg):
+    op_segprod_wide, op_segprod_eq_wide, op_segprod_nod_wide = op_segprod, op_segprod_eq, op_segprod_nod
+
+    def op_multiexp_wide(self, op, ncols, arg):
+        self.op_multiexp(op, ncols, arg, True)
+
+    def op_multiexp(self, op, ncols, arg, wide=False):
         from xfl_amd.paillier import resident
         nbases, n2, KB = int(arg), self.n2, 60
         rng = self.rng(op)
-        distinct = self.vec("multiexp-units", lambda: self.units(self.d, self.rng("multiexp")))
+        if wide:
+            distinct = self.vec("multiexp-wide", lambda: self.wide("multiexp", units=False))
+        else:
+            distinct = self.vec("multiexp-units", lambda: self.units(self.d, self.rng("multiexp")))
         bases = [distinct[(i + nbases) % len(distinct)] for i in range(nbases)]
         nterms = min(nbases, 40)
         idx = [[rng.randrange(nbases) for _ in range(nterms)] for _ in range(ncols)]

@@ -3,7 +3,8 @@ invert branch, paillier.py:173-187, utils.py:71-76) across the batch sizes
 of its shapes - the whole-block product tree (2048-bit keys, up to 256
 elements, k_wtree_*) and the level-by-level tree of larger batches - against
 Python's pow(c, -1, n^2), with odd sizes (lone children at every level) and
-edge residues; a non-invertible element fails with XHE_ENOINV."""
+edge residues; a non-invertible element fails with XHE_ENOINV, also one at
+or above n^2 (a payload value is not reduced before it gets here)."""
 import random
 
 import numpy as np
@@ -82,3 +83,38 @@ def test_invert_no_inverse_level_tree():
     for i, (c, g) in enumerate(zip(cs, got)):
         assert g == pow(c, -1, n2), i
 
+
+@pytest.mark.parametrize("count", [3, 300, 4200])
+def test_invert_no_inverse_above_n_square(count):
+    """A batch of units at and above n^2 (tests/wide_cases.py) with one operand
+    in the middle whose residue mod n^2 has no inverse - a multiple of p plus
+    q_max n^2, then q_max n^2 itself (residue 0), then n^2 + n: XHE_ENOINV in
+    the whole-block tree and in both shapes of the level tree; the same batch
+    without it inverts to pow(c mod n^2, -1, n^2)."""
+    import torch
+
+    from tests import wide_cases as W
+    from xfl_amd import _native as nat
+    k = load_fixture("paillier_2048_djn.json")["key"]
+    n, p = hx(k["n"]), hx(k["p"])
+    n2 = n * n
+    dk = nat.DeviceKey(2048, n, None, None, None, device=0)
+    L = nat.lib()
+    s = torch.cuda.current_stream().cuda_stream
+    qm = W.q_max(n, dk.n2w)
+    assert qm >= 2
+    units = W.units_wide(n, dk.n2w, 32, random.Random(13))
+    cs = [units[(i + count) % 32] for i in range(count)]
+    for bad in (5 * p + qm * n2, qm * n2, n2 + n):
+        assert bad < 1 << (32 * dk.n2w)
+        row = cs[:count // 2] + [bad] + cs[count // 2 + 1:]
+        dc = torch.from_numpy(nat.ints_to_words(row, dk.n2w).view(np.int32).copy()).cuda()
+        out = torch.empty_like(dc)
+        assert L.xhe_invert(dk.handle, dc.data_ptr(), count, out.data_ptr(), s) == nat.XHE_ENOINV, (count, hex(bad)[:12])
+    dc = torch.from_numpy(nat.ints_to_words(cs, dk.n2w).view(np.int32).copy()).cuda()
+    out = torch.empty_like(dc)
+    nat.check(L.xhe_invert(dk.handle, dc.data_ptr(), count, out.data_ptr(), s), "invert")
+    torch.cuda.synchronize()
+    got = nat.words_to_ints(out.cpu().numpy().view(np.uint32))
+    want = {c: pow(c, -1, n2) for c in units}
+    assert [want[c] for c in cs] == got

@@ -10,6 +10,7 @@ be the literal decision the case names, and without any, where it must be
 another one. The switch names are held against parse_pins and INTEGRATION.md,
 so a misspelt name (which the library would silently ignore) fails here.
 """
+import math
 import os
 import re
 
@@ -94,8 +95,71 @@ def test_table_is_well_formed():
         assert case["key"][0] in PC.FIXTURE and case["key"][1] in ("priv_djn", "priv_nodjn", "pub_djn", "pub_nodjn")
         K = int(case["key"][0].split("-")[0])
         assert all(f"K={K}" in row[0] for row in case["paths"] if " K=" in row[0]), case["name"]
-        if K == 8192:  # golden vectors only, tiled to at most 5
-            assert all(op == "decrypt_golden" and count <= 5 for op, count in lines), case["name"]
+        if K == 8192:  # the golden vectors and the 5 wide units, tiled to at most 5
+            assert all(op in ("decrypt_golden", "decrypt_arb_wide") and count <= 5 for op, count in lines), case["name"]
+
+
+def test_every_narrow_operation_has_its_wide_twin():
+    """a case that runs an operation on residues below n^2 runs it on operands
+    at and above n^2 too, at the same counts; decrypt_arb_wide also where the
+    2048-bit-only decrypt_arb is not: in every case that decrypts"""
+    twins = set(PC.WIDE_TWIN.values())
+    assert all(t.partition(":")[0] in PC.OPS and t.partition(":")[0].endswith("_wide") for t in twins)
+    seen = set()
+    for case in PC.CASES:
+        ops = {}
+        for op, counts in case["ops"]:
+            ops.setdefault(op, set()).update(counts)
+        for op, counts in ops.items():
+            if op in PC.WIDE_TWIN:
+                assert ops.get(PC.WIDE_TWIN[op]) == counts, (case["name"], op)
+                seen.add(PC.WIDE_TWIN[op])
+            elif op in twins:
+                narrow = [k for k, v in PC.WIDE_TWIN.items() if v == op]
+                assert any(ops.get(k) == counts for k in narrow) or op == "decrypt_arb_wide", (case["name"], op)
+        if "decrypt_golden" in ops:
+            assert ops.get("decrypt_arb_wide") == ops["decrypt_golden"], case["name"]
+    assert seen == twins, twins - seen
+
+
+@pytest.mark.parametrize("K", sorted(PC.DISTINCT))
+def test_wide_rows_are_wide(K):
+    """no (wide operation, count) of the table compares only residues below
+    n^2: of the rows a count tiles (tests/pinned_cases.py _tile, start = count;
+    segprod and multiexp roll the same way), one at least holds an operand at
+    or above n^2 - a batch of one the largest value the words hold"""
+    import random
+
+    from tests import wide_cases as W
+    fx = {2048: "golden-2048-nodjn", 3072: "golden-3072", 4096: "golden-4096", 8192: "golden-8192"}[K]
+    _, n, _, _, _ = W.key(fx)
+    n2, d = n * n, PC.DISTINCT[K]
+    counts = set()
+    for case in PC.CASES:
+        if int(case["key"][0].split("-")[0]) == K:
+            counts |= {c for op, cs in case["ops"] if op in PC.WIDE_TWIN.values() for c in cs}
+    assert counts
+    for units in (True, False):
+        ops = PC.wide_operands(K, n, d, "host", units)
+        assert len(ops) == d and 4 * sum(c >= n2 for c in ops) >= 3 * (d - d // 4)
+        top = 1 << (2 * K)  # n2w = 2 K / 32 words
+        assert all(c < top for c in ops) and ops[1] >= top - 2, "row 1: a batch of one"
+        assert all(c % n2 != W.truncated(c, n) for c in ops if c >= n2)
+        if units:
+            assert all(math.gcd(c % n2, n) == 1 for c in ops)
+        else:
+            assert W.q_max(n, 2 * K // 32) * n2 in ops
+        for count in sorted(counts):
+            rows = [ops[(count + i) % d] for i in range(min(count, d))]
+            assert any(c >= n2 for c in rows), (count, units)
+    assert random.Random(f"pinned-{K}-x-wide").random() != random.Random(f"pinned-{K}-y-wide").random()
+
+
+def test_add_operands_are_not_reduced():
+    """the Barrett edge list of the narrow adds keeps its operands above n^2"""
+    import inspect
+    src = inspect.getsource(PC.Child._add_vectors)
+    assert "% n2" not in src.split("want = []")[0]
 
 
 def test_switch_names():

@@ -381,7 +381,11 @@ class NDigits(MontDigits):
 
     def to_digits(self, x, ctr):
         t, m = self.redc(x + self.Kn2, 2 * self.k + 1, ctr)
-        assert self.P <= t < 2 * self.P + 2, "REDC(x + Kn2) left [n, 2n]"
+        # R t = x + Kn2 + m n with Kn2 < R n + n^2 and m < R: t < 2n + (x + n^2) / R. R >= 2^13 n, so for any x
+        # the 2K words of a ciphertext hold (x < 64 n^2 on the sparsest modulus: (x + n^2) / R < 65 n / 2^13) the
+        # first digit t - n stays below n + n / 100, inside the 2n of the state bound
+        assert self.P <= t <= 2 * self.P + (x + self.P * self.P) // self.R, "REDC(x + Kn2) left [n, 2n + (x + n^2)/R]"
+        assert t - self.P < 2 * self.P
         return self.mul((t - self.P, self.R - m), self.w, ctr)
 
     def from_digits(self, a, c, ctr):

@@ -1546,9 +1546,12 @@ XHE_DEV void pmdx_row_to_tab(const uint2* __restrict__ row, uint2* tab, int t, i
   for (int j = 0; j < D::L; ++j) p[(size_t)j * gs] = row[g * D::L + j];
 }
 
-// plain x (2K limbs lo | hi, W-bit, < n^2) -> its digits (a, c):
+// plain x (2K limbs lo | hi, W-bit; any value the ciphertext words hold, not
+// only x < n^2: include/xhe.h) -> its digits (a, c):
 //   X = x + ceil(R/n) n^2 (kn2, 2K limbs), REDC(X): X + m n = R t with t in
-//   [n, 2n]; (t - n, R - m) are the digits of x R^-2 (R (t - n) + n (R - m) =
+//   [n, 2n + (x + n^2)/R] - R >= 2^13 n, so t - n < n + n/100 < 2n, the state
+//   bound of the products, for every such x (tools/pdigit_model.py asserts
+//   it); (t - n, R - m) are the digits of x R^-2 (R (t - n) + n (R - m) =
 //   X - R n + n R ... = R t - n m = X = x mod n^2); one product by the digits
 //   of R^2 mod n^2 (dw) gives x's. (tools/pdigit_model.py NDigits.to_digits)
 template <class D>

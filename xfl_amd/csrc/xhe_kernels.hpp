@@ -1789,7 +1789,9 @@ __global__ void __launch_bounds__(256, 2) k_mulmod_n2(KeyDev key, const uint32_t
   const uint32_t* xw = (xb ? bw : a) + (size_t)e * key.n2w;
   const uint32_t* yw = (xb ? a : bw) + (size_t)e * key.n2w;
   uint32_t b[MN2::L];
-  // y as plain limbs, parked in `row` (c < n^2, so no reduction is needed)
+  // y as plain limbs, parked in `row`, unreduced: any value the n2w words hold (include/xhe.h). y < 2^(32 n2w)
+  // <= R / 256 in every MN2 shape, so the closing product x^(2^d) R * y / R stays below 2 n^2 like any other
+  // and reduce_once finishes it; x enters through a product by R^2 mod n^2, which reduces it the same way
   M.load_words(b, yw, key.n2w);
   M.store_strided(b, row, st);
   M.load_words(b, xw, key.n2w);
