@@ -11,9 +11,10 @@
  * gives the thread-local message. A key handle is immutable after creation
  * and may be shared between threads; calls on distinct streams are reentrant.
  *
- * Ciphertext operands: the seven entry points that read ciphertext words -
- * xhe_decrypt, xhe_mulmod, xhe_powmod, xhe_pack, xhe_invert, xhe_segprod and
- * xhe_multiexp (and their _host variants) - accept ANY value in [0, 2^(32 n2w))
+ * Ciphertext operands: the eight entry points that read ciphertext words -
+ * xhe_decrypt, xhe_mulmod, xhe_powmod, xhe_pack, xhe_invert, xhe_segprod,
+ * xhe_segscan and xhe_multiexp (and their _host variants) - accept ANY value in
+ * [0, 2^(32 n2w))
  * in an operand row, not only residues below n^2: a received payload is not
  * reduced on its way into a device array (xhe_wire_decode, xhe_wire_scan and
  * xhe_wire_unpack reject or cut only what is wider than n2w words). The result
@@ -197,6 +198,18 @@ int xhe_invert(const xhe_key* key, const uint32_t* c_dev, int64_t count, uint32_
 int xhe_segprod(const xhe_key* key, const uint32_t* c_dev, const int32_t* d_dev, int dmax, int64_t count,
                 const int64_t* seg_begin, int64_t nseg, uint32_t* out_dev, void* stream);
 
+/* Inclusive prefix products per segment (np.cumsum / Series.cumsum over
+ * ciphertexts of one exponent: the left fold of paillier.py:106-123,153-154):
+ * out[i] = prod_{seg_begin[s] <= j <= i} c_j mod n^2 for i in segment s.
+ * seg_begin is a HOST array of nseg+1 offsets as in xhe_segprod (seg_begin[0]
+ * == 0, seg_begin[nseg] == count, non-decreasing, else XHE_EINVAL); an empty
+ * segment produces nothing, count == 0 writes nothing. out (count rows) must
+ * not overlap c in any way (XHE_EINVAL). There is no exponent argument: the
+ * scan is defined for rows of one exponent, which the caller ensures. Needs no
+ * private key. c: any values below 2^(32 n2w), taken mod n^2; out < n^2. */
+int xhe_segscan(const xhe_key* key, const uint32_t* c_dev, int64_t count, const int64_t* seg_begin, int64_t nseg,
+                uint32_t* out_dev, void* stream);
+
 /* Encrypted matrix-vector product as a multi-exponentiation: the object-dtype
  * np.matmul(enc[B], X[B, D]) of logistic_regression/trainer.py:166 (and
  * linear_regression/trainer.py:207, poisson_regression/trainer.py:267,
@@ -252,6 +265,8 @@ int xhe_multiexp_host(const xhe_key* key, const uint32_t* bases, int64_t nbases,
                       int kw, int kbits, int64_t ncols, int64_t nterms, int win_bits, uint32_t* out);
 int xhe_segprod_host(const xhe_key* key, const uint32_t* c, const int32_t* d, int dmax, int64_t count,
                      const int64_t* seg_begin, int64_t nseg, uint32_t* out);
+int xhe_segscan_host(const xhe_key* key, const uint32_t* c, int64_t count, const int64_t* seg_begin, int64_t nseg,
+                     uint32_t* out);
 /* xhe_pack: count ciphertexts in, ceil(count/k) out. */
 int xhe_pack_host(const xhe_key* key, const uint32_t* c, int64_t count, int k, int shift_bits, uint32_t* out);
 int xhe_mulmod_host(const xhe_key* key, const uint32_t* a, const int32_t* ea, const uint32_t* b, const int32_t* eb,

@@ -26,7 +26,7 @@ LIB = os.path.join(HERE, "lib", "libxhe.so")
 OBJ = os.path.join(HERE, "lib", "obj")
 HEADER = os.path.join(ROOT, "include", "xhe.h")
 DEVICE_DEPS = [os.path.join(CSRC, f) for f in ("xhe.hip", "xhe_kernels.hpp", "bn_dev.hpp", "fermat_dev.hpp", "pdigit_dev.hpp", "dec_wave.hpp", "barrett_dev.hpp", "rns_dev.hpp", "enc_obf_dev.hpp", "wire_unpack.hpp", "hostbn.hpp",
-                                               "keydev.hpp", "keyconst.hpp", "paths.hpp", "rns_layout.hpp", "abi_common.hpp")] + [HEADER]
+                                               "keydev.hpp", "keyconst.hpp", "paths.hpp", "scan_plan.hpp", "rns_layout.hpp", "abi_common.hpp")] + [HEADER]
 HOST_DEPS = [os.path.join(CSRC, f) for f in ("wire_abi.cpp", "wire.hpp", "abi_common.hpp")] + [HEADER]
 SOURCES = sorted(set(DEVICE_DEPS + HOST_DEPS))
 HIPCC = os.environ.get("HIPCC", "/opt/rocm/bin/hipcc")

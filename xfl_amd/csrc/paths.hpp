@@ -145,6 +145,8 @@ inline EncNoDjn enc_nodjn(int K, bool priv, bool ndig, int64_t count, const Pins
 // chain of dependent products sets the time), the batch shape beyond (4 lanes
 // at 2048 and 3072 bits). $XHE_N2_TPI (4 or 16) pins one shape (A/B
 // measurement). Multiexp passes max(nbases, ncols).
+// (xhe_segscan takes this shape too; its chunks and levels are planned in
+// scan_plan.hpp, a pure header like this one.)
 enum class N2Shape { ROW16, LANES4 };
 constexpr int64_t kN2RowMax = 4096;
 

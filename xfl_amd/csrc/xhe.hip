@@ -22,6 +22,7 @@
 #include "hostbn.hpp"
 #include "keyconst.hpp"
 #include "paths.hpp"
+#include "scan_plan.hpp"
 #include "xhe_kernels.hpp"
 #include "fermat_dev.hpp"
 #include "dec_wave.hpp"
@@ -1309,6 +1310,53 @@ void segprod_impl(const xhe_key* k, const uint32_t* c, const int32_t* d, int dma
   launch(k_from_mont_rows<MN2>, blocks(nseg), dim3(256), s, k->kd, n2h<MN2>(k).N, cur.as<uint32_t>(), nseg, out);
 }
 
+// Segmented inclusive prefix products: out[i] = prod of its segment's elements
+// up to i (scan_plan.hpp). Down the levels a chunk pass each - level 0 reads
+// the ciphertext words, the levels above scan the Montgomery rows of the chunk
+// totals in place - then back up an apply pass each, which multiplies in the
+// carries from the level above and leaves the level plain; the last one packs
+// `out`. Per element one product on the chain and two off it (one in a
+// segment's first chunk), plus 2 + 1/C per chunk for the levels above. Every
+// level keeps its rows ([rows][S4] limbs) and a chunk index per row for the
+// call; one plan upload, no host sync.
+static_assert(scan::kChunkLen + 1 < kRpowRows, "a chunk's fix-up rows: R^(u+2) for u < kChunkLen");
+template <class Sh, class MN2 = typename Sh::MN2>
+void segscan_impl(const xhe_key* k, const uint32_t* c, int64_t count, const int64_t* seg_begin_host, int64_t nseg,
+                  uint32_t* out, hipStream_t s) {
+  constexpr int PW = Sh::RW2;
+  const scan::Plan plan = scan::make_plan(seg_begin_host, nseg, scan::chunk_len(count));
+  const size_t nl = plan.levels.size();
+  auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
+  DevBuf dplan_(plan.chunks.size() * 8, s, DevBuf::kAsync);
+  host_stage().upload(dplan_.p, plan.chunks.data(), plan.chunks.size() * 8, s, k->device);  // no host sync
+  std::vector<DevBuf> rows(nl), cid(nl);
+  for (size_t l = 0; l < nl; ++l) {
+    rows[l] = DevBuf((size_t)MN2::S4 * plan.levels[l].rows * 4, s, DevBuf::kAsync);
+    cid[l] = DevBuf((size_t)plan.levels[l].rows * 4, s, DevBuf::kAsync);
+  }
+  auto lplan = [&](size_t l) { return dplan_.as<int64_t>() + (size_t)plan.levels[l].chunk0 * scan::kFields; };
+  auto above = [&](size_t l) { return l + 1 < nl ? rows[l + 1].as<uint32_t>() : nullptr; };
+  ProfScope ps("k_segscan", s);
+  for (size_t l = 0; l < nl; ++l) {
+    const scan::Level& L = plan.levels[l];
+    if (l == 0)
+      launch((k_segscan_chunk<MN2, PW, true>), blocks(L.nchunks), dim3(256), s, k->kd, n2h<MN2>(k).N, c,
+             rows[l].as<uint32_t>(), lplan(l), L.nchunks, cid[l].as<int32_t>(), above(l));
+    else
+      launch((k_segscan_chunk<MN2, PW, false>), blocks(L.nchunks), dim3(256), s, k->kd, n2h<MN2>(k).N, nullptr,
+             rows[l].as<uint32_t>(), lplan(l), L.nchunks, cid[l].as<int32_t>(), above(l));
+  }
+  for (size_t l = nl; l-- > 0;) {
+    const scan::Level& L = plan.levels[l];
+    if (l == 0)
+      launch((k_segscan_apply<MN2, PW, true>), blocks(L.rows), dim3(256), s, k->kd, n2h<MN2>(k).N, out,
+             rows[l].as<uint32_t>(), L.rows, lplan(l), cid[l].as<int32_t>(), above(l));
+    else
+      launch((k_segscan_apply<MN2, PW, false>), blocks(L.rows), dim3(256), s, k->kd, n2h<MN2>(k).N, nullptr,
+             rows[l].as<uint32_t>(), L.rows, lplan(l), cid[l].as<int32_t>(), above(l));
+  }
+}
+
 // Window bits for a multi-exponentiation: minimise table products
 // nbases*(2^c - 2) plus gathered products ncols*nterms*ceil(kbits/c), with the
 // tables capped at ~2 GiB.
@@ -1552,6 +1600,37 @@ int xhe_segprod(const xhe_key* key, const uint32_t* c_dev, const int32_t* d_dev,
       using Sh = decltype(sh);
       if (row) segprod_impl<Sh, typename Sh::MN2X>(key, c_dev, d_dev, dmax, count, seg_begin, nseg, out_dev, hs);
       else segprod_impl<Sh>(key, c_dev, d_dev, dmax, count, seg_begin, nseg, out_dev, hs);
+    });
+    return XHE_OK;
+  });
+}
+
+namespace {
+int segscan_args(const xhe_key* key, const uint32_t* c, int64_t count, const int64_t* seg_begin, int64_t nseg,
+                 const uint32_t* out, const char* who) {
+  if (!key || !seg_begin || nseg <= 0 || count < 0 || (count > 0 && (!c || !out)))
+    return fail(XHE_EINVAL, std::string(who) + ": bad argument");
+  if (seg_begin[0] != 0 || seg_begin[nseg] != count) return fail(XHE_EINVAL, std::string(who) + ": bad segment offsets");
+  for (int64_t i = 0; i < nseg; ++i)
+    if (seg_begin[i + 1] < seg_begin[i]) return fail(XHE_EINVAL, std::string(who) + ": offsets must be non-decreasing");
+  if (count > 0 && out < c + (size_t)count * key->n2w && c < out + (size_t)count * key->n2w)
+    return fail(XHE_EINVAL, std::string(who) + ": out overlaps c");
+  return XHE_OK;
+}
+}  // namespace
+
+int xhe_segscan(const xhe_key* key, const uint32_t* c_dev, int64_t count, const int64_t* seg_begin, int64_t nseg,
+                uint32_t* out_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (int rc = segscan_args(key, c_dev, count, seg_begin, nseg, out_dev, "xhe_segscan")) return rc;
+    if (count == 0) return XHE_OK;
+    DevGuard dg(key->device);
+    const bool row = paths::n2_shape(count, pins()) == paths::N2Shape::ROW16;
+    hipStream_t hs = (hipStream_t)stream;
+    with_shape(key->K, [&](auto sh) {
+      using Sh = decltype(sh);
+      if (row) segscan_impl<Sh, typename Sh::MN2X>(key, c_dev, count, seg_begin, nseg, out_dev, hs);
+      else segscan_impl<Sh>(key, c_dev, count, seg_begin, nseg, out_dev, hs);
     });
     return XHE_OK;
   });
@@ -2540,6 +2619,24 @@ int xhe_segprod_host(const xhe_key* key, const uint32_t* c, const int32_t* d, in
                          dout.as<uint32_t>(), st.s);
     if (rc != XHE_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)nseg * key->n2w * 4, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    return XHE_OK;
+  });
+}
+
+int xhe_segscan_host(const xhe_key* key, const uint32_t* c, int64_t count, const int64_t* seg_begin, int64_t nseg,
+                     uint32_t* out) {
+  return guarded([&]() -> int {
+    if (int rc = segscan_args(key, c, count, seg_begin, nseg, out, "xhe_segscan_host")) return rc;
+    if (count == 0) return XHE_OK;
+    DevGuard dg(key->device);
+    const size_t bytes = (size_t)count * key->n2w * 4;
+    Stream st;
+    DevBuf dc(bytes, st.s), dout(bytes, st.s);
+    HIPCHK(hipMemcpyAsync(dc.p, c, bytes, hipMemcpyHostToDevice, st.s));
+    int rc = xhe_segscan(key, dc.as<uint32_t>(), count, seg_begin, nseg, dout.as<uint32_t>(), st.s);
+    if (rc != XHE_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, bytes, hipMemcpyDeviceToHost, st.s));
     HIPCHK(hipStreamSynchronize(st.s));
     return XHE_OK;
   });

@@ -2346,6 +2346,128 @@ __global__ void __launch_bounds__(256, 2) k_chunk_prod_words(KeyDev key, const u
   M.store_strided(b, outp + j, (int)n_out);
 }
 
+// ---- cumulative sums: segmented inclusive prefix products (xhe_segscan)
+// Chunk pass of one level (plan: scan_plan.hpp, 4 int64 per chunk). Lane
+// group j walks the `len` consecutive rows of chunk j, one product per row,
+// and parks every row's chain state in the level's rows ([n][S4] limbs, row-
+// major: a lane group reads and writes whole rows); the fix-up and the carry
+// are k_segscan_apply's, off the chain. Unlike the reduction's chunks these
+// cannot be interleaved over the segment - a prefix needs its rows in order -
+// so neighbouring groups are a chunk apart here, and it is the apply pass
+// whose neighbouring groups take neighbouring rows (whole rows through ARow:
+// with column-major rows and strided operands the 57-limb shape spilled
+// hundreds of registers; 1 M elements run at 3.07 adds per element for 3.2
+// products per element, DESIGN "Cumulative sums"). The chain is not reduced:
+// its states stay below 2 n^2, which a product accepts on either side.
+// RAW (level 0): the inputs are ciphertext words ([n][PW], any value the
+// words hold, unpacked where they are used). Row u's state is P_u R^-u (P_u =
+// c_0 .. c_u; the chain starts from R, so the first product leaves c_0 mod
+// n^2). The chunk's total goes up as the Montgomery row P R, by one product
+// with R^(len+1).
+// !RAW: the inputs are the level's own rows, the Montgomery totals of the
+// level below, scanned in place: a chain of Montgomery rows stays in
+// Montgomery form, and the last state is the total.
+// cid[row] = j tells the apply pass which chunk a row belongs to.
+// Blocks per CU the scan kernels are compiled for: 2, as the other n^2 kernels,
+// except where a lane holds more than 48 limbs (the 3072-bit 4-lane shape, 57):
+// b, the 64-bit accumulators and the modulus limbs alone are 228 registers
+// there, and at 2 blocks (256 registers) the chain's loop spilled 9 VGPRs and
+// 48 SGPRs; at 1 block nothing spills.
+template <class MN2>
+constexpr int scan_waves() {
+  return MN2::L > 48 ? 1 : 2;
+}
+template <class MN2, int PW, bool RAW>
+__global__ void __launch_bounds__(256, scan_waves<MN2>()) k_segscan_chunk(KeyDev key, const uint32_t* __restrict__ Nn2,
+                                                          const uint32_t* __restrict__ words, uint32_t* rows,
+                                                          const int64_t* __restrict__ plan, int64_t nchunks,
+                                                          int32_t* __restrict__ cid, uint32_t* __restrict__ tot) {
+  const int64_t j = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MN2::TPI;
+  if (j >= nchunks) return;
+  const int64_t first = plan[4 * j];
+  const int len = (int)plan[4 * j + 1];
+  const int64_t total = plan[4 * j + 2];
+  const bool lead = MN2::G::g() == 0;
+  MN2 M;
+  M.init(Nn2, n2dev<MN2>(key).n0inv);
+  uint32_t b[MN2::L];
+  uint32_t* row = rows + (size_t)first * MN2::S4;
+  int32_t* id = cid + first;
+  if constexpr (RAW) {
+    // from R: the first product is c_0 R / R, and every row takes the same steps
+    const uint32_t* w = words + (size_t)first * PW;
+    M.load_row(b, n2dev<MN2>(key).Rpow + (size_t)MN2::S4);
+#pragma unroll 1
+    for (int u = 0; u < len; ++u, w += PW, row += MN2::S4) {
+      M.mul(b, ARowPacked<MN2::W, PW>{w});
+      __builtin_amdgcn_sched_barrier(0);
+      M.store_row(b, row);
+      if (lead) id[u] = (int32_t)j;
+    }
+  } else {
+    M.load_row(b, row);
+    if (lead) id[0] = (int32_t)j;
+#pragma unroll 1
+    for (int u = 1; u < len; ++u) {
+      row += MN2::S4;
+      M.mul(b, ARow{row});
+      __builtin_amdgcn_sched_barrier(0);
+      M.store_row(b, row);  // (below 2 n^2, as the chain keeps it: the apply pass reduces)
+      if (lead) id[u] = (int32_t)j;
+    }
+  }
+  if (total < 0) return;  // a one-chunk segment sends nothing up
+  if constexpr (RAW) {
+    M.mul(b, ARow{n2dev<MN2>(key).Rpow + (size_t)(len + 1) * MN2::S4});
+    M.reduce_once(b);
+  }
+  M.store_row(b, tot + (size_t)total * MN2::S4);
+}
+
+// Apply pass of one level, one lane group per row e of chunk j = cid[e], row
+// u of its chunk: the row's state times the carry - the scanned (plain) row
+// `carry` of the level above `up`, the inclusive total of the chunks before
+// j in the segment - leaves the row plain and below n^2:
+//   level 0 (WORDS):  R^(u+1) * P_u R^-u / R = P_u               (first chunk)
+//                     T * R^(u+2) / R * P_u R^-u / R = T P_u     (carry T)
+//     packed into the output words;
+//   above:            P R * 1 / R = P,   P R * T / R = P T   in place (the
+//     row of R^0 is the operand 1: one product either way).
+template <class MN2, int PW, bool WORDS>
+__global__ void __launch_bounds__(256, scan_waves<MN2>()) k_segscan_apply(KeyDev key, const uint32_t* __restrict__ Nn2,
+                                                          uint32_t* __restrict__ words, uint32_t* rows, int64_t n,
+                                                          const int64_t* __restrict__ plan,
+                                                          const int32_t* __restrict__ cid,
+                                                          const uint32_t* __restrict__ up) {
+  const int64_t e = ((int64_t)blockIdx.x * blockDim.x + threadIdx.x) / MN2::TPI;
+  if (e >= n) return;
+  const int64_t j = cid[e];
+  const int64_t u = e - plan[4 * j], carry = plan[4 * j + 3];
+  MN2 M;
+  M.init(Nn2, n2dev<MN2>(key).n0inv);
+  uint32_t b[MN2::L];
+  const uint32_t* rp = n2dev<MN2>(key).Rpow;
+  if constexpr (WORDS) {
+    if (carry >= 0) {
+      M.load_row(b, up + (size_t)carry * MN2::S4);
+      M.mul(b, ARow{rp + (size_t)(u + 2) * MN2::S4});
+    } else {
+      M.load_row(b, rp + (size_t)(u + 1) * MN2::S4);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    M.mul(b, ARow{rows + (size_t)e * MN2::S4});
+    __builtin_amdgcn_sched_barrier(0);
+    M.reduce_once(b);
+    M.store_words(b, words + (size_t)e * PW, PW);
+  } else {
+    uint32_t* row = rows + (size_t)e * MN2::S4;
+    M.load_row(b, row);
+    M.mul(b, ARow{carry >= 0 ? up + (size_t)carry * MN2::S4 : rp});
+    M.reduce_once(b);
+    M.store_row(b, row);
+  }
+}
+
 // ---- batch modular inversion mod n^2 (Montgomery's trick as a product tree)
 // Up-sweep: out[i] = in[2i] * in[2i+1] (Montgomery form, rows [S4][n]).
 template <class MN2>

@@ -590,6 +590,29 @@ class PaillierArray(_EABase):
                                                    initial=initial, where=where))
         return _sum(self, axis, keepdims)
 
+    def cumsum(self, axis=None, dtype=None, out=None):
+        """ndarray.cumsum: the inclusive prefix sums along `axis` (None: over
+        the flattened array), one segmented scan (xhe_segscan) when every scan
+        line has a single exponent; else the reference's object left fold."""
+        try:
+            return _f_cumsum(self, axis=axis, dtype=dtype, out=out)
+        except _Fallback:
+            return _obj_call(np.cumsum, (self,), dict(axis=axis, dtype=dtype, out=out))
+
+    def _accumulate(self, name, *, skipna=True, **kwargs):
+        """Series.cumsum() over a ciphertext column. With missing entries
+        pandas' own object path runs, so NaN stands where the reference's
+        object column has it; other accumulations stay unsupported."""
+        if name != "cumsum":
+            if _EABase is object:
+                raise NotImplementedError(f"cannot perform {name} with type {self.dtype}")
+            return super()._accumulate(name, skipna=skipna, **kwargs)
+        if self._has_na():
+            import pandas as pd
+            res = pd.Series(np.asarray(self), dtype=object).cumsum(skipna=skipna)
+            return type(self)._from_sequence(res.to_numpy(dtype=object))
+        return self.cumsum()
+
     # ------------------------------------------------------------ operators
     def __add__(self, other):
         return _dispatch(_add, self, other, np.add)
@@ -1153,6 +1176,61 @@ def _f_sum(a, axis=None, dtype=None, out=None, keepdims=False, initial=None, whe
     return _sum(c, axis, keepdims)
 
 
+def _scan_segments(x, seg):
+    """Inclusive prefix sums of the consecutive segments of the 1-D x (seg:
+    int64 offsets) in one xhe_segscan call -> 1-D PaillierArray with x's
+    exponents, in HBM when the scan ran there. A prefix sum of ciphertexts of
+    one exponent is the prefix product of the residues (paillier.py:106-123,
+    no alignment); any other input is the caller's object fold: _Fallback.
+    Wherever the context has a resident device the scan runs there: a host
+    input of any size is uploaded (there is no SMALL threshold - as in
+    _groupby_op, whose two conditions together send every size to the device)
+    and the result stays in HBM; without one, ops.segscan_words."""
+    if x.context is None or x.size == 0 or x._has_na():
+        raise _Fallback()
+    ctx = x.context
+    e = x._e
+    seg = np.ascontiguousarray(seg, dtype=np.int64)
+    first = np.repeat(e[np.minimum(seg[:-1], x.size - 1)], np.diff(seg))
+    if not np.array_equal(first, e):
+        raise _Fallback()  # two exponents inside one scan line
+    n2w = ops.n2w_of(ctx)
+    x = x._aligned_words(n2w)
+    dev = resident.device_for(ctx, -1, x.size, 4 * n2w)
+    if dev is not None:
+        rd = ops.segscan_dev(ctx, ctx.device_key(dev), x._dw(dev), seg)
+        return PaillierArray.from_device(ctx, rd, e.copy(), (x.size,))
+    return _result(ctx, ops.segscan_words(ctx, x._w, seg), e.copy(), (x.size,))
+
+
+def _cumsum(x, axis=None):
+    """np.cumsum over ciphertexts: numpy's add.accumulate over an object array
+    is a left fold along the axis, here one segment per scan line."""
+    if x.ndim == 0 or x.size == 0:
+        raise _Fallback()
+    if axis is None:
+        return _scan_segments(x.reshape(-1), np.array([0, x.size], dtype=np.int64))
+    if not isinstance(axis, (int, np.integer)) or not -x.ndim <= axis < x.ndim:
+        raise _Fallback()  # numpy raises its own error
+    ax = int(axis) % x.ndim
+    keep = [d for d in range(x.ndim) if d != ax]
+    order = x._index_map().transpose(keep + [ax]).reshape(-1)
+    seglen = x.shape[ax]
+    seg = np.arange(x.size // seglen + 1, dtype=np.int64) * seglen
+    if _identity(order, x.size):
+        return _scan_segments(x.reshape(-1), seg).reshape(x.shape)
+    back = np.empty_like(order)
+    back[order] = np.arange(x.size, dtype=np.int64)
+    return _scan_segments(x._take(order, (x.size,)), seg)._take(back, x.shape)
+
+
+def _f_cumsum(a, axis=None, dtype=None, out=None):
+    c = _as_cipher(a)
+    if c is None or out is not None or dtype not in (None, object):
+        raise _Fallback()
+    return _cumsum(c, axis)
+
+
 def _f_concatenate(arrays, axis=0, out=None, dtype=None, casting="same_kind"):
     if out is not None or dtype not in (None, object):
         raise _Fallback()
@@ -1359,7 +1437,7 @@ def _shifted_words(k, shift):
 
 _UFUNCS = {np.add: _add, np.subtract: _sub, np.multiply: _mul, np.true_divide: _div, np.matmul: _matmul,
            np.negative: lambda a: _mul(a, -1)}
-_FUNCS = {np.sum: _f_sum, np.concatenate: _f_concatenate, np.reshape: _f_reshape, np.ravel: _f_ravel,
+_FUNCS = {np.sum: _f_sum, np.cumsum: _f_cumsum, np.concatenate: _f_concatenate, np.reshape: _f_reshape, np.ravel: _f_ravel,
           np.shape: _f_shape, np.ndim: _f_ndim, np.size: _f_size, np.copy: _f_copy, np.transpose: _f_transpose,
           np.matmul: lambda a, b, **kw: _dispatch(_matmul, a, b, np.matmul) if not kw else _obj_call(np.matmul, (a, b), kw),
           np.dot: lambda a, b, out=None: _dispatch(_matmul, a, b, np.dot) if out is None else _obj_call(np.dot, (a, b), {"out": out}),

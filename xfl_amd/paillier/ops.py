@@ -449,6 +449,26 @@ def segprod_words(ctx, cw, d, seg):
     return out
 
 
+def segscan_words(ctx, cw, seg):
+    """out[i] = prod_{seg[s] <= j <= i} c_j mod n^2 for i in segment s: the
+    inclusive prefix products of every segment in one xhe_segscan call (int64
+    seg offsets; rows of one exponent per segment, which the caller ensures)."""
+    cw = _u32(cw)
+    n = cw.shape[0]
+    seg = np.ascontiguousarray(seg, dtype=np.int64)
+    out = np.empty((n, n2w_of(ctx)), dtype=np.uint32)
+    if n:
+        dk = ctx.device_key(ctx.own_device())
+        nat.check(nat.lib().xhe_segscan_host(dk.handle, _vp(cw), n, _vp(seg), seg.shape[0] - 1, _vp(out)), "segscan")
+    return out
+
+
+def segscan_dev(ctx, dk, cd, seg):
+    """segscan_words on device words -> device [count, n2w]"""
+    from . import resident
+    return resident.segscan(dk, cd, seg)
+
+
 def multiexp_words(ctx, bw, idx, kw_, kbits, win_bits=0):
     """out[j] = prod_t bases[idx[j][t]]^k[j][t] mod n^2 (k >= 0, [ncols,
     nterms, kw] words): one xhe_multiexp call (Straus windows, per-base tables

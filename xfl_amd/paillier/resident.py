@@ -727,6 +727,22 @@ def segprod(dk, c, d, seg):
     return out
 
 
+def segscan(dk, c, seg):
+    """out[i] = prod of segment s's rows up to i mod n^2 (device c; host int64
+    offsets) -> device [count, n2w] (xhe_segscan)"""
+    torch = _torch()
+    dev = dk.device
+    n = c.shape[0]
+    seg = np.ascontiguousarray(seg, dtype=np.int64)
+    with _On(dev):
+        out = torch.empty((n, dk.n2w), dtype=torch.int32, device=f"cuda:{dev}")
+        src = c.contiguous()
+    if n:
+        nat.check(nat.lib().xhe_segscan(dk.handle, _dp(src), n, seg.ctypes.data_as(ctypes.c_void_p), seg.shape[0] - 1,
+                                        _dp(out), _sp(dev)), "segscan")
+    return out
+
+
 def multiexp(dk, bases, idx, kw_, kbits, win_bits=0):
     """out[j] = prod_t bases[idx[j][t]]^k[j][t] mod n^2 on device bases; idx
     and k host arrays (validated here: the device entry point trusts them)"""

@@ -230,6 +230,48 @@ def pack_ciphertexts(arr, num: int = 2, interval: int = (1 << 128), k: int = Non
     return PaillierArray.from_buffers(context, ops.pack_words(context, arr.words, k, shift), exps)
 
 
+def cumsum_segments(arr, lengths):
+    """Cumulative sums of consecutive runs of a 1-D ciphertext array: the run
+    of lengths[i] elements after the runs before it is scanned on its own
+    (np.cumsum of that slice), all runs in ONE device call - a message's
+    per-feature histograms concatenated, with lengths the bin counts. Returns
+    a PaillierArray of len(arr) ciphertexts with the inputs' exponents, in HBM
+    when the scan ran there; cumulative bins at exponent 0 are what
+    pack_ciphertexts takes. Needs only the public key.
+
+    The device path serves arrays with a context, without missing entries and
+    with one exponent per run; anything else is the reference's object left
+    fold per run, concatenated. A call walks one chain of dependent products
+    whatever the batch: scan everything a message carries in one call."""
+    from .paillier import PaillierCiphertext
+    from .paillier.array import PaillierArray, _Fallback, _scan_segments, _wrap
+    if isinstance(arr, np.ndarray) and arr.dtype == object and arr.ndim == 1 and \
+            all(isinstance(c, PaillierCiphertext) for c in arr):
+        arr = PaillierArray(arr)
+    if not isinstance(arr, PaillierArray):
+        raise TypeError("cumsum_segments takes a PaillierArray or an object array of PaillierCiphertext")
+    if arr.ndim != 1:
+        raise ValueError("cumsum_segments takes a 1-D array")
+    lens = np.asarray(lengths, dtype=np.int64).reshape(-1)
+    if lens.size and lens.min() < 0:
+        raise ValueError("cumsum_segments: negative run length")
+    if int(lens.sum()) != arr.size:
+        raise ValueError(f"cumsum_segments: the run lengths add up to {int(lens.sum())}, the array has {arr.size}")
+    seg = np.zeros(lens.size + 1, dtype=np.int64)
+    np.cumsum(lens, out=seg[1:])
+    try:
+        if lens.size == 0:
+            raise _Fallback()
+        return _scan_segments(arr, seg)
+    except _Fallback:
+        obj = np.asarray(arr)
+        parts = [np.cumsum(obj[lo:hi]) for lo, hi in zip(seg[:-1], seg[1:]) if hi > lo]
+        if not parts:
+            return arr.copy()
+        res = np.concatenate(parts)
+        return PaillierArray._from_sequence(res) if arr._has_na() else _wrap(res)
+
+
 def unpack_columns(cols, count: int, num: int, k: int):
     """decrypt_unpack's index mapping: cols[t * num + i][j] (the num * k digit
     columns of the packed plaintexts) -> out[i][j * k + t], cut to count."""
