@@ -790,6 +790,92 @@ class LogDigits(MontDigits):
         assert x == u + P * z and x < P * P
         return x
 
+    # -- rows in pairs (pdigit_dev.hpp "Rows in pairs"; k_djn_pmd, one lane per
+    # element). Two rows y1, y2 with y_i R^2 = R e_i (1 + P l_i): one Montgomery
+    # product mod P with its quotient digits kept, e1 e2 = R a12 - m P exactly,
+    # gives y1 y2 R^2 = (R a12 + P c12)(1 + P (l1 + l2)) with c12 = (R - 1 - m) +
+    # E = -m (mod P): an ordinary two-digit operand of the general product.
+    @staticmethod
+    def _note(ranges, key, val):
+        if ranges is not None:
+            ranges[key] = max(ranges.get(key, float("-inf")), val)
+
+    def pair(self, row1, row2, ctr, ranges=None):
+        """PMD::mul_pair's step schedule: e1 in registers, e2 streamed. Returns
+        a12 (< P (1 + P/R)), the lazy limbs (MASK - m_i) + E_i of c12 (each below
+        2^29) and lhat1 + lhat2. 2 k^2 mads."""
+        k, P = self.k, self.P
+        (e1, l1), (e2, l2) = row1, row2
+        al, el = limbs(e1, k), limbs(e2, k)
+        T, cl, ml = [0] * k, [], []
+        for i in range(k):
+            x = T[0] + el[i] * al[0]
+            m = (x * self.n0inv) & MASK
+            x += m * self.Pl[0]
+            assert x & MASK == 0
+            for j in range(1, k):
+                T[j - 1] = T[j] + el[i] * al[j] + m * self.Pl[j]
+            T[k - 1] = 0
+            T[0] += x >> W
+            ctr.mads += 2 * k
+            ctr.max_col = max(ctr.max_col, x, max(T))
+            ml.append(m)
+            cl.append((MASK - m) + self.El[i])
+        a12 = _norm_value(T)
+        assert a12 * self.R == e1 * e2 + value(ml) * P, "e1 e2 = R a12 - m P"
+        assert max(cl) < 1 << 29 and (_norm_value(cl) + value(ml)) % P == 0
+        self._note(ranges, "a12_over_P", a12 / P)
+        self._note(ranges, "pair_col_log2", ctr.max_col.bit_length())
+        return a12, cl, l1 + l2
+
+    def mul_lazy(self, x, y, ctr, ranges=None):
+        """MontDigits.mul with the operand's second digit given as lazy limbs (f_i
+        below 2^29, value possibly above R: c12 of `pair`; `mul` would mask it)"""
+        k = self.k
+        (a, c), (e, fl) = x, y
+        al, cl, el = limbs_loose(a, k), limbs_loose(c, k), limbs(e, k)
+        assert len(fl) == k and max(fl) < 1 << 29
+        T1, T2 = [0] * k, [0] * k
+        for i in range(k):
+            x1 = T1[0] + el[i] * al[0]
+            m1 = (x1 * self.n0inv) & MASK
+            x1 += m1 * self.Pl[0]
+            x2 = T2[0] + el[i] * cl[0] + fl[i] * al[0]
+            m2 = (x2 * self.n0inv) & MASK
+            x2 += m2 * self.Pl[0]
+            assert x1 & MASK == 0 and x2 & MASK == 0
+            for j in range(1, k):
+                T1[j - 1] = T1[j] + el[i] * al[j] + m1 * self.Pl[j]
+                T2[j - 1] = T2[j] + el[i] * cl[j] + fl[i] * al[j] + m2 * self.Pl[j]
+            ctr.mads += 5 * k
+            T1[k - 1] = 0
+            T2[k - 1] = (MASK - m1) + self.El[i]
+            T1[0] += x1 >> W
+            T2[0] += x2 >> W
+            ctr.max_col = max(ctr.max_col, x1, x2, max(T1), max(T2))
+        self._note(ranges, "mul_col_log2", ctr.max_col.bit_length())
+        return _norm_value(T1), _norm_value(T2)
+
+    def chain_pairs(self, rows, ctr, ranges=None):
+        """k_djn_pmd's loop at one lane per element: the start row, then the rows
+        two at a time (pair, general product, the sum takes lhat1 + lhat2), one
+        mul_row for an odd leftover. Returns the state (a, c, sum words)."""
+        P, R = self.P, self.R
+        st = self.start(rows[0])
+        i = 1
+        while i < len(rows):
+            if i + 1 < len(rows):
+                a12, fl, ls = self.pair(rows[i], rows[i + 1], ctr, ranges)
+                a, c = self.mul_lazy((st[0], st[1]), (a12, fl), ctr, ranges)
+                st = (a, c, self.lam_add(st[2], ls))
+                i += 2
+            else:
+                st = self.mul_row(st, rows[i], ctr)
+                i += 1
+            self._note(ranges, "a_over_P", st[0] / P)
+            self._note(ranges, "c_minus_R_over_P", (st[1] - R) / P)
+        return st
+
 
 def red_rows(lo, hi, Nl, n0inv, ctr, digits=None):
     """Mont::red_rows: L rows T <- (T + m N) / 2^W on the lazy columns T = lo

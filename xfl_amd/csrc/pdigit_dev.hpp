@@ -105,6 +105,26 @@
 // (bn_dev.hpp red_rows, red_rows_q), no modulus P^2. Every column is below
 // 2^63: the product's are 2K products of 2^56 on a start value below 2^29.
 // (Model: tools/pdigit_model.py LogDigits; tests/test_pdigit_ends_model.py.)
+//
+// Rows in pairs (k_djn_pmd at one lane per element). Two rows y1, y2 with y_i R^2
+// = R e_i (1 + P l_i) multiply to
+//     y1 y2 R^2 = e1 e2 (1 + P (l1 + l2))   (mod P^2),
+// and one Montgomery product mod P whose quotient digits m are kept, e1 e2 = R
+// a12 - m P exactly (mul_pair: 2 K^2 mads, one accumulator), turns e1 e2 into R
+// a12 + P c12 with c12 = (R - 1 - m) + E = -m (mod P): an ordinary two-digit
+// operand (a12, c12), a12 < P (1 + P/R), whose second digit is the lazy limbs
+// topc_i - m_i (below 2^29, value up to R + P: never masked). The state takes it
+// by the general product `mul` (5 K^2) and the sum takes lhat1 + lhat2: 7 K^2 =
+// 9,583 mads per two windows against 8 K^2 = 10,952 for two row products. The
+// f_i a_j products stay below 2^57, the accumulator bound above; a' < P (1 +
+// 2P/R) and c' < R + 4P as for every product. A single row left over goes
+// through the same product as the operand (e, 0) (unpack_e0_lds), which gives
+// mul_row's result for K^2 more mads; a second product routine on (a, c) beside
+// `mul` in one kernel made the register allocator spill. While the operand
+// fills the lane's slot the log sum cannot live there: it does not depend on
+// the state and is formed in one pass before the window loop (lam_acc).
+// (Model: LogDigits.pair / mul_lazy / chain_pairs; tests/test_pdigit_pair_model.py;
+// device: tests/native/pmd_pair_selftest.hip.)
 #pragma once
 #include "bn_dev.hpp"
 
@@ -474,6 +494,123 @@ struct PMD {
     normalize(T2, c);
   }
 
+  // ---- rows in pairs (header: "Rows in pairs"): one accumulator,
+  // 12 mads per 6 positions
+  //   T[j-1+k] = T[j+k] + e r[j+k] + m P[j+k]
+  XHE_DEV void blk6(uint64_t (&T)[K], const uint32_t (&r)[K], uint32_t e, uint32_t m, int j) const {
+    asm(
+      "v_mad_u64_u32 %0, vcc, %7, %9, %1\n\t"
+      "v_mad_u64_u32 %1, vcc, %7, %10, %2\n\t"
+      "v_mad_u64_u32 %2, vcc, %7, %11, %3\n\t"
+      "v_mad_u64_u32 %3, vcc, %7, %12, %4\n\t"
+      "v_mad_u64_u32 %4, vcc, %7, %13, %5\n\t"
+      "v_mad_u64_u32 %5, vcc, %7, %14, %6\n\t"
+      "v_mad_u64_u32 %0, vcc, %8, %15, %0\n\t"
+      "v_mad_u64_u32 %1, vcc, %8, %16, %1\n\t"
+      "v_mad_u64_u32 %2, vcc, %8, %17, %2\n\t"
+      "v_mad_u64_u32 %3, vcc, %8, %18, %3\n\t"
+      "v_mad_u64_u32 %4, vcc, %8, %19, %4\n\t"
+      "v_mad_u64_u32 %5, vcc, %8, %20, %5"
+        : "+v"(T[j - 1]), "+v"(T[j]), "+v"(T[j + 1]), "+v"(T[j + 2]), "+v"(T[j + 3]), "+v"(T[j + 4])
+        : "v"(T[j + 5]), "v"(e), "v"(m), "v"(r[j]), "v"(r[j + 1]), "v"(r[j + 2]), "v"(r[j + 3]), "v"(r[j + 4]),
+          "v"(r[j + 5]), "s"(p[j]), "s"(p[j + 1]), "s"(p[j + 2]), "s"(p[j + 3]), "s"(p[j + 4]), "s"(p[j + 5])
+        : "vcc");
+  }
+  // blk6 of the product's first step (T zero on entry, written, not read)
+  XHE_DEV void blk6_0(uint64_t (&T)[K], const uint32_t (&r)[K], uint32_t e, uint32_t m, int j) const {
+    asm(
+      "v_mad_u64_u32 %0, vcc, %6, %8, 0\n\t"
+      "v_mad_u64_u32 %1, vcc, %6, %9, 0\n\t"
+      "v_mad_u64_u32 %2, vcc, %6, %10, 0\n\t"
+      "v_mad_u64_u32 %3, vcc, %6, %11, 0\n\t"
+      "v_mad_u64_u32 %4, vcc, %6, %12, 0\n\t"
+      "v_mad_u64_u32 %5, vcc, %6, %13, 0\n\t"
+      "v_mad_u64_u32 %0, vcc, %7, %14, %0\n\t"
+      "v_mad_u64_u32 %1, vcc, %7, %15, %1\n\t"
+      "v_mad_u64_u32 %2, vcc, %7, %16, %2\n\t"
+      "v_mad_u64_u32 %3, vcc, %7, %17, %3\n\t"
+      "v_mad_u64_u32 %4, vcc, %7, %18, %4\n\t"
+      "v_mad_u64_u32 %5, vcc, %7, %19, %5"
+        : "=&v"(T[j - 1]), "=&v"(T[j]), "=&v"(T[j + 1]), "=&v"(T[j + 2]), "=&v"(T[j + 3]), "=&v"(T[j + 4])
+        : "v"(e), "v"(m), "v"(r[j]), "v"(r[j + 1]), "v"(r[j + 2]), "v"(r[j + 3]), "v"(r[j + 4]), "v"(r[j + 5]),
+          "s"(p[j]), "s"(p[j + 1]), "s"(p[j + 2]), "s"(p[j + 3]), "s"(p[j + 4]), "s"(p[j + 5])
+        : "vcc");
+  }
+
+  // `step_row` on one accumulator: entry x = T[0] + e r[0] and its digit m; the
+  // next step's x and m are formed under this step's mads.
+  template <bool FIRST = false>
+  XHE_DEV void step_one(uint64_t (&T)[K], const uint32_t (&r)[K], uint32_t e, uint32_t en, uint32_t& m,
+                        uint64_t& x) const {
+    uint64_t xn = 0;
+    uint32_t t = 0, mn = 0;
+    asm("v_mad_u64_u32 %0, vcc, %1, %2, %0" : "+v"(x) : "v"(m), "s"(p[0]) : "vcc");
+#pragma unroll
+    for (int b = 0; b < (K - 1) / BL; ++b) {
+      const int j = 1 + BL * b;
+      if constexpr (FIRST) blk6_0(T, r, e, m, j);
+      else blk6(T, r, e, m, j);
+      if (b == 0) {
+        T[0] += x >> W;
+        asm volatile("" : "+v"(T[0]));
+      } else if (b == 1) {
+        asm("v_mad_u64_u32 %0, vcc, %1, %2, %3" : "=&v"(xn) : "v"(en), "v"(r[0]), "v"(T[0]) : "vcc");
+        asm volatile("" : "+v"(xn));
+      } else if (b == 2) {
+        t = (uint32_t)xn * n0inv;
+        asm volatile("" : "+v"(t));
+      } else if (b == 3) {
+        mn = t & MASK;
+        asm volatile("" : "+v"(mn));
+      }
+      __builtin_amdgcn_sched_barrier(0);
+    }
+    T[K - 1] = 0;
+    x = xn;
+    m = mn;
+  }
+
+  // Two table rows into one two-digit operand (header: "Rows in pairs"): r
+  // holds the K limbs of e1, the limbs of e2 are streamed from quads [PQ, NQ) of
+  // the lane's slot (plain quad-major, zero beyond K: unpack_e_lds<.., PQ>). One
+  // Montgomery product mod P, e1 e2 = R a12 - m P, whose quotient digits are
+  // kept: the slot leaves as the interleaved image PMD::mul reads, quad q =
+  // (a12_2q, c12_2q, a12_2q+1, c12_2q+1) with c12_i = topc_i - m_i (lazy, below
+  // 2^29). 2 K^2 mads. In place: c12_i is written at step i into quad i / 2; the
+  // pair of e2 limbs (2h + 2, 2h + 3) is read at the start of iteration h, before
+  // the iteration's two writes into quads h and h + 1, which hold e2 limbs 4 (h
+  // - PQ) + 3 and 4 (h + 1 - PQ) + 1 when they lie in the streamed row: both at
+  // most 2h + 3 for h <= 2 PQ - 1, already read. The a12 limbs follow after the
+  // product. A lane touches its own slot alone.
+  static constexpr int PQ = NQ - (K + 3) / 4;  // first quad of the streamed row
+  XHE_DEV void mul_pair(uint32_t (&r)[K], uint32_t* slot, const uint32_t* topc) const {
+    static_assert(K & 1, "the first step alone, then pairs of steps");
+    static_assert(PQ >= 0 && K / 2 - 1 <= 2 * PQ - 1, "c12 is written over e2 limbs already read");
+    const uint32_t* es = slot + PQ * 256;
+    uint64_t T[K];  // first written by the first step
+    uint2 p0 = *reinterpret_cast<const uint2*>(es);
+    uint64_t x = mad64(p0.x, r[0], 0ull);
+    uint32_t m = ((uint32_t)x * n0inv) & MASK;
+    slot[1] = topc[0] - m;
+    step_one<true>(T, r, p0.x, p0.y, m, x);
+    for (int h = 0; h < K / 2; ++h) {
+      const int k = 2 * h + 2;  // the next pair: limbs k, k + 1 (limb K = 0)
+      const uint32_t tc1 = topc[2 * h + 1], tc2 = topc[2 * h + 2];
+      const uint2 p1 = *reinterpret_cast<const uint2*>(es + (k >> 2) * 256 + (k & 2));
+      __builtin_amdgcn_sched_barrier(0);
+      slot[h * 256 + 3] = tc1 - m;
+      step_one(T, r, p0.y, p1.x, m, x);
+      __builtin_amdgcn_sched_barrier(0);
+      slot[(h + 1) * 256 + 1] = tc2 - m;
+      step_one(T, r, p1.x, p1.y, m, x);
+      __builtin_amdgcn_sched_barrier(0);
+      p0 = p1;
+    }
+    normalize(T, r);  // a12 < P (1 + P/R) < R
+#pragma unroll
+    for (int j = 0; j < K; ++j) slot[(j >> 1) * 256 + 2 * (j & 1)] = r[j];
+  }
+
   // The log sum of a lane: LW little-endian words in quads [EQ, NQ) of its
   // slot, beside the EQ quads of the row's e limbs.
   static constexpr int EQ = (K + 3) / 4;           // quads of e limbs
@@ -548,6 +685,23 @@ struct PMD {
 #pragma unroll
     for (int q = 0; q < LQ; ++q)
       *reinterpret_cast<uint4*>(slot + (EQ + q) * 256) = make_uint4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
+  }
+  // lam_add's chain on a sum held in registers (s: the words of the sum quads,
+  // those past LW zero): the log sum formed in one pass over a lane's rows,
+  // outside the window loop (header: "Rows in pairs")
+  template <int HW>
+  XHE_DEV static void lam_acc(uint32_t (&s)[4 * ((LW + 3) / 4)], const uint32_t (&lam)[HW]) {
+    constexpr int NW = HW < LW ? HW : LW;
+    static_assert(HW >= 8 && HW <= 4 * ((LW + 3) / 4), "at least one block of the chain, at most a whole sum");
+    uint64_t cy;
+    add8<true>(s, lam, 0, cy);
+#pragma unroll
+    for (int k = 8; k + 8 <= NW; k += 8) add8<false>(s, lam, k, cy);
+#pragma unroll
+    for (int k = NW & ~7; k < NW; ++k)
+      asm("v_addc_co_u32_e64 %0, %1, %0, %2, %1" : "+v"(s[k]), "+s"(cy) : "v"(lam[k]));
+#pragma unroll
+    for (int k = NW; k < LW; ++k) asm("v_addc_co_u32_e64 %0, %1, 0, %0, %1" : "+v"(s[k]), "+s"(cy));
   }
   // sum <- sum + the sum in another lane's slot (the tree of a lane group)
   XHE_DEV static void lam_add_slot(uint32_t* slot, const uint32_t* other) {
@@ -1022,8 +1176,10 @@ XHE_DEV void unpack_pairs_lds(uint32_t* slot) {
 // The e half of a packed row alone (HW words, staged quad-major in quads
 // [0, HW/4) of the slot by LDS-DMA) rewritten in place as (K + 3) / 4 quads of
 // plain 28-bit limbs, zero beyond K (PMD::mul_row's operand). The quads above
-// stay untouched: they hold the lane's log sum.
-template <int K, int HW>
+// stay untouched: they hold the lane's log sum. QO: the first quad of the limbs
+// written (PMD::PQ for the streamed row of PMD::mul_pair, which may overlap the
+// packed words: they are all in registers before the first write).
+template <int K, int HW, int QO = 0>
 XHE_DEV void unpack_e_lds(uint32_t* slot) {
   static_assert(HW % 4 == 0 && 32 * HW >= 28 * K - 27, "the packed digit holds K limbs");
   uint32_t w[HW];
@@ -1042,7 +1198,47 @@ XHE_DEV void unpack_e_lds(uint32_t* slot) {
   };
 #pragma unroll
   for (int q = 0; q < (K + 3) / 4; ++q)
-    *reinterpret_cast<uint4*>(slot + q * 256) = make_uint4(limb(4 * q), limb(4 * q + 1), limb(4 * q + 2), limb(4 * q + 3));
+    *reinterpret_cast<uint4*>(slot + (QO + q) * 256) =
+        make_uint4(limb(4 * q), limb(4 * q + 1), limb(4 * q + 2), limb(4 * q + 3));
+}
+
+// The e half of a packed row alone (staged as for unpack_e_lds) rewritten as the
+// interleaved image of the operand (e, 0): quad q = (e_2q, 0, e_2q+1, 0), (2K +
+// 3) / 4 quads - a single row through the general product PMD::mul, whose
+// result is mul_row's (the f a mads add zero).
+template <int K, int HW>
+XHE_DEV void unpack_e0_lds(uint32_t* slot) {
+  static_assert(HW % 4 == 0 && 32 * HW >= 28 * K - 27, "the packed digit holds K limbs");
+  uint32_t w[HW];
+#pragma unroll
+  for (int q = 0; q < HW / 4; ++q) {
+    const uint4 v = *reinterpret_cast<const uint4*>(slot + q * 256);
+    w[4 * q] = v.x;
+    w[4 * q + 1] = v.y;
+    w[4 * q + 2] = v.z;
+    w[4 * q + 3] = v.w;
+  }
+  auto limb = [&](int i) -> uint32_t {
+    const int bit = 28 * i, k = bit >> 5, sh = bit & 31;
+    const uint32_t lo = k < HW ? w[k] : 0u, hi = k + 1 < HW ? w[k + 1] : 0u;
+    return i < K ? (__builtin_amdgcn_alignbit(hi, lo, sh) & ((1u << 28) - 1u)) : 0u;
+  };
+#pragma unroll
+  for (int q = 0; q < (2 * K + 3) / 4; ++q)
+    *reinterpret_cast<uint4*>(slot + q * 256) = make_uint4(limb(2 * q), 0u, limb(2 * q + 1), 0u);
+}
+
+// The e half of a packed row (HW words in registers) as K plain 28-bit limbs:
+// the register row of PMD::mul_pair (unpack_e_lds's arithmetic)
+template <int K, int HW>
+XHE_DEV void unpack_e_regs(const uint32_t (&w)[HW], uint32_t (&r)[K]) {
+  static_assert(32 * HW >= 28 * K - 27, "the packed digit holds K limbs");
+#pragma unroll
+  for (int i = 0; i < K; ++i) {
+    const int bit = 28 * i, k = bit >> 5, sh = bit & 31;
+    const uint32_t lo = k < HW ? w[k] : 0u, hi = k + 1 < HW ? w[k + 1] : 0u;
+    r[i] = __builtin_amdgcn_alignbit(hi, lo, sh) & ((1u << 28) - 1u);
+  }
 }
 
 }  // namespace xhe

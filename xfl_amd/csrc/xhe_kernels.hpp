@@ -611,7 +611,8 @@ __global__ void __launch_bounds__(128, 2) k_djn_pow_lds(KeyDev key, const uint32
 // per wave), else a REDC of m by P and one Montgomery product mod P by the
 // key's Q R^4 (pmd_lam_plain); the
 // first window's row is the start value (e, 0), its lhat added to the sum;
-// each further window's row is fetched in one visit - e by LDS-DMA into the
+// each further window's row (in a lane group; G = 1 is described below) is
+// fetched in one visit - e by LDS-DMA into the
 // wave's image and unpacked into limbs, lhat into registers and added to the
 // lane's log sum, which lives in the upper quads of the lane's slot - and e is
 // multiplied in (nwin - 1 row products, 4 K^2 mads each); the exit goes through
@@ -619,6 +620,20 @@ __global__ void __launch_bounds__(128, 2) k_djn_pow_lds(KeyDev key, const uint32
 // mads, the log sum folded in on the way) to the canonical residue
 // djn_prime_lds writes. Output rows as k_djn_pow_lds (MP2 limbs, [prime][2
 // S4][count]) for k_crt_enc_w.
+//
+// G = 1 (full batches; pdigit_dev.hpp "Rows in pairs"): the windows after the
+// first are taken two at a time. A visit fetches two rows' e halves - the second
+// row's by LDS-DMA, unpacked into the upper quads of the lane's slot, the first
+// row's through registers - mul_pair multiplies them mod P into the two-digit
+// operand (a12, c12) in the slot, and the state takes it by the general product
+// PMD::mul: 7 K^2 mads per two windows against 8 K^2. A last single row goes
+// through the same product as (e, 0). The operand fills the slot, so the log sum
+// is formed before the loop in one pass over the lane's rows (their lhat halves,
+// four rows in flight; the same bytes as a visit fetched), parked in the first
+// LW rows of the element's own column of ws - rows nothing reads before this
+// lane's final store overwrites them - and read back into the sum quads for
+// pmd_exit. The window digits are extracted twice; the exponent's address is
+// formed again at each visit (two VGPRs not held across the products).
 //
 // G > 1 (small batches, where the chip is not full and the chain of nwin
 // dependent products is the latency): G adjacent lanes share an element; lane
@@ -701,6 +716,118 @@ __global__ void __launch_bounds__(128, 2) k_djn_pmd(KeyDev key, const uint32_t* 
   }
   __builtin_amdgcn_sched_barrier(0);
   uint32_t a[KP], c[KP];
+  if constexpr (G == 1) {
+    constexpr int LQ = (D::LW + 3) / 4, HW = RW / 2;
+    // The log sum does not depend on the state: Lhat = muhat + the lhat of every
+    // window's row, formed here in one pass with four rows' halves in flight, and
+    // parked in the element's own column of ws (rows the final store overwrites)
+    // - during the window loop the general product's operand takes the whole slot.
+    {
+      uint32_t s[4 * LQ];
+#pragma unroll
+      for (int q = 0; q < LQ; ++q) {
+        const uint4 v = *reinterpret_cast<const uint4*>(slot + (D::EQ + q) * 256);
+        s[4 * q] = v.x, s[4 * q + 1] = v.y, s[4 * q + 2] = v.z, s[4 * q + 3] = v.w;
+      }
+      auto lam_row = [&](int w, uint32_t (&lam)[HW]) XHE_INL {
+        int64_t row0;
+        const uint32_t d = win_digit(key, ae, aw, w, row0);
+        const uint32_t* row = tab + (size_t)(row0 + d) * key.tab_rs;
+#pragma unroll
+        for (int k = 0; k < HW / 4; ++k) {
+          const uint4 v = *reinterpret_cast<const uint4*>(row + HW + 4 * k);
+          lam[4 * k] = v.x, lam[4 * k + 1] = v.y, lam[4 * k + 2] = v.z, lam[4 * k + 3] = v.w;
+        }
+      };
+      int w = 0;
+      for (; w + 4 <= key.nwin; w += 4) {
+        uint32_t l0[HW], l1[HW], l2[HW], l3[HW];
+        lam_row(w, l0);
+        lam_row(w + 1, l1);
+        lam_row(w + 2, l2);
+        lam_row(w + 3, l3);
+        D::template lam_acc<HW>(s, l0);
+        D::template lam_acc<HW>(s, l1);
+        D::template lam_acc<HW>(s, l2);
+        D::template lam_acc<HW>(s, l3);
+      }
+      for (; w < key.nwin; ++w) {
+        uint32_t l0[HW];
+        lam_row(w, l0);
+        D::template lam_acc<HW>(s, l0);
+      }
+      uint32_t* park = ws + (size_t)prime * 2 * MP2::S4 * count + e;
+#pragma unroll
+      for (int k = 0; k < D::LW; ++k) park[(size_t)k * count] = s[k];
+    }
+    __builtin_amdgcn_sched_barrier(0);
+    // a row's e half alone: by LDS-DMA into quads [0, RW/8) of the image
+    auto ae_now = [&]() XHE_INL -> const uint32_t* {
+      return a_words + (size_t)((int64_t)blockIdx.x * blockDim.x + (uint32_t)opaque_i((int)threadIdx.x)) * aw;
+    };
+    auto dma_e = [&](int w) XHE_INL {
+      int64_t row0;
+      const uint32_t d = win_digit(key, ae_now(), aw, w, row0);
+      const uint32_t* row = tab + (size_t)(row0 + d) * key.tab_rs;
+#pragma unroll
+      for (int k = 0; k < RW / 8; ++k)
+        __builtin_amdgcn_global_load_lds((xhe_glb_void*)(row + 4 * k), (xhe_lds_void*)(img + k * 256), 16, 0, 0);
+    };
+    dma_e(0);  // the start value: (e, 0)
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+    unpack_e_lds<KP, HW>(slot);
+#pragma unroll
+    for (int q = 0; q < D::EQ; ++q) {
+      const uint4 v = *reinterpret_cast<const uint4*>(slot + q * 256);
+      if (4 * q < KP) a[4 * q] = v.x;
+      if (4 * q + 1 < KP) a[4 * q + 1] = v.y;
+      if (4 * q + 2 < KP) a[4 * q + 2] = v.z;
+      if (4 * q + 3 < KP) a[4 * q + 3] = v.w;
+    }
+#pragma unroll
+    for (int j = 0; j < KP; ++j) c[j] = 0u;
+    // Two windows per visit: the second row's e by LDS-DMA and unpacked as the
+    // streamed row of mul_pair, the first row's e through registers; their
+    // product (a12, c12) leaves in the slot as the general product's operand.
+    for (int w = 1; w < key.nwin; w += 2) {
+      if (w + 1 < key.nwin) {
+        uint32_t r[KP];
+        dma_e(w + 1);
+        int64_t row0;
+        const uint32_t d = win_digit(key, ae_now(), aw, w, row0);
+        const uint32_t* row = tab + (size_t)(row0 + d) * key.tab_rs;
+        uint32_t pw[HW];
+#pragma unroll
+        for (int k = 0; k < HW / 4; ++k) {
+          const uint4 v = *reinterpret_cast<const uint4*>(row + 4 * k);
+          pw[4 * k] = v.x, pw[4 * k + 1] = v.y, pw[4 * k + 2] = v.z, pw[4 * k + 3] = v.w;
+        }
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        unpack_e_lds<KP, HW, D::PQ>(slot);
+        unpack_e_regs<KP, HW>(pw, r);
+        __builtin_amdgcn_sched_barrier(0);
+        M.mul_pair(r, slot, topc);
+      } else {  // an odd leftover: the row as the operand (e, 0)
+        dma_e(w);
+        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        unpack_e0_lds<KP, HW>(slot);
+      }
+      __builtin_amdgcn_sched_barrier(0);
+      M.mul(a, c, slot, topc);
+    }
+    // the parked log sum back where pmd_exit reads it
+    {
+      const int64_t ep = (int64_t)blockIdx.x * blockDim.x + (uint32_t)opaque_i((int)threadIdx.x);
+      const uint32_t* park = ws + (size_t)prime * 2 * MP2::S4 * count + ep;
+      uint32_t s[4 * LQ];
+#pragma unroll
+      for (int k = 0; k < 4 * LQ; ++k) s[k] = k < D::LW ? park[(size_t)k * count] : 0u;
+#pragma unroll
+      for (int q = 0; q < LQ; ++q)
+        *reinterpret_cast<uint4*>(slot + (D::EQ + q) * 256) = make_uint4(s[4 * q], s[4 * q + 1], s[4 * q + 2], s[4 * q + 3]);
+    }
+    __builtin_amdgcn_sched_barrier(0);
+  } else {
   if (G == 1 || g < key.nwin) {
     stage(g);  // the start value: (e, 0); the row's lhat joins the sum
 #pragma unroll
@@ -741,6 +868,7 @@ __global__ void __launch_bounds__(128, 2) k_djn_pmd(KeyDev key, const uint32_t* 
     }
     if (g != 0) return;
   }
+  }  // G > 1
   // out through the digits: the log sum folded in on the way to the canonical
   // residue (1 + n m) h^a mod P^2 (pmd_exit; only P, no modulus P^2)
   uint32_t b[MP2::L];
