@@ -11,9 +11,9 @@
  * gives the thread-local message. A key handle is immutable after creation
  * and may be shared between threads; calls on distinct streams are reentrant.
  *
- * Ciphertext operands: the eight entry points that read ciphertext words -
+ * Ciphertext operands: the nine entry points that read ciphertext words -
  * xhe_decrypt, xhe_mulmod, xhe_powmod, xhe_pack, xhe_invert, xhe_segprod,
- * xhe_segscan and xhe_multiexp (and their _host variants) - accept ANY value in
+ * xhe_segscan, xhe_hist and xhe_multiexp (and their _host variants) - accept ANY value in
  * [0, 2^(32 n2w))
  * in an operand row, not only residues below n^2: a received payload is not
  * reduced on its way into a device array (xhe_wire_decode, xhe_wire_scan and
@@ -210,6 +210,37 @@ int xhe_segprod(const xhe_key* key, const uint32_t* c_dev, const int32_t* d_dev,
 int xhe_segscan(const xhe_key* key, const uint32_t* c_dev, int64_t count, const int64_t* seg_begin, int64_t nseg,
                 uint32_t* out_dev, void* stream);
 
+/* Fused multi-feature histogram (the per-feature groupby('bin').agg({'count',
+ * 'sum'}) of one ciphertext column over every feature of the party:
+ * decision_tree_trainer.py:131-160,208, binning_woe_iv/trainer.py:55-65,101)
+ * in one call, from the ciphertext rows where they lie and a bin matrix - no
+ * bin-ordered copy, no sort, no host plan, no host synchronisation.
+ * c: n_rows ciphertexts of n2w words (any values below 2^(32 n2w), taken mod
+ * n^2). bins: nfeat rows of uint16 bin ids, the id of feature f for
+ * ciphertext row r at bins[f * bins_stride + r], bins_stride >= n_rows.
+ * Element i < count of the call is row r = rows ? rows[i] : i (a tree node's
+ * sample subset; ids need not be distinct; rows == NULL requires count ==
+ * n_rows). rows is the caller's own device data and is TRUSTED: every id must
+ * be in [0, n_rows), the kernel does not check it.
+ *   out[(f * nbins + b) * n2w ..] = prod c[r] mod n^2 over the call's elements
+ *     with bins[f][r] == b, below n^2; an empty bin gives 1 (the raw encryption
+ *     of 0, as xhe_segprod);
+ *   cnt[f * nbins + b] = the number of such elements (cnt may be NULL).
+ * A bin id >= nbins drops the row for that feature (0xFFFF: NaN, a dropped
+ * group, a missing ciphertext). No exponent argument: as xhe_segscan, the call
+ * is defined for rows of one exponent, which the caller ensures. Needs no
+ * private key. tile_rows: elements per block tile, 0 = the planner's choice
+ * (paths.hpp hist_tile), else a power of two in [64, 8192]. count == 0 writes
+ * ones and zero counts. XHE_EINVAL: nbins outside [1, 4096], nfeat < 1, a
+ * negative count, bins_stride < n_rows, tile_rows outside its set, rows ==
+ * NULL with count != n_rows, out overlapping c. Runs in the batch n^2 shape
+ * for every key size ($XHE_N2_TPI does not apply); enqueues on `stream` and
+ * returns without synchronising. Timed as "k_hist" under xhe_profile (its
+ * first stage alone as "k_hist_tile"). */
+int xhe_hist(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const uint16_t* bins_dev, int64_t bins_stride,
+             int nfeat, int nbins, const int32_t* rows_dev, int64_t count, int tile_rows, uint32_t* out_dev,
+             int32_t* cnt_dev, void* stream);
+
 /* Encrypted matrix-vector product as a multi-exponentiation: the object-dtype
  * np.matmul(enc[B], X[B, D]) of logistic_regression/trainer.py:166 (and
  * linear_regression/trainer.py:207, poisson_regression/trainer.py:267,
@@ -267,6 +298,10 @@ int xhe_segprod_host(const xhe_key* key, const uint32_t* c, const int32_t* d, in
                      const int64_t* seg_begin, int64_t nseg, uint32_t* out);
 int xhe_segscan_host(const xhe_key* key, const uint32_t* c, int64_t count, const int64_t* seg_begin, int64_t nseg,
                      uint32_t* out);
+/* xhe_hist on host buffers; rows (host ids) are validated: XHE_EINVAL for an id outside [0, n_rows). */
+int xhe_hist_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins, int64_t bins_stride,
+                  int nfeat, int nbins, const int32_t* rows, int64_t count, int tile_rows, uint32_t* out,
+                  int32_t* cnt);
 /* xhe_pack: count ciphertexts in, ceil(count/k) out. */
 int xhe_pack_host(const xhe_key* key, const uint32_t* c, int64_t count, int k, int shift_bits, uint32_t* out);
 int xhe_mulmod_host(const xhe_key* key, const uint32_t* a, const int32_t* ea, const uint32_t* b, const int32_t* eb,

@@ -233,6 +233,46 @@ inline SegFirst segprod_first(int64_t count, int dmax, bool has_d, const Pins& p
   return count > 0 && (dmax == 0 || !has_d) && pins.sum_words ? SegFirst::WORDS : SegFirst::ALIGN;
 }
 
+// ------------------------------------------------------- fused histogram
+// xhe_hist (hist_dev.hpp): elements per tile. About kRawChunk = 32 rows per
+// (bin, tile) - one slice per bin, so a block's products are the elements'
+// plus one per bin - that is 32 nbins rounded up to a power of two in
+// [kHistTileMin, kHistTileMax], but at least a slice for each of a block's 64
+// lane groups (32 x 64 rows: with 32 nbins alone a 2-bin histogram ran 2 of
+// its 64 groups per block, 485 ms for config 5's rows against 23 ms at 256
+// bins; the bins' further slices are combined in the block); halved while nfeat x tiles blocks would leave
+// the chip short of two blocks per CU (kHistFillBlocks = 512 blocks of 256
+// threads: the 131072 lanes reduce_segments' kFill counts), since a short grid
+// costs more than the extra product per shorter slice. Runs in the batch n^2
+// shape (Sh::MN2) whatever the count: $XHE_N2_TPI does not apply.
+constexpr int kHistTileMin = 64, kHistTileMax = 8192;
+constexpr int64_t kHistFillBlocks = 512;
+
+inline bool hist_tile_ok(int tile_rows) {
+  return tile_rows >= kHistTileMin && tile_rows <= kHistTileMax && (tile_rows & (tile_rows - 1)) == 0;
+}
+
+inline int hist_tile(int64_t count, int nfeat, int nbins) {
+  int tile = kHistTileMin;
+  while (tile < kHistTileMax && tile < 32 * (int64_t)(nbins > 64 ? nbins : 64)) tile <<= 1;
+  while (tile > kHistTileMin && (int64_t)nfeat * ((count + tile - 1) / tile) < kHistFillBlocks) tile >>= 1;
+  return tile;
+}
+
+// Dynamic LDS of k_hist_tile: two words per bin, the work list, the element list.
+inline int64_t hist_lds_bytes(int tile_rows, int nbins) {
+  return 8 * (int64_t)nbins + 4 * (int64_t)(tile_rows / 32) + 2 * (int64_t)tile_rows;
+}
+
+// Features per launch group: the partial rows (nbins per feature and tile)
+// and the parked rows (tile_rows / 16 per block) of one group stay within
+// cap_rows residue rows (the launch layer's kChunk), at least one feature.
+inline int hist_group(int nfeat, int nbins, int tile_rows, int64_t tiles, int64_t cap_rows) {
+  const int64_t per_feat = tiles * ((int64_t)nbins + tile_rows / 16);
+  const int64_t g = cap_rows / (per_feat > 0 ? per_feat : 1);
+  return (int)(g < 1 ? 1 : g > nfeat ? nfeat : g);
+}
+
 enum class Horner {
   WAVE,   // 2048, 16 lanes: k_mexp_horner_wave, one 16-wave block per column (latency)
   LANES,  // k_mexp_horner

@@ -30,6 +30,7 @@
 #include "rns_dev.hpp"
 #include "enc_obf_dev.hpp"
 #include "wire_unpack.hpp"
+#include "hist_dev.hpp"
 
 using namespace xhe;
 
@@ -1357,6 +1358,55 @@ void segscan_impl(const xhe_key* k, const uint32_t* c, int64_t count, const int6
   }
 }
 
+// Fused multi-feature histogram (hist_dev.hpp): stage A leaves one Montgomery
+// row per (feature, bin, tile), stage B folds the T tiles of every (feature,
+// bin) - uniform segments: no plan upload, no host sync - and packs the
+// words. The features run in groups whose partial and parked rows fit kChunk
+// residue rows; every buffer is freed in stream order.
+template <class Sh>
+void hist_impl(const xhe_key* k, const uint32_t* c, const uint16_t* bins, int64_t bins_stride, int nfeat, int nbins,
+               const int32_t* rows_idx, int64_t count, int tile_rows, uint32_t* out, int32_t* cnt, hipStream_t s) {
+  using MN2 = typename Sh::MN2;
+  const int S4 = MN2::S4;
+  auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
+  ProfScope ps("k_hist", s);
+  if (!tile_rows) tile_rows = paths::hist_tile(count, nfeat, nbins);
+  const int64_t T = std::max<int64_t>(1, (count + tile_rows - 1) / tile_rows);
+  const int gmax = paths::hist_group(nfeat, nbins, tile_rows, T, kChunk);
+  if ((int64_t)gmax * nbins * T > INT32_MAX) throw std::logic_error("xhe_hist: problem too large for one call");
+  const size_t lds = (size_t)paths::hist_lds_bytes(tile_rows, nbins);
+  if (cnt) {
+    const int64_t nc = (int64_t)nfeat * nbins;
+    launch(k_hist_zero, dim3((unsigned)((nc + 255) / 256)), dim3(256), s, cnt, nc);
+  }
+  for (int f0 = 0; f0 < nfeat; f0 += gmax) {
+    const int gf = std::min(gmax, nfeat - f0);
+    const int64_t nseg = (int64_t)gf * nbins, ncols = nseg * T;
+    DevBuf cur;
+    {
+      DevBuf park, part;
+      part = DevBuf((size_t)S4 * ncols * 4, s, DevBuf::kAsync);
+      park = DevBuf((size_t)gf * T * (tile_rows / kHistParkDiv) * S4 * 4, s, DevBuf::kAsync);
+      {
+        ProfScope pt("k_hist_tile", s);
+        hipLaunchKernelGGL((k_hist_tile<MN2, Sh::RW2>), dim3((unsigned)(gf * T)), dim3(256), lds, s, k->kd,
+                           n2h<MN2>(k).N, c, bins, bins_stride, nbins, rows_idx, count, tile_rows, f0, gf, T,
+                           part.as<uint32_t>(), park.as<uint32_t>(), cnt);
+        HIPCHK(hipGetLastError());
+      }
+      if (T == 1) {
+        cur = std::move(part);
+      } else {
+        std::vector<int64_t> seg((size_t)nseg + 1);
+        for (int64_t i = 0; i <= nseg; ++i) seg[(size_t)i] = i * T;
+        cur = reduce_segments<Sh, MN2>(k, std::move(part), ncols, std::move(seg), s);
+      }
+    }
+    launch(k_from_mont_rows<MN2>, blocks(nseg), dim3(256), s, k->kd, n2h<MN2>(k).N, cur.as<uint32_t>(), nseg,
+           out + (size_t)f0 * nbins * k->n2w);
+  }
+}
+
 // Window bits for a multi-exponentiation: minimise table products
 // nbases*(2^c - 2) plus gathered products ncols*nterms*ceil(kbits/c), with the
 // tables capped at ~2 GiB.
@@ -1631,6 +1681,41 @@ int xhe_segscan(const xhe_key* key, const uint32_t* c_dev, int64_t count, const 
       using Sh = decltype(sh);
       if (row) segscan_impl<Sh, typename Sh::MN2X>(key, c_dev, count, seg_begin, nseg, out_dev, hs);
       else segscan_impl<Sh>(key, c_dev, count, seg_begin, nseg, out_dev, hs);
+    });
+    return XHE_OK;
+  });
+}
+
+namespace {
+int hist_args(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins, int64_t bins_stride,
+              int nfeat, int nbins, const int32_t* rows, int64_t count, int tile_rows, const uint32_t* out,
+              const char* who) {
+  (void)rows;
+  if (!key || !out || n_rows < 0 || count < 0 || nfeat < 1 || (n_rows > 0 && !c) || (count > 0 && (!c || !bins)))
+    return fail(XHE_EINVAL, std::string(who) + ": bad argument");
+  if (nbins < 1 || nbins > 4096) return fail(XHE_EINVAL, std::string(who) + ": nbins must be in [1, 4096]");
+  if (bins_stride < n_rows) return fail(XHE_EINVAL, std::string(who) + ": bins_stride is shorter than n_rows");
+  if (tile_rows != 0 && !paths::hist_tile_ok(tile_rows))
+    return fail(XHE_EINVAL, std::string(who) + ": tile_rows must be 0 or a power of two in [64, 8192]");
+  if (!rows && count != n_rows) return fail(XHE_EINVAL, std::string(who) + ": without row ids count must equal n_rows");
+  if (count > 0 && n_rows == 0) return fail(XHE_EINVAL, std::string(who) + ": row ids into an empty array");
+  if (n_rows > 0 && out < c + (size_t)n_rows * key->n2w && c < out + (size_t)nfeat * nbins * key->n2w)
+    return fail(XHE_EINVAL, std::string(who) + ": out overlaps c");
+  return XHE_OK;
+}
+}  // namespace
+
+int xhe_hist(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const uint16_t* bins_dev, int64_t bins_stride,
+             int nfeat, int nbins, const int32_t* rows_dev, int64_t count, int tile_rows, uint32_t* out_dev,
+             int32_t* cnt_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (int rc = hist_args(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins, rows_dev, count, tile_rows,
+                           out_dev, "xhe_hist"))
+      return rc;
+    DevGuard dg(key->device);
+    with_shape(key->K, [&](auto sh) {
+      hist_impl<decltype(sh)>(key, c_dev, bins_dev, bins_stride, nfeat, nbins, rows_dev, count, tile_rows, out_dev,
+                              cnt_dev, (hipStream_t)stream);
     });
     return XHE_OK;
   });
@@ -2637,6 +2722,35 @@ int xhe_segscan_host(const xhe_key* key, const uint32_t* c, int64_t count, const
     int rc = xhe_segscan(key, dc.as<uint32_t>(), count, seg_begin, nseg, dout.as<uint32_t>(), st.s);
     if (rc != XHE_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, bytes, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    return XHE_OK;
+  });
+}
+
+int xhe_hist_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins, int64_t bins_stride,
+                  int nfeat, int nbins, const int32_t* rows, int64_t count, int tile_rows, uint32_t* out,
+                  int32_t* cnt) {
+  return guarded([&]() -> int {
+    if (int rc = hist_args(key, c, n_rows, bins, bins_stride, nfeat, nbins, rows, count, tile_rows, out,
+                           "xhe_hist_host"))
+      return rc;
+    // host row ids are checked here (the device entry point trusts its caller's device data)
+    for (int64_t i = 0; rows && i < count; ++i)
+      if (rows[i] < 0 || rows[i] >= n_rows) return fail(XHE_EINVAL, "xhe_hist_host: row id out of range");
+    DevGuard dg(key->device);
+    Stream st;
+    const size_t cb = (size_t)n_rows * key->n2w * 4, bb = ((size_t)(nfeat - 1) * bins_stride + n_rows) * 2,
+                 ob = (size_t)nfeat * nbins * key->n2w * 4, nb = (size_t)nfeat * nbins * 4;
+    DevBuf dc(cb, st.s), db(bb, st.s), dr(rows ? (size_t)count * 4 : 0, st.s), dout(ob, st.s), dcnt(nb, st.s);
+    if (n_rows > 0) HIPCHK(hipMemcpyAsync(dc.p, c, cb, hipMemcpyHostToDevice, st.s));
+    if (n_rows > 0 && bins) HIPCHK(hipMemcpyAsync(db.p, bins, bb, hipMemcpyHostToDevice, st.s));
+    if (rows && count > 0) HIPCHK(hipMemcpyAsync(dr.p, rows, (size_t)count * 4, hipMemcpyHostToDevice, st.s));
+    int rc = xhe_hist(key, dc.as<uint32_t>(), n_rows, db.as<uint16_t>(), bins_stride, nfeat, nbins,
+                      rows ? dr.as<int32_t>() : nullptr, count, tile_rows, dout.as<uint32_t>(),
+                      cnt ? dcnt.as<int32_t>() : nullptr, st.s);
+    if (rc != XHE_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
+    if (cnt) HIPCHK(hipMemcpyAsync(cnt, dcnt.p, nb, hipMemcpyDeviceToHost, st.s));
     HIPCHK(hipStreamSynchronize(st.s));
     return XHE_OK;
   });

@@ -463,6 +463,36 @@ def segscan_words(ctx, cw, seg):
     return out
 
 
+def hist_words(ctx, cw, bins, nbins, rows=None):
+    """out[f * nbins + b] = prod of the rows r of cw ([n_rows, n2w] host words)
+    with bins[f][r] == b mod n^2, and their number: every (feature, bin) sum
+    and count in one xhe_hist call through host buffers, on the process's GPU.
+    bins: [nfeat, n_rows] uint16 ids (>= nbins: dropped); rows: int32 row ids
+    in [0, n_rows) (validated here: the device trusts them) or None for all
+    rows. -> ([nfeat * nbins, n2w] uint32, [nfeat * nbins] int32). Not sharded:
+    the partial histograms of sample shards are merged by
+    shard.merge_segment_products."""
+    cw = _u32(cw)
+    bins = np.ascontiguousarray(bins, dtype=np.uint16)
+    if bins.ndim != 2 or bins.shape[1] != cw.shape[0]:
+        raise ValueError("hist: bins must be [nfeat, n_rows]")
+    n_rows, nfeat = cw.shape[0], bins.shape[0]
+    count = n_rows
+    if rows is not None:
+        rows = _i32(rows).reshape(-1)
+        count = rows.shape[0]
+        if count and (rows.min() < 0 or rows.max() >= n_rows):
+            raise ValueError("hist: row id out of range")
+    n2w = n2w_of(ctx)
+    out = np.empty((nfeat * nbins, n2w), dtype=np.uint32)
+    cnt = np.empty(nfeat * nbins, dtype=np.int32)
+    dk = ctx.device_key(ctx.own_device())
+    nat.check(nat.lib().xhe_hist_host(dk.handle, _vp(cw) if n_rows else None, n_rows, _vp(bins) if n_rows else None,
+                                      n_rows, nfeat, int(nbins), _vp(rows) if rows is not None else None, count, 0,
+                                      _vp(out), _vp(cnt)), "hist")
+    return out, cnt
+
+
 def segscan_dev(ctx, dk, cd, seg):
     """segscan_words on device words -> device [count, n2w]"""
     from . import resident

@@ -743,6 +743,30 @@ def segscan(dk, c, seg):
     return out
 
 
+def hist(dk, c, bins_d, nbins, rows=None, tile_rows=0):
+    """Per-(feature, bin) sums and counts of the device ciphertext rows c [n_rows,
+    n2w] in one call (xhe_hist): bins_d a device int16 tensor [nfeat, stride >=
+    n_rows] holding uint16 bin ids (an id >= nbins drops the row for that
+    feature), rows a device int32 tensor of row ids (every id < n_rows; None:
+    all rows in order) -> (device [nfeat * nbins, n2w] words, device int32
+    [nfeat * nbins] counts). Nothing here waits for the kernels."""
+    torch = _torch()
+    dev = dk.device
+    n_rows, nfeat = c.shape[0], bins_d.shape[0]
+    if bins_d.dim() != 2 or bins_d.element_size() != 2 or bins_d.stride(1) != 1:
+        raise ValueError("hist: bins must be a [nfeat, stride] tensor of 16-bit ids, rows contiguous")
+    if rows is not None and (rows.dim() != 1 or rows.dtype != torch.int32 or not rows.is_contiguous()):
+        raise ValueError("hist: rows must be a contiguous int32 tensor")
+    count = n_rows if rows is None else rows.shape[0]
+    with _On(dev):
+        out = torch.empty((nfeat * nbins, dk.n2w), dtype=torch.int32, device=f"cuda:{dev}")
+        cnt = torch.empty(nfeat * nbins, dtype=torch.int32, device=f"cuda:{dev}")
+        src = c.contiguous()
+    nat.check(nat.lib().xhe_hist(dk.handle, _dp(src), n_rows, _dp(bins_d), bins_d.stride(0), nfeat, int(nbins),
+                                 _dp(rows), count, int(tile_rows), _dp(out), _dp(cnt), _sp(dev)), "hist")
+    return out, cnt
+
+
 def multiexp(dk, bases, idx, kw_, kbits, win_bits=0):
     """out[j] = prod_t bases[idx[j][t]]^k[j][t] mod n^2 on device bases; idx
     and k host arrays (validated here: the device entry point trusts them)"""

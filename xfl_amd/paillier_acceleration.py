@@ -272,6 +272,84 @@ def cumsum_segments(arr, lengths):
         return PaillierArray._from_sequence(res) if arr._has_na() else _wrap(res)
 
 
+def histograms(arr, bins, nbins: int = None, rows=None):
+    """Every feature's per-bin sums and counts of one ciphertext column in ONE
+    device call (xhe_hist): what the per-column
+    DataFrame.groupby(feature)[column].agg({'count', 'sum'}) loops of
+    decision_tree_trainer.py:131-160 and binning_woe_iv/trainer.py:55-65 compute
+    feature by feature. arr: a 1-D PaillierArray (or object array of
+    PaillierCiphertext); bins: an [nfeat, len(arr)] integer array of bin ids, or
+    a DataFrame of the feature columns (one row per element of arr); negative
+    or NaN entries, ids >= nbins and missing ciphertexts are dropped rows.
+    nbins defaults to the largest id + 1. rows: indices into arr (a tree
+    node's samples, repeats allowed), default all. Returns (sums, counts):
+    sums a PaillierArray of shape (nfeat, nbins) - sums[f][b] what
+    groupby(bins[f]).sum() gives for group b, an empty bin the encryption of
+    0 - at the inputs' common exponent and in HBM when the input is; counts an
+    int64 array of the same shape. Needs only the public key.
+
+    The device path serves arrays with one exponent and nbins <= 4096; anything
+    else takes the drop-in's groupby sum feature by feature."""
+    from .paillier import PaillierCiphertext, ops, resident
+    from .paillier.array import NA_EXP, PaillierArray, _Fallback, _result
+    if isinstance(arr, np.ndarray) and arr.dtype == object and arr.ndim == 1 and \
+            all(isinstance(c, PaillierCiphertext) for c in arr):
+        arr = PaillierArray(arr)
+    if not isinstance(arr, PaillierArray):
+        raise TypeError("histograms takes a PaillierArray or an object array of PaillierCiphertext")
+    if arr.ndim != 1:
+        raise ValueError("histograms takes a 1-D array")
+    ctx = arr.context
+    if ctx is None:
+        raise ValueError("ciphertext array without a context: pass one to Paillier.ciphertext_from")
+    b = bins.to_numpy().T if hasattr(bins, "columns") else np.asarray(bins)
+    if b.ndim != 2 or b.shape[1] != arr.size or b.shape[0] < 1:
+        raise ValueError(f"histograms: bins must be [nfeat, {arr.size}]")
+    if b.dtype.kind not in "iu":
+        bf = b.astype(np.float64)
+        ok = np.isfinite(bf)
+        b = np.where(ok, bf, -1).astype(np.int64)
+    ids = b.astype(np.int64)
+    if nbins is None:
+        nbins = max(1, int(ids.max()) + 1) if ids.size else 1
+    nbins = int(nbins)
+    if nbins < 1:
+        raise ValueError("histograms: nbins must be positive")
+    ids = np.where((ids < 0) | (ids >= nbins), -1, ids)
+    if arr._has_na():
+        ids[:, arr.isna()] = -1
+    nfeat = ids.shape[0]
+    if rows is not None:
+        rows = np.asarray(rows, dtype=np.int64).reshape(-1)
+        if rows.size and (rows.min() < 0 or rows.max() >= arr.size):
+            raise IndexError("histograms: row index out of range")
+    sel = ids if rows is None else ids[:, rows]
+    try:
+        used = arr.exponents if rows is None else arr.exponents[rows]
+        used = used[used != NA_EXP]
+        if nbins > 4096 or (used.size and int(used.min()) != int(used.max())):
+            raise _Fallback()
+        e0 = int(used[0]) if used.size else 0
+        n2w = ops.n2w_of(ctx)
+        x = arr._aligned_words(n2w)
+        u16 = np.where(ids < 0, 0xFFFF, ids).astype(np.uint16)
+        exps = np.full(nfeat * nbins, e0, dtype=np.int32)
+        dev = resident.device_for(ctx, -1, x.size, 4 * n2w)
+        if dev is None:
+            w, cnt = ops.hist_words(ctx, x.words, u16, nbins, rows)
+            return _result(ctx, w, exps, (nfeat, nbins)), cnt.astype(np.int64).reshape(nfeat, nbins)
+        rd = None if rows is None else resident.upload_async(rows.astype(np.int32), dev)
+        out, cnt = resident.hist(ctx.device_key(dev), x._dw(dev), resident.upload(u16.view(np.int16), dev), nbins, rd)
+        counts = resident.download(cnt, np.int32).astype(np.int64).reshape(nfeat, nbins)
+        return PaillierArray.from_device(ctx, out, exps, (nfeat, nbins)), counts
+    except _Fallback:
+        sub = arr if rows is None else arr.take(rows)
+        parts = [sub._groupby_op(how="sum", has_dropped_na=True, min_count=0, ngroups=nbins, ids=sel[f])
+                 for f in range(nfeat)]
+        counts = np.stack([np.bincount(sel[f][sel[f] >= 0], minlength=nbins) for f in range(nfeat)]).astype(np.int64)
+        return PaillierArray._concat_same_type(parts).reshape((nfeat, nbins)), counts
+
+
 def unpack_columns(cols, count: int, num: int, k: int):
     """decrypt_unpack's index mapping: cols[t * num + i][j] (the num * k digit
     columns of the packed plaintexts) -> out[i][j * k + t], cut to count."""
