@@ -11,9 +11,9 @@
  * gives the thread-local message. A key handle is immutable after creation
  * and may be shared between threads; calls on distinct streams are reentrant.
  *
- * Ciphertext operands: the nine entry points that read ciphertext words -
+ * Ciphertext operands: the ten entry points that read ciphertext words -
  * xhe_decrypt, xhe_mulmod, xhe_powmod, xhe_pack, xhe_invert, xhe_segprod,
- * xhe_segscan, xhe_hist and xhe_multiexp (and their _host variants) - accept ANY value in
+ * xhe_segscan, xhe_hist, xhe_multiexp and xhe_bucketexp (and their _host variants) - accept ANY value in
  * [0, 2^(32 n2w))
  * in an operand row, not only residues below n^2: a received payload is not
  * reduced on its way into a device array (xhe_wire_decode, xhe_wire_scan and
@@ -256,6 +256,38 @@ int xhe_multiexp(const xhe_key* key, const uint32_t* bases_dev, int64_t nbases, 
                  const uint32_t* k_dev, int kw, int kbits, int64_t ncols, int64_t nterms, int win_bits,
                  uint32_t* out_dev, void* stream);
 
+/* The same product for a DENSE operand - every column takes every base once,
+ * the encrypted dot product over all samples of pearson/trainer.py:120-139 -
+ * by the bucket method, with no table and no inverted base:
+ *   out[j] = prod_{t < nterms} bases[t]^(s k[j*nterms + t]) mod n^2,
+ * s = -1 where neg[j*nterms + t] != 0 (neg_dev == NULL: every term positive).
+ * k: the magnitudes, kw words per term, < 2^kbits, [ncols][nterms][kw]. Per
+ * column and window of win_bits every term is multiplied into the bucket of
+ * its digit (xhe_hist's accumulation), the 2^win_bits - 1 buckets are folded
+ * as prod_d B_d^d, the windows by Horner, and the negative terms - a second
+ * bucket range - leave as one inversion per output: out = Pos * Neg^-1.
+ * bases: any values below 2^(32 n2w), taken mod n^2; out < n^2, word for word
+ * what xhe_multiexp gives on the inverted bases. A term with k = 0 contributes
+ * 1 whatever its sign byte; a column of zeros gives 1. XHE_ENOINV when some
+ * column's negative product has no inverse mod n^2 (a base sharing a factor
+ * with n under a negative non-zero scalar: the reference's ZeroDivisionError).
+ * win_bits: 0 = the planner's choice (paths.hpp bucket_window), else 1..11.
+ * XHE_EINVAL for a bad argument and for out overlapping bases. Needs no
+ * private key; runs in the batch n^2 shape for every key size. With neg_dev ==
+ * NULL it enqueues on `stream` and returns without synchronising; with a sign
+ * array it synchronises the stream once, inside the batch inversion (as
+ * xhe_invert does, to report XHE_ENOINV), and enqueues the last product after
+ * it. Timed as "k_bucketexp" under xhe_profile (its accumulation as
+ * "k_hist_tile", its fold alone as "k_bucket_fold"). */
+int xhe_bucketexp(const xhe_key* key, const uint32_t* bases_dev, int64_t nterms, const uint32_t* k_dev,
+                  const uint8_t* neg_dev, int kw, int kbits, int64_t ncols, int win_bits, uint32_t* out_dev,
+                  void* stream);
+/* Host only: 1 when the planner (paths.hpp multiexp_route) sends a dense
+ * product of nterms bases and ncols columns with exponents below 2^kbits, ninv
+ * of the bases under some negative scalar, to xhe_bucketexp; 0 when it stays
+ * on xhe_multiexp with the caller's base inversions. */
+int xhe_multiexp_route(const xhe_key* key, int64_t nterms, int64_t ncols, int kbits, int64_t ninv);
+
 /* Row moves of device ciphertext arrays (words per row), the element
  * selection and assignment of the flat arrays the drop-in returns (fancy
  * indexing and views of the reference's np.ndarray[object] results,
@@ -294,6 +326,8 @@ int xhe_rns_constants(const uint32_t* p_words, int pw, uint32_t* shared_out, uin
 /* Host-buffer variants (H2D -> kernels -> D2H on an internal stream). */
 int xhe_multiexp_host(const xhe_key* key, const uint32_t* bases, int64_t nbases, const int32_t* idx, const uint32_t* k,
                       int kw, int kbits, int64_t ncols, int64_t nterms, int win_bits, uint32_t* out);
+int xhe_bucketexp_host(const xhe_key* key, const uint32_t* bases, int64_t nterms, const uint32_t* k,
+                       const uint8_t* neg, int kw, int kbits, int64_t ncols, int win_bits, uint32_t* out);
 int xhe_segprod_host(const xhe_key* key, const uint32_t* c, const int32_t* d, int dmax, int64_t count,
                      const int64_t* seg_begin, int64_t nseg, uint32_t* out);
 int xhe_segscan_host(const xhe_key* key, const uint32_t* c, int64_t count, const int64_t* seg_begin, int64_t nseg,

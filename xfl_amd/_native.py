@@ -74,6 +74,11 @@ SIGNATURES = {
                                     ctypes.c_int64, ctypes.c_int, _vp, _vp]),
     "xhe_multiexp_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, ctypes.c_int,
                                          ctypes.c_int64, ctypes.c_int64, ctypes.c_int, _vp]),
+    "xhe_bucketexp": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64,
+                                     ctypes.c_int, _vp, _vp]),
+    "xhe_bucketexp_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, ctypes.c_int,
+                                          ctypes.c_int64, ctypes.c_int, _vp]),
+    "xhe_multiexp_route": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int64, ctypes.c_int, ctypes.c_int64]),
     "xhe_encrypt_host": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp]),
     "xhe_decrypt_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp]),
     "xhe_encrypt_f64_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
@@ -419,6 +424,7 @@ TABLE_ROW_WORDS = {2048: 64, 3072: 96, 4096: 128, 8192: 256}  # packed rows: xhe
 
 
 PUB_WAVE_MAX = 2048  # csrc/paths.hpp kPubWaveMax (tests/test_paths.py holds them equal): public non-DJN 2048-bit encrypts up to here run one block per element
+BUCKET_MIN_TERMS = 8192  # csrc/paths.hpp kBucketMinTerms (tests/test_bucket_plan.py holds them equal): the floor of the bucket matmul route
 
 XHE_WIN_SPLIT = 0x100  # include/xhe.h: floor(rand_bits/w) windows, the first rand_bits mod w of them w+1 bits
 

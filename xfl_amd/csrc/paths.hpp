@@ -283,6 +283,100 @@ inline Horner mexp_horner(int K, int lanes, int64_t ncols, const Pins& pins) {
   return K == 2048 && lanes == 16 && pins.mexp_wave && ncols <= kMexpWaveMax ? Horner::WAVE : Horner::LANES;
 }
 
+// ------------------------------------------------- multi-exponentiation
+// Two device paths serve out[j] = prod_t base^k: Straus windows with per-base
+// tables (xhe_multiexp) and buckets (xhe_bucketexp, bucket_dev.hpp). Both are
+// planned by product counts.
+//
+// Straus: window bits minimising the table products nbases (2^c - 2) plus the
+// gathered products ncols nterms ceil(kbits / c), with the tables (s4 words a
+// row) capped at kMexpTabBytes.
+constexpr int kMexpWinMax = 8;
+constexpr double kMexpTabBytes = 2147483648.0;
+
+struct MexpPlan {
+  int c;
+  double cost;  // products of the whole call
+};
+
+inline MexpPlan mexp_plan(int64_t nbases, int64_t ncols, int64_t nterms, int kbits, int s4) {
+  MexpPlan best{1, 1e300};
+  for (int c = 1; c <= kMexpWinMax; ++c) {
+    if (c > 1 && (double)(nbases << c) * s4 * 4 > kMexpTabBytes) break;
+    const double cost = (double)nbases * ((1 << c) - 2) + (double)ncols * nterms * ((kbits + c - 1) / c) +
+                        (double)ncols * kbits;
+    if (cost < best.cost) best = {c, cost};
+  }
+  return best;
+}
+
+inline int mexp_window(int64_t nbases, int64_t ncols, int64_t nterms, int kbits, int s4) {
+  return mexp_plan(nbases, ncols, nterms, kbits, s4).c;
+}
+
+// Buckets: per column and window of c bits one product per term, one per
+// (bin, tile) of the accumulation (k_hist_tile's slices and stage B, T tiles
+// of the tile hist_tile chooses for ncols * nwin features) and 2 * 2^c for the
+// fold:
+//   cost(c) = nwin (nterms + nbins T) + nwin 2 2^c,   nwin = ceil(kbits / c),
+//   nbins = (2^c - 1) * (sgn ? 2 : 1)   (<= 4094: c <= kBucketWinMax = 11)
+constexpr int kBucketWinMax = 11;
+
+inline int bucket_nbins(int c, bool sgn) { return ((1 << c) - 1) * (sgn ? 2 : 1); }
+
+inline double bucket_cost(int64_t nterms, int64_t ncols, int kbits, bool sgn, int c) {
+  const int nwin = (kbits + c - 1) / c > 1 ? (kbits + c - 1) / c : 1;
+  const int nbins = bucket_nbins(c, sgn);
+  const int64_t feat = ncols * nwin;
+  const int tile = hist_tile(nterms, (int)(feat < (1 << 30) ? feat : (1 << 30)), nbins);
+  const int64_t T = (nterms + tile - 1) / tile;
+  return (double)nwin * ((double)nterms + (double)nbins * T) + (double)nwin * 2 * (1 << c);
+}
+
+inline int bucket_window(int64_t nterms, int64_t ncols, int kbits, bool sgn) {
+  int best = 1;
+  double best_cost = 1e300;
+  for (int c = 1; c <= kBucketWinMax; ++c) {
+    const double cost = bucket_cost(nterms, ncols, kbits, sgn, c);
+    if (cost < best_cost) {
+      best_cost = cost;
+      best = c;
+    }
+  }
+  return best;
+}
+
+// Which of the two serves a dense product of nterms bases and ncols columns,
+// ninv of the bases under some negative scalar: Straus pays for ninv extra
+// bases and their batch inversion (kInvProducts each: into Montgomery form,
+// up and down the product tree, out again). Buckets only from
+// kBucketMinTerms terms and a modelled saving of kBucketMinSaving: the
+// regression steps (2048 x 15) and every small shape stay where they were.
+// Measured at 2048 bits (DESIGN "Bucket multi-exponentiation",
+// profiles/r25/bucketexp/): at 2048 x 15 x 60 bits (model 1.25) Straus is
+// 1.86x faster; buckets are faster, beyond the spread, at 8197 x 2 (24 bits,
+// model 1.98: 1.13x; 60 bits, model 1.77: 1.18x), at 100 k x 16 x 24 (model
+// 2.49) 1.38x and at 1 M x 16 x 24 (model 7.6) 4.14x. The floor of 8192 terms
+// stands between the first two; the saving is set just below the lowest
+// modelled ratio at which buckets were measured faster. The model overstates
+// the saving: per product a bucket row costs more than a gathered table row.
+enum class MexpRoute {
+  STRAUS,   // xhe_multiexp (the caller inverts the bases of negative terms)
+  BUCKETS,  // xhe_bucketexp
+};
+constexpr int64_t kBucketMinTerms = 8192;  // mirrored as xfl_amd._native.BUCKET_MIN_TERMS
+constexpr double kBucketMinSaving = 1.75;
+constexpr int kInvProducts = 4;
+
+inline MexpRoute multiexp_route(int64_t nterms, int64_t ncols, int kbits, int64_t ninv, int s4) {
+  if (nterms < kBucketMinTerms || ncols < 1) return MexpRoute::STRAUS;
+  const int kb = kbits > 1 ? kbits : 1;
+  const double straus = mexp_plan(nterms + ninv, ncols, nterms, kb, s4).cost + (double)kInvProducts * ninv;
+  const bool sgn = ninv > 0;
+  const double buckets = (double)ncols * bucket_cost(nterms, ncols, kb, sgn, bucket_window(nterms, ncols, kb, sgn));
+  return straus >= kBucketMinSaving * buckets ? MexpRoute::BUCKETS : MexpRoute::STRAUS;
+}
+
 // ----------------------------------------------------------------- decrypt
 // Decided by the whole call's count: every launch chunk takes the same path.
 enum class Dec {

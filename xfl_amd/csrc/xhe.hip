@@ -31,6 +31,7 @@
 #include "enc_obf_dev.hpp"
 #include "wire_unpack.hpp"
 #include "hist_dev.hpp"
+#include "bucket_dev.hpp"
 
 using namespace xhe;
 
@@ -1360,16 +1361,16 @@ void segscan_impl(const xhe_key* k, const uint32_t* c, int64_t count, const int6
 
 // Fused multi-feature histogram (hist_dev.hpp): stage A leaves one Montgomery
 // row per (feature, bin, tile), stage B folds the T tiles of every (feature,
-// bin) - uniform segments: no plan upload, no host sync - and packs the
-// words. The features run in groups whose partial and parked rows fit kChunk
-// residue rows; every buffer is freed in stream order.
-template <class Sh>
-void hist_impl(const xhe_key* k, const uint32_t* c, const uint16_t* bins, int64_t bins_stride, int nfeat, int nbins,
-               const int32_t* rows_idx, int64_t count, int tile_rows, uint32_t* out, int32_t* cnt, hipStream_t s) {
+// bin) - uniform segments: no plan upload, no host sync. The features run in
+// groups whose partial and parked rows fit kChunk residue rows; every buffer
+// is freed in stream order. hist_rows hands each group's Montgomery rows
+// ([S4][gf * nbins], column fl * nbins + b) to sink(f0, gf, rows): xhe_hist
+// packs their words, xhe_bucketexp folds them as buckets.
+template <class Sh, class Sink>
+void hist_rows(const xhe_key* k, const uint32_t* c, const uint16_t* bins, int64_t bins_stride, int nfeat, int nbins,
+               const int32_t* rows_idx, int64_t count, int tile_rows, int32_t* cnt, hipStream_t s, Sink&& sink) {
   using MN2 = typename Sh::MN2;
   const int S4 = MN2::S4;
-  auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
-  ProfScope ps("k_hist", s);
   if (!tile_rows) tile_rows = paths::hist_tile(count, nfeat, nbins);
   const int64_t T = std::max<int64_t>(1, (count + tile_rows - 1) / tile_rows);
   const int gmax = paths::hist_group(nfeat, nbins, tile_rows, T, kChunk);
@@ -1402,27 +1403,90 @@ void hist_impl(const xhe_key* k, const uint32_t* c, const uint16_t* bins, int64_
         cur = reduce_segments<Sh, MN2>(k, std::move(part), ncols, std::move(seg), s);
       }
     }
-    launch(k_from_mont_rows<MN2>, blocks(nseg), dim3(256), s, k->kd, n2h<MN2>(k).N, cur.as<uint32_t>(), nseg,
-           out + (size_t)f0 * nbins * k->n2w);
+    sink(f0, gf, cur);
   }
 }
 
-// Window bits for a multi-exponentiation: minimise table products
-// nbases*(2^c - 2) plus gathered products ncols*nterms*ceil(kbits/c), with the
-// tables capped at ~2 GiB.
-int mexp_window(int64_t nbases, int64_t ncols, int64_t nterms, int kbits, int s4) {
-  int best = 1;
-  double best_cost = 1e300;
-  for (int c = 1; c <= 8; ++c) {
-    if (c > 1 && (double)(nbases << c) * s4 * 4 > 2147483648.0) break;
-    double cost = (double)nbases * ((1 << c) - 2) + (double)ncols * nterms * ((kbits + c - 1) / c) +
-                  (double)ncols * kbits;
-    if (cost < best_cost) {
-      best_cost = cost;
-      best = c;
-    }
+template <class Sh>
+void hist_impl(const xhe_key* k, const uint32_t* c, const uint16_t* bins, int64_t bins_stride, int nfeat, int nbins,
+               const int32_t* rows_idx, int64_t count, int tile_rows, uint32_t* out, int32_t* cnt, hipStream_t s) {
+  using MN2 = typename Sh::MN2;
+  auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
+  ProfScope ps("k_hist", s);
+  hist_rows<Sh>(k, c, bins, bins_stride, nfeat, nbins, rows_idx, count, tile_rows, cnt, s,
+                [&](int f0, int gf, const DevBuf& cur) {
+                  const int64_t nseg = (int64_t)gf * nbins;
+                  launch(k_from_mont_rows<MN2>, blocks(nseg), dim3(256), s, k->kd, n2h<MN2>(k).N, cur.as<uint32_t>(),
+                         nseg, out + (size_t)f0 * nbins * k->n2w);
+                });
+}
+
+// Bucket multi-exponentiation (bucket_dev.hpp). The columns run in groups
+// whose digit matrix stays within kBucketDigitCap ids (and hist_rows groups
+// the (column, window) features within kChunk rows below that); every group
+// leaves its folds in P, the Horner and the finish run once over all columns.
+constexpr int64_t kBucketDigitCap = 64 * kChunk;  // uint16 ids: 128 MiB
+
+template <class Sh>
+int bucketexp_impl(const xhe_key* k, const uint32_t* bases, int64_t nterms, const uint32_t* kx, const uint8_t* neg,
+                   int kw, int kbits, int64_t ncols, int c, uint32_t* out, hipStream_t s) {
+  using MN2 = typename Sh::MN2;
+  const int S4 = MN2::S4;
+  auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
+  const int nsign = neg ? 2 : 1;
+  const int nwin = std::max(1, (kbits + c - 1) / c);
+  const int nbins = paths::bucket_nbins(c, neg != nullptr);
+  const int64_t stride = (nterms + 63) & ~(int64_t)63;  // rows of the digit matrix start on 128-byte lines
+  const int64_t gcols =
+      std::max<int64_t>(1, std::min<int64_t>(std::min<int64_t>(ncols, 65535), kBucketDigitCap / (stride * nwin)));
+  const int64_t hcols = nsign * ncols, pcols = hcols * nwin;
+  // (one column's digits alone must fit the cap; hist_rows has a limit of its
+  // own on a feature group's partial rows and reports it under xhe_hist's name)
+  if (pcols > INT32_MAX || gcols * nwin > INT32_MAX || stride * nwin > kBucketDigitCap)
+    throw std::logic_error("xhe_bucketexp: problem too large for one call");
+  ProfScope ps("k_bucketexp", s);
+  // (declared in reverse, filled in allocation order: DevBuf's note)
+  DevBuf ninv, hw, sq, P, digits;
+  digits = DevBuf((size_t)gcols * nwin * stride * 2, s, DevBuf::kAsync);
+  P = DevBuf((size_t)S4 * pcols * 4, s, DevBuf::kAsync);
+  for (int64_t c0 = 0; c0 < ncols; c0 += gcols) {
+    const int64_t gc = std::min(gcols, ncols - c0);
+    launch(k_bucket_digits, dim3((unsigned)((nterms + 255) / 256), (unsigned)gc), dim3(256), s,
+           kx + (size_t)c0 * nterms * kw, neg ? neg + (size_t)c0 * nterms : nullptr, kw, nterms, c, nwin,
+           digits.as<uint16_t>(), stride);
+    // (the tile is hist_tile's for this group's gc * nwin features; the cost
+    // model sizes it for all ncols * nwin, the same while one group holds every column)
+    hist_rows<Sh>(k, bases, digits.as<uint16_t>(), stride, (int)(gc * nwin), nbins, nullptr, nterms, 0, nullptr, s,
+                  [&](int f0, int gf, const DevBuf& cur) {
+                    ProfScope pf("k_bucket_fold", s);
+                    const unsigned nblk = (unsigned)(gf * nsign);
+                    DevBuf frows((size_t)nblk * (256 / MN2::TPI) * S4 * 4, s, DevBuf::kAsync);
+                    hipLaunchKernelGGL((k_bucket_fold<MN2>), dim3(nblk), dim3(256), (size_t)bucket_fold_lds<MN2>(), s,
+                                       k->kd, n2h<MN2>(k).N, cur.as<uint32_t>(), (int)((int64_t)gf * nbins), nbins, c,
+                                       nsign, frows.as<uint32_t>(), P.as<uint32_t>(), (int)pcols, c0 * nwin + f0,
+                                       ncols * nwin);
+                    HIPCHK(hipGetLastError());
+                  });
   }
-  return best;
+  sq = DevBuf((size_t)S4 * hcols * 4, s, DevBuf::kAsync);
+  uint32_t* hout = out;
+  if (neg) {
+    hw = DevBuf((size_t)hcols * k->n2w * 4, s, DevBuf::kAsync);
+    hout = hw.as<uint32_t>();
+  }
+  {
+    ProfScope ph("k_mexp_horner", s);
+    launch(k_mexp_horner<MN2>, blocks(hcols), dim3(256), s, k->kd, n2h<MN2>(k).N, P.as<uint32_t>(), nwin, c, hcols,
+           sq.as<uint32_t>(), hout);
+  }
+  if (!neg) return XHE_OK;
+  ninv = DevBuf((size_t)ncols * k->n2w * 4, s, DevBuf::kAsync);
+  // (synchronises the stream: the batch inversion's one scalar inverse is the host's)
+  const int rc = invert_impl<Sh, MN2>(k, hout + (size_t)ncols * k->n2w, ncols, ninv.as<uint32_t>(), s);
+  if (rc != XHE_OK) return rc;
+  launch((k_bucket_finish<MN2, Sh::RW2>), blocks(ncols), dim3(256), s, k->kd, n2h<MN2>(k).N, hout, ninv.as<uint32_t>(),
+         ncols, out);
+  return XHE_OK;
 }
 
 // Multi-exponentiation out[j] = prod_t bases[idx[j][t]]^k[j][t] mod n^2.
@@ -2771,7 +2835,7 @@ int xhe_multiexp(const xhe_key* key, const uint32_t* bases_dev, int64_t nbases, 
       using Sh = decltype(sh);
       return row ? Sh::MN2X::S4 : Sh::MN2::S4;
     });
-    const int c = win_bits ? win_bits : mexp_window(nbases, ncols, nterms, std::max(kbits, 1), s4);
+    const int c = win_bits ? win_bits : paths::mexp_window(nbases, ncols, nterms, std::max(kbits, 1), s4);
     const int kb = std::max(kbits, 1);
     hipStream_t hs = (hipStream_t)stream;
     with_shape(key->K, [&](auto sh) {
@@ -2806,6 +2870,67 @@ int xhe_multiexp_host(const xhe_key* key, const uint32_t* bases, int64_t nbases,
     HIPCHK(hipMemcpyAsync(out, dout.p, (size_t)ncols * key->n2w * 4, hipMemcpyDeviceToHost, st.s));
     HIPCHK(hipStreamSynchronize(st.s));
     return XHE_OK;
+  });
+}
+
+namespace {
+int bucketexp_args(const xhe_key* key, const uint32_t* bases, int64_t nterms, const uint32_t* k, int kw, int kbits,
+                   int64_t ncols, int win_bits, const uint32_t* out, const char* who) {
+  if (!key || nterms <= 0 || ncols <= 0 || !bases || !k || !out || kw <= 0 || kbits < 0 || kbits > 32 * kw ||
+      win_bits < 0 || win_bits > paths::kBucketWinMax)
+    return fail(XHE_EINVAL, std::string(who) + ": bad argument");
+  if (nterms > (int64_t)1 << 30 || ncols > (int64_t)1 << 24)
+    return fail(XHE_EINVAL, std::string(who) + ": problem too large for one call");
+  if (out < bases + (size_t)nterms * key->n2w && bases < out + (size_t)ncols * key->n2w)
+    return fail(XHE_EINVAL, std::string(who) + ": out overlaps bases");
+  return XHE_OK;
+}
+}  // namespace
+
+int xhe_bucketexp(const xhe_key* key, const uint32_t* bases_dev, int64_t nterms, const uint32_t* k_dev,
+                  const uint8_t* neg_dev, int kw, int kbits, int64_t ncols, int win_bits, uint32_t* out_dev,
+                  void* stream) {
+  return guarded([&]() -> int {
+    if (int rc = bucketexp_args(key, bases_dev, nterms, k_dev, kw, kbits, ncols, win_bits, out_dev, "xhe_bucketexp"))
+      return rc;
+    DevGuard dg(key->device);
+    const int kb = std::max(kbits, 1);
+    const int c = win_bits ? win_bits : paths::bucket_window(nterms, ncols, kb, neg_dev != nullptr);
+    return with_shape(key->K, [&](auto sh) -> int {
+      return bucketexp_impl<decltype(sh)>(key, bases_dev, nterms, k_dev, neg_dev, kw, kb, ncols, c, out_dev,
+                                          (hipStream_t)stream);
+    });
+  });
+}
+
+int xhe_bucketexp_host(const xhe_key* key, const uint32_t* bases, int64_t nterms, const uint32_t* k,
+                       const uint8_t* neg, int kw, int kbits, int64_t ncols, int win_bits, uint32_t* out) {
+  return guarded([&]() -> int {
+    if (int rc = bucketexp_args(key, bases, nterms, k, kw, kbits, ncols, win_bits, out, "xhe_bucketexp_host"))
+      return rc;
+    DevGuard dg(key->device);
+    Stream st;
+    const size_t bb = (size_t)nterms * key->n2w * 4, kb = (size_t)ncols * nterms * kw * 4,
+                 nb = (size_t)ncols * nterms, ob = (size_t)ncols * key->n2w * 4;
+    DevBuf db(bb, st.s), dk(kb, st.s), dn(neg ? nb : 0, st.s), dout(ob, st.s);
+    HIPCHK(hipMemcpyAsync(db.p, bases, bb, hipMemcpyHostToDevice, st.s));
+    HIPCHK(hipMemcpyAsync(dk.p, k, kb, hipMemcpyHostToDevice, st.s));
+    if (neg) HIPCHK(hipMemcpyAsync(dn.p, neg, nb, hipMemcpyHostToDevice, st.s));
+    int rc = xhe_bucketexp(key, db.as<uint32_t>(), nterms, dk.as<uint32_t>(), neg ? dn.as<uint8_t>() : nullptr, kw,
+                           kbits, ncols, win_bits, dout.as<uint32_t>(), st.s);
+    if (rc != XHE_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    return XHE_OK;
+  });
+}
+
+int xhe_multiexp_route(const xhe_key* key, int64_t nterms, int64_t ncols, int kbits, int64_t ninv) {
+  return guarded([&]() -> int {
+    if (!key || nterms <= 0 || ncols <= 0 || kbits < 0 || ninv < 0)
+      return fail(XHE_EINVAL, "xhe_multiexp_route: bad argument");
+    const int s4 = with_shape(key->K, [&](auto sh) -> int { return decltype(sh)::MN2::S4; });
+    return paths::multiexp_route(nterms, ncols, kbits, ninv, s4) == paths::MexpRoute::BUCKETS ? 1 : 0;
   });
 }
 

@@ -1383,6 +1383,12 @@ def _matmul_run(A, X, cshape, xshape, left, out_shape):
     A = A._aligned_words(ops.n2w_of(ctx))
     kw_, neg, e_k = _encode_scalars(ctx, X)
     kvec = kw_.ndim == 1  # int64 |k| from the vectorised encoder
+    r = _matmul_buckets(ctx, A, kw_, neg, e_k, cshape, xshape, left)
+    if r is not None:
+        words, emin = r
+        if isinstance(words, np.ndarray):
+            return _result(ctx, words, emin.astype(np.int32), out_shape)
+        return PaillierArray.from_device(ctx, words, emin.astype(np.int32), out_shape)
     bidx, sidx = _matmul_terms(cshape, xshape, left)
     need_inv, idx, shift, emin = _matmul_plan(A._e, neg, e_k, bidx, sidx)
     dev = _res_dev(ctx, A)
@@ -1411,17 +1417,99 @@ def _matmul_run(A, X, cshape, xshape, left, out_shape):
     return _result(ctx, r, emin.astype(np.int32), out_shape)
 
 
+def _matmul_buckets(ctx, A, kw_, neg, e_k, cshape, xshape, left):
+    """The bucket route of a ciphertext matmul (xhe_bucketexp), or None where
+    the planner keeps the product on xhe_multiexp. Every product _matmul
+    accepts is dense per ciphertext row (left: row m of enc[M, B] against the
+    D columns of X; right: column j of enc[B, D] against the M rows of X), so
+    there is no index plan and no inverted base: one call per ciphertext row
+    with the magnitudes |k| << shift and the signs, exponents aligned per
+    output as _matmul_plan does. -> (words [M * D, n2w] in C order of the
+    outputs, host or device as the operand; emin int64 [M * D])"""
+    if left:
+        (M, Bn), D = cshape, xshape[1]
+        nrows, ncols = M, D
+    else:
+        (M, Bn), D = xshape, cshape[1]
+        nrows, ncols = D, M
+    if Bn < nat.BUCKET_MIN_TERMS:  # (before any device is asked: the planner's floor)
+        return None
+    kvec = kw_.ndim == 1
+    # scalars as [ncols, B]: column j of X (left), row m of X (right)
+    smap = np.arange(Bn * D).reshape(Bn, D).T if left else np.arange(M * Bn).reshape(M, Bn)
+    negs = np.asarray(neg, dtype=bool)[smap]
+    eks = np.asarray(e_k, dtype=np.int64)[smap]
+    signed = bool(negs.any())
+    ninv = int(negs.any(axis=0).sum())
+    cexp = np.asarray(A._e, dtype=np.int64).reshape(cshape)
+    dev = _res_dev(ctx, A)
+    if dev is not None:
+        dk = ctx.device_key(dev)
+        base_all = A._dw(dev)
+    kmat = kw_[smap] if kvec else None
+    ks = None if kvec else nat.words_to_ints(kw_)
+    outs, emins = [], []
+    for r in range(nrows):
+        ce = cexp[r] if left else cexp[:, r]
+        ex = ce[None, :] + eks
+        emin = ex.min(axis=1)
+        shift = ex - emin[:, None]
+        if not kvec:
+            exps = [ks[t] << int(d) for t, d in zip(smap.reshape(-1), shift.reshape(-1))]
+            kbits = max(1, max(k.bit_length() for k in exps))
+        # the route is asked on row 0's exponent width, before any word is built:
+        # a product the planner keeps on Straus pays for these few vectors only
+        if r == 0 and not ops.multiexp_route(ctx, Bn, ncols, _shifted_kbits(kmat, shift) if kvec else kbits, ninv):
+            return None
+        if kvec:
+            kwords, kbits = _shifted_words(kmat, shift)
+        else:
+            kwords = nat.ints_to_words(exps, (kbits + 31) // 32)
+        kwords = kwords.reshape(ncols, Bn, -1)
+        rows = np.arange(r * Bn, (r + 1) * Bn) if left else np.arange(r, Bn * D, D)
+        if dev is not None:
+            bases = base_all[r * Bn:(r + 1) * Bn] if left else resident.take(base_all, rows)
+            outs.append(resident.bucketexp(dk, bases, kwords, negs if signed else None, kbits))
+        else:
+            outs.append(ops.bucketexp_words(ctx, A._w[rows], kwords, negs if signed else None, kbits))
+        emins.append(emin)
+    # outputs in C order (m, j): left rows are m already; right has j outermost
+    if left or nrows == 1 or ncols == 1:
+        order = None
+    else:
+        order = np.arange(nrows * ncols).reshape(nrows, ncols).T.reshape(-1)
+    emin = np.concatenate(emins)
+    if dev is not None:
+        words = outs[0] if len(outs) == 1 else resident.cat(outs)
+        if order is not None:
+            words = resident.take(words, order)
+    else:
+        words = outs[0] if len(outs) == 1 else np.concatenate(outs)
+        if order is not None:
+            words = words[order]
+    return words, (emin if order is None else emin[order])
+
+
+def _shifted_kbits(k, shift):
+    """the kbits _shifted_words(k, shift) returns, without building the words"""
+    k = k.reshape(-1).astype(np.uint64)
+    nz = k != 0
+    if not nz.any():
+        return 1
+    kb = np.frexp(k[nz].astype(np.float64))[1].astype(np.int64)  # >= the bit length (float rounding up)
+    return int((kb + shift.reshape(-1).astype(np.int64)[nz]).max())
+
+
 def _shifted_words(k, shift):
     """words of k << shift for int64 k >= 0 (< 2^63) and shifts >= 0, same
     shape -> (uint32 [k.size, kw], kbits) with every value < 2^kbits: the
     aligned multi-exponentiation exponents without a Python int per term"""
+    kbits = _shifted_kbits(k, shift)
     k = k.reshape(-1).astype(np.uint64)
     s = shift.reshape(-1).astype(np.int64)
     nz = k != 0
     if not nz.any():
         return np.zeros((k.size, 1), np.uint32), 1
-    kb = np.frexp(k[nz].astype(np.float64))[1].astype(np.int64)  # >= the bit length (float rounding up)
-    kbits = int((kb + s[nz]).max())
     kw = (kbits + 31) // 32
     out = np.zeros((k.size, kw + 3), np.uint32)
     w0 = np.where(nz, s // 32, 0)  # zero terms may carry any shift

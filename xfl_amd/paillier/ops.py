@@ -516,6 +516,37 @@ def multiexp_words(ctx, bw, idx, kw_, kbits, win_bits=0):
     return out
 
 
+def bucketexp_words(ctx, bw, kwords, neg, kbits, win_bits=0):
+    """out[j] = prod_t bases[t]^(+-k[j][t]) mod n^2 by the bucket method (one
+    xhe_bucketexp call): bw [nterms, n2w] words, kwords [ncols, nterms, kw]
+    magnitudes below 2^kbits, neg [ncols, nterms] (non-zero: negative scalar) or
+    None. ZeroDivisionError when a column's negative product has no inverse."""
+    bw = _u32(bw)
+    kwords = _u32(kwords)
+    if kwords.ndim != 3 or kwords.shape[1] != bw.shape[0] or 0 in kwords.shape:
+        raise ValueError("bucketexp: kwords must be [ncols, nterms, kw] with one term per base")
+    ncols, nterms, kw = kwords.shape
+    if neg is not None:
+        neg = np.ascontiguousarray(neg, dtype=np.uint8)
+        if neg.shape != (ncols, nterms):
+            raise ValueError("bucketexp: neg must be [ncols, nterms]")
+    out = np.empty((ncols, n2w_of(ctx)), dtype=np.uint32)
+    dk = ctx.device_key(ctx.own_device())
+    nat.check(nat.lib().xhe_bucketexp_host(dk.handle, _vp(bw), nterms, _vp(kwords), _vp(neg) if neg is not None else None,
+                                           kw, int(kbits), ncols, int(win_bits), _vp(out)), "bucketexp")
+    return out
+
+
+def multiexp_route(ctx, nterms, ncols, kbits, ninv):
+    """True when the planner sends a dense product of this shape (ninv bases
+    under some negative scalar) to the bucket method, False for Straus"""
+    dk = ctx.device_key(ctx.own_device())
+    rc = nat.lib().xhe_multiexp_route(dk.handle, int(nterms), int(ncols), int(kbits), int(ninv))
+    if rc < 0:
+        nat.check(rc, "multiexp_route")
+    return rc == 1
+
+
 # ------------------------------------------------------------ int forms
 def encrypt_floats(ctx, xs, precision, max_exponent, obfuscation):
     """-> (raw ints, exponents, status)"""

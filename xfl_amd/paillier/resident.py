@@ -788,6 +788,33 @@ def multiexp(dk, bases, idx, kw_, kbits, win_bits=0):
     return out
 
 
+def bucketexp(dk, bases, kwords, neg, kbits, win_bits=0):
+    """out[j] = prod_t bases[t]^(+-k[j][t]) mod n^2 on device bases [nterms,
+    n2w] by the bucket method (xhe_bucketexp): kwords host uint32 [ncols,
+    nterms, kw] magnitudes below 2^kbits, neg host bool [ncols, nterms] (True:
+    the term's scalar is negative) or None -> device [ncols, n2w].
+    ZeroDivisionError when a column's negative product has no inverse."""
+    torch = _torch()
+    dev = dk.device
+    kwords = np.ascontiguousarray(kwords, dtype=np.uint32)
+    if kwords.ndim != 3 or kwords.shape[1] != bases.shape[0] or 0 in kwords.shape:
+        raise ValueError("bucketexp: kwords must be [ncols, nterms, kw] with one term per base")
+    ncols, nterms, kw = kwords.shape
+    dneg = None
+    if neg is not None:
+        neg = np.ascontiguousarray(neg, dtype=np.uint8)
+        if neg.shape != (ncols, nterms):
+            raise ValueError("bucketexp: neg must be [ncols, nterms]")
+        dneg = upload_small(neg, dev)
+    dkw = upload_small(kwords, dev)
+    with _On(dev):
+        out = torch.empty((ncols, dk.n2w), dtype=torch.int32, device=f"cuda:{dev}")
+        src = bases.contiguous()
+    nat.check(nat.lib().xhe_bucketexp(dk.handle, _dp(src), nterms, _dp(dkw), _dp(dneg), kw, int(kbits), ncols,
+                                      int(win_bits), _dp(out), _sp(dev)), "bucketexp")
+    return out
+
+
 def take(c, idx):
     """rows of device c at host indices idx (a new tensor; xhe_gather_rows, so
     no torch kernel is loaded on first use - a first index_select of a new
