@@ -11,9 +11,10 @@
  * gives the thread-local message. A key handle is immutable after creation
  * and may be shared between threads; calls on distinct streams are reentrant.
  *
- * Ciphertext operands: the ten entry points that read ciphertext words -
+ * Ciphertext operands: the eleven entry points that read ciphertext words -
  * xhe_decrypt, xhe_mulmod, xhe_powmod, xhe_pack, xhe_invert, xhe_segprod,
- * xhe_segscan, xhe_hist, xhe_multiexp and xhe_bucketexp (and their _host variants) - accept ANY value in
+ * xhe_segscan, xhe_hist, xhe_hist_level, xhe_multiexp and xhe_bucketexp (and
+ * their _host variants) - accept ANY value in
  * [0, 2^(32 n2w))
  * in an operand row, not only residues below n^2: a received payload is not
  * reduced on its way into a device array (xhe_wire_decode, xhe_wire_scan and
@@ -241,6 +242,30 @@ int xhe_hist(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const ui
              int nfeat, int nbins, const int32_t* rows_dev, int64_t count, int tile_rows, uint32_t* out_dev,
              int32_t* cnt_dev, void* stream);
 
+/* Level-wise histogram: xhe_hist for every node of a tree level in one call
+ * (cal_hist_for_node over all nodes of a level), keyed by (node, feature,
+ * bin), from one pass over the level's rows - no gather, no sort of
+ * ciphertext rows, no host plan, no host synchronisation. c, bins,
+ * bins_stride, nfeat, nbins, tile_rows: as xhe_hist. node[r]: the level-local
+ * node slot of ciphertext row r; an id >= nnodes (0xFFFF by convention: the
+ * row sits in a finished leaf or was not sampled) skips the row for every
+ * feature. There is no row-id list: the node array is the selection.
+ *   out[((v * nfeat + f) * nbins + b) * n2w ..] = prod c[r] mod n^2 over the
+ *     rows with node[r] == v and bins[f][r] == b, below n^2; an empty (node,
+ *     feature, bin) gives 1;
+ *   cnt[(v * nfeat + f) * nbins + b] = the number of such rows (cnt may be NULL).
+ * A bin id >= nbins drops the row for that feature only. c: any values below
+ * 2^(32 n2w), taken mod n^2. No exponent argument, no private key. tile_rows
+ * 0 = the planner's choice (paths.hpp level_tile). n_rows == 0 writes ones and
+ * zero counts. XHE_EINVAL: nnodes or nbins outside [1, 4096], nfeat < 1, a
+ * negative n_rows, bins_stride < n_rows, tile_rows outside its set, out
+ * overlapping c. Runs in the batch n^2 shape for every key size; enqueues on
+ * `stream` and returns without synchronising. Timed as "k_hist_level" under
+ * xhe_profile (its stages as "k_level_order", "k_level_tile", "k_level_fold"). */
+int xhe_hist_level(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const uint16_t* bins_dev,
+                   int64_t bins_stride, int nfeat, int nbins, const uint16_t* node_dev, int nnodes, int tile_rows,
+                   uint32_t* out_dev, int32_t* cnt_dev, void* stream);
+
 /* Encrypted matrix-vector product as a multi-exponentiation: the object-dtype
  * np.matmul(enc[B], X[B, D]) of logistic_regression/trainer.py:166 (and
  * linear_regression/trainer.py:207, poisson_regression/trainer.py:267,
@@ -336,6 +361,10 @@ int xhe_segscan_host(const xhe_key* key, const uint32_t* c, int64_t count, const
 int xhe_hist_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins, int64_t bins_stride,
                   int nfeat, int nbins, const int32_t* rows, int64_t count, int tile_rows, uint32_t* out,
                   int32_t* cnt);
+/* xhe_hist_level on host buffers. */
+int xhe_hist_level_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                        int64_t bins_stride, int nfeat, int nbins, const uint16_t* node, int nnodes, int tile_rows,
+                        uint32_t* out, int32_t* cnt);
 /* xhe_pack: count ciphertexts in, ceil(count/k) out. */
 int xhe_pack_host(const xhe_key* key, const uint32_t* c, int64_t count, int k, int shift_bits, uint32_t* out);
 int xhe_mulmod_host(const xhe_key* key, const uint32_t* a, const int32_t* ea, const uint32_t* b, const int32_t* eb,

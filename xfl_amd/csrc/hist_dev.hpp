@@ -72,17 +72,17 @@ constexpr int hist_waves() {
   return scan_waves<MN2>();
 }
 
-// Block x = t * gf + fl: tile t of feature f0 + fl (the features of one tile
-// are neighbours, so the tile's ciphertext rows are read from HBM once and
-// from L2 by the others). part: [S4][gf * nbins * T] strided rows, column
-// (fl * nbins + b) * T + t. rows_idx: the caller's row ids (trusted < n_rows)
-// or null (element i is row i). cnt_out: zeroed before the launch, or null.
+// One block's work, shared by k_hist_tile and k_level_tile (hist_level_dev.hpp):
+// the m elements base .. base + m - 1 of the call (row rows_idx[base + i], or
+// base + i without row ids) by the bin ids fb[row] of one feature. The bin's
+// partial row goes to column bin * bin_stride of mypart ([S4][ncols] strided
+// rows), its count is added to cnt_f[bin] (null: no counts); mypark: the
+// block's tile_rows / kHistParkDiv parked rows.
 template <class MN2, int PW>
-__global__ void __launch_bounds__(256, hist_waves<MN2>())
-    k_hist_tile(KeyDev key, const uint32_t* __restrict__ Nn2, const uint32_t* __restrict__ words,
-                const uint16_t* __restrict__ bins, int64_t bins_stride, int nbins,
-                const int32_t* __restrict__ rows_idx, int64_t count, int tile_rows, int f0, int gf, int64_t T,
-                uint32_t* __restrict__ part, uint32_t* park, int32_t* __restrict__ cnt_out) {
+XHE_DEV void hist_tile_block(KeyDev key, const uint32_t* __restrict__ Nn2, const uint32_t* __restrict__ words,
+                             const uint16_t* __restrict__ fb, int nbins, const int32_t* __restrict__ rows_idx,
+                             int64_t base, int m, int tile_rows, uint32_t* mypart, int64_t bin_stride, int ncols,
+                             uint32_t* mypark, int32_t* __restrict__ cnt_f) {
   extern __shared__ uint32_t hist_lds[];
   uint32_t* A = hist_lds;       // count | start << 16, later the bin's parked rows still to combine
   uint32_t* B = A + nbins;      // scatter cursor, later the bin's first parked row
@@ -92,11 +92,6 @@ __global__ void __launch_bounds__(256, hist_waves<MN2>())
 
   constexpr int S4 = MN2::S4, NGRP = 256 / MN2::TPI;
   const int tid = threadIdx.x, grp = tid / MN2::TPI;
-  const int64_t t = blockIdx.x / gf;
-  const int fl = (int)(blockIdx.x - t * gf);
-  const int64_t base = t * tile_rows;
-  const int m = (int)(count - base < tile_rows ? count - base : tile_rows);
-  const uint16_t* fb = bins + (size_t)(f0 + fl) * bins_stride;
   auto row_of = [&](int i) -> int64_t { return rows_idx ? (int64_t)rows_idx[base + i] : base + i; };
 
   for (int b = tid; b < nbins; b += 256) A[b] = 0;
@@ -112,7 +107,7 @@ __global__ void __launch_bounds__(256, hist_waves<MN2>())
     const uint32_t start = n ? atomicAdd(&s_total, n) : 0u;
     A[b] = n | (start << 16);  // n <= 8192 and start < 8192
     B[b] = start;
-    if (cnt_out && n) atomicAdd(&cnt_out[(size_t)(f0 + fl) * nbins + b], (int)n);
+    if (cnt_f && n) atomicAdd(&cnt_f[b], (int)n);
   }
   __syncthreads();
   for (int i = tid; i < m; i += 256) {
@@ -134,9 +129,6 @@ __global__ void __launch_bounds__(256, hist_waves<MN2>())
   M.init(Nn2, n2dev<MN2>(key).n0inv);
   uint32_t b[MN2::L];
   const uint32_t* rpow = n2dev<MN2>(key).Rpow;
-  uint32_t* mypark = park + (size_t)blockIdx.x * (tile_rows / kHistParkDiv) * S4;
-  const int ncols = (int)((int64_t)gf * nbins * T);
-  uint32_t* mypart = part + (int64_t)fl * nbins * T + t;
 
   const int nitems = nbins + (int)s_nwork;
   for (int it = grp; it < nitems; it += NGRP) {
@@ -160,7 +152,7 @@ __global__ void __launch_bounds__(256, hist_waves<MN2>())
       M.mul(b, ARow{rpow + (size_t)(len + 1) * S4});
       M.reduce_once(b);
     }
-    if (ns == 1) M.store_strided(b, mypart + (int64_t)bin * T, opaque_i(ncols));
+    if (ns == 1) M.store_strided(b, mypart + (int64_t)bin * bin_stride, opaque_i(ncols));
     else M.store_row(b, mypark + (size_t)(B[bin] + j) * S4);
   }
   __syncthreads();  // (every parked row is written)
@@ -192,7 +184,7 @@ __global__ void __launch_bounds__(256, hist_waves<MN2>())
 #pragma unroll 1
       for (int u = 1; u < len; ++u) M.mul(b, ARowV{r0 + (size_t)u * nch * S4});
       M.reduce_once(b);
-      if (nch == 1) M.store_strided(b, mypart + (int64_t)bin * T, opaque_i(ncols));
+      if (nch == 1) M.store_strided(b, mypart + (int64_t)bin * bin_stride, opaque_i(ncols));
       else M.store_row(b, r0);
     }
     __syncthreads();
@@ -204,6 +196,27 @@ __global__ void __launch_bounds__(256, hist_waves<MN2>())
       }
     }
   }
+}
+
+// Block x = t * gf + fl: tile t of feature f0 + fl (the features of one tile
+// are neighbours, so the tile's ciphertext rows are read from HBM once and
+// from L2 by the others). part: [S4][gf * nbins * T] strided rows, column
+// (fl * nbins + b) * T + t. rows_idx: the caller's row ids (trusted < n_rows)
+// or null (element i is row i). cnt_out: zeroed before the launch, or null.
+template <class MN2, int PW>
+__global__ void __launch_bounds__(256, hist_waves<MN2>())
+    k_hist_tile(KeyDev key, const uint32_t* __restrict__ Nn2, const uint32_t* __restrict__ words,
+                const uint16_t* __restrict__ bins, int64_t bins_stride, int nbins,
+                const int32_t* __restrict__ rows_idx, int64_t count, int tile_rows, int f0, int gf, int64_t T,
+                uint32_t* __restrict__ part, uint32_t* park, int32_t* __restrict__ cnt_out) {
+  const int64_t t = blockIdx.x / gf;
+  const int fl = (int)(blockIdx.x - t * gf);
+  const int64_t base = t * tile_rows;
+  const int m = (int)(count - base < tile_rows ? count - base : tile_rows);
+  hist_tile_block<MN2, PW>(key, Nn2, words, bins + (size_t)(f0 + fl) * bins_stride, nbins, rows_idx, base, m,
+                           tile_rows, part + (int64_t)fl * nbins * T + t, T, (int)((int64_t)gf * nbins * T),
+                           park + (size_t)blockIdx.x * (tile_rows / kHistParkDiv) * MN2::S4,
+                           cnt_out ? cnt_out + (size_t)(f0 + fl) * nbins : nullptr);
 }
 
 }  // namespace xhe

@@ -273,6 +273,42 @@ inline int hist_group(int nfeat, int nbins, int tile_rows, int64_t tiles, int64_
   return (int)(g < 1 ? 1 : g > nfeat ? nfeat : g);
 }
 
+// ------------------------------------------- level-wise histogram
+// xhe_hist_level (hist_level_dev.hpp): every node of a tree level from one
+// pass. The rows are ordered by node into tile slots that each lie inside one
+// node, so the tile is hist_tile's, but not above the power of two at or
+// above the mean node size n_rows / nnodes (floor kHistTileMin): most nodes
+// are then one tile, the partial rows are about the output itself and the
+// fold is nearly a copy. A node of c rows takes ceil(c / tile) slots; the sum
+// over the nodes is at most floor(n_rows / tile) + nnodes, which the host
+// knows without reading a count back: level_tiles_max sizes every grid and
+// workspace (a slot behind the used ones returns at once). The LDS layout is
+// k_hist_tile's (hist_lds_bytes) and the features run in hist_group's groups
+// with level_tiles_max in place of the tile count.
+constexpr int kLevelNodesMax = 4096;
+
+inline int level_tile(int64_t n_rows, int nnodes, int nfeat, int nbins) {
+  int tile = hist_tile(n_rows, nfeat, nbins);
+  const int64_t mean = (n_rows + nnodes - 1) / (nnodes > 0 ? nnodes : 1);
+  int cap = kHistTileMin;
+  while (cap < kHistTileMax && cap < mean) cap <<= 1;
+  return tile < cap ? tile : cap;
+}
+
+inline int64_t level_tiles_max(int64_t n_rows, int nnodes, int tile_rows) {
+  return (n_rows + tile_rows - 1) / tile_rows + nnodes;
+}
+
+// Fold passes before the last one: a node's partial rows are folded in
+// chunks of at most `chunk` (kRawChunk) until that many are left; no node has
+// more than ceil(n_rows / tile) of them.
+inline int level_fold_passes(int64_t n_rows, int tile_rows, int chunk) {
+  int64_t t = (n_rows + tile_rows - 1) / tile_rows;
+  int p = 0;
+  for (; t > chunk; ++p) t = (t + chunk - 1) / chunk;
+  return p;
+}
+
 enum class Horner {
   WAVE,   // 2048, 16 lanes: k_mexp_horner_wave, one 16-wave block per column (latency)
   LANES,  // k_mexp_horner

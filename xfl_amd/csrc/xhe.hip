@@ -31,6 +31,7 @@
 #include "enc_obf_dev.hpp"
 #include "wire_unpack.hpp"
 #include "hist_dev.hpp"
+#include "hist_level_dev.hpp"
 #include "bucket_dev.hpp"
 
 using namespace xhe;
@@ -1421,6 +1422,74 @@ void hist_impl(const xhe_key* k, const uint32_t* c, const uint16_t* bins, int64_
                 });
 }
 
+// Level-wise histogram (hist_level_dev.hpp): the row ids ordered by node into
+// tile slots (three small launches), then per feature group stage A over
+// level_tiles_max slots x features and the fold over the nodes' slot ranges,
+// which it reads on the device. Grids and workspaces are sized from the bound
+// on the slots; nothing is read back and nothing uploaded.
+template <class Sh>
+void hist_level_impl(const xhe_key* k, const uint32_t* c, int64_t n_rows, const uint16_t* bins, int64_t bins_stride,
+                     int nfeat, int nbins, const uint16_t* node, int nnodes, int tile_rows, uint32_t* out,
+                     int32_t* cnt, hipStream_t s) {
+  using MN2 = typename Sh::MN2;
+  const int S4 = MN2::S4;
+  auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
+  if (!tile_rows) tile_rows = paths::level_tile(n_rows, nnodes, nfeat, nbins);
+  const int64_t tmax = paths::level_tiles_max(n_rows, nnodes, tile_rows);
+  const int gmax = paths::hist_group(nfeat, nbins, tile_rows, tmax, kChunk);
+  if ((int64_t)gmax * nbins * tmax > INT32_MAX || tmax * tile_rows > INT32_MAX ||
+      (int64_t)gmax * nbins * std::max<int64_t>(tmax, nnodes) * MN2::TPI > (int64_t)INT32_MAX * 256)
+    throw std::logic_error("xhe_hist_level: problem too large for one call");
+  const int passes = paths::level_fold_passes(n_rows, tile_rows, kRawChunk);
+  const size_t lds = (size_t)paths::hist_lds_bytes(tile_rows, nbins);
+  ProfScope ps("k_hist_level", s);
+  // node_cnt[nnodes] | cursor[nnodes] | tile_begin[nnodes + 1] | tile_node[tmax]
+  DevBuf order, lv;
+  lv = DevBuf((size_t)(3 * (int64_t)nnodes + 1 + tmax) * 4, s, DevBuf::kAsync);
+  order = DevBuf((size_t)(tmax * tile_rows) * 4, s, DevBuf::kAsync);
+  int32_t* node_cnt = lv.as<int32_t>();
+  int32_t *cursor = node_cnt + nnodes, *tile_begin = cursor + nnodes, *tile_node = tile_begin + nnodes + 1;
+  launch(k_hist_zero, dim3((unsigned)((3 * nnodes + 1 + 255) / 256)), dim3(256), s, node_cnt,
+         (int64_t)3 * nnodes + 1);
+  if (cnt) {
+    const int64_t nc = (int64_t)nnodes * nfeat * nbins;
+    launch(k_hist_zero, dim3((unsigned)((nc + 255) / 256)), dim3(256), s, cnt, nc);
+  }
+  if (n_rows > 0) {  // (without rows tile_begin stays zero: every node folds to 1)
+    ProfScope po("k_level_order", s);
+    const dim3 rb((unsigned)((n_rows + kLevelBlockRows - 1) / kLevelBlockRows));
+    hipLaunchKernelGGL(k_level_count, rb, dim3(256), (size_t)nnodes * 4, s, node, n_rows, nnodes, node_cnt);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_level_plan, dim3(1), dim3(256), (size_t)(nnodes + 1) * 4, s, node_cnt, nnodes, tile_rows, tmax,
+                       tile_begin, tile_node);
+    HIPCHK(hipGetLastError());
+    hipLaunchKernelGGL(k_level_scatter, rb, dim3(256), (size_t)nnodes * 8, s, node, n_rows, nnodes, tile_rows,
+                       tile_begin, cursor, order.as<int32_t>());
+    HIPCHK(hipGetLastError());
+  }
+  for (int f0 = 0; f0 < nfeat; f0 += gmax) {
+    const int gf = std::min(gmax, nfeat - f0);
+    const int gn = gf * nbins;
+    const int ncols = (int)(gn * tmax);
+    DevBuf park, part;
+    part = DevBuf((size_t)S4 * ncols * 4, s, DevBuf::kAsync);
+    park = DevBuf((size_t)gf * tmax * (tile_rows / kHistParkDiv) * S4 * 4, s, DevBuf::kAsync);
+    if (n_rows > 0) {
+      ProfScope pt("k_level_tile", s);
+      hipLaunchKernelGGL((k_level_tile<MN2, Sh::RW2>), dim3((unsigned)(gf * tmax)), dim3(256), lds, s, k->kd,
+                         n2h<MN2>(k).N, c, bins, bins_stride, nbins, order.as<int32_t>(), node_cnt, tile_begin,
+                         tile_node, tile_rows, f0, gf, nfeat, ncols, part.as<uint32_t>(), park.as<uint32_t>(), cnt);
+      HIPCHK(hipGetLastError());
+    }
+    ProfScope pf("k_level_fold", s);
+    for (int p = 0; p < passes; ++p)
+      launch(k_level_fold_pass<MN2>, blocks((int64_t)ncols), dim3(256), s, k->kd, n2h<MN2>(k).N, part.as<uint32_t>(),
+             ncols, gn, tmax, tile_begin, tile_node, p);
+    launch(k_level_fold<MN2>, blocks((int64_t)nnodes * gn), dim3(256), s, k->kd, n2h<MN2>(k).N, part.as<uint32_t>(),
+           ncols, gn, nbins, nnodes, f0, nfeat, tile_begin, passes, out);
+  }
+}
+
 // Bucket multi-exponentiation (bucket_dev.hpp). The columns run in groups
 // whose digit matrix stays within kBucketDigitCap ids (and hist_rows groups
 // the (column, window) features within kChunk rows below that); every group
@@ -1780,6 +1849,40 @@ int xhe_hist(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const ui
     with_shape(key->K, [&](auto sh) {
       hist_impl<decltype(sh)>(key, c_dev, bins_dev, bins_stride, nfeat, nbins, rows_dev, count, tile_rows, out_dev,
                               cnt_dev, (hipStream_t)stream);
+    });
+    return XHE_OK;
+  });
+}
+
+namespace {
+int hist_level_args(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins, int64_t bins_stride,
+                    int nfeat, int nbins, const uint16_t* node, int nnodes, int tile_rows, const uint32_t* out,
+                    const char* who) {
+  if (!key || !out || n_rows < 0 || nfeat < 1 || (n_rows > 0 && (!c || !bins || !node)))
+    return fail(XHE_EINVAL, std::string(who) + ": bad argument");
+  if (nnodes < 1 || nnodes > paths::kLevelNodesMax)
+    return fail(XHE_EINVAL, std::string(who) + ": nnodes must be in [1, 4096]");
+  if (nbins < 1 || nbins > 4096) return fail(XHE_EINVAL, std::string(who) + ": nbins must be in [1, 4096]");
+  if (bins_stride < n_rows) return fail(XHE_EINVAL, std::string(who) + ": bins_stride is shorter than n_rows");
+  if (tile_rows != 0 && !paths::hist_tile_ok(tile_rows))
+    return fail(XHE_EINVAL, std::string(who) + ": tile_rows must be 0 or a power of two in [64, 8192]");
+  if (n_rows > 0 && out < c + (size_t)n_rows * key->n2w && c < out + (size_t)nnodes * nfeat * nbins * key->n2w)
+    return fail(XHE_EINVAL, std::string(who) + ": out overlaps c");
+  return XHE_OK;
+}
+}  // namespace
+
+int xhe_hist_level(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const uint16_t* bins_dev,
+                   int64_t bins_stride, int nfeat, int nbins, const uint16_t* node_dev, int nnodes, int tile_rows,
+                   uint32_t* out_dev, int32_t* cnt_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (int rc = hist_level_args(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins, node_dev, nnodes, tile_rows,
+                                 out_dev, "xhe_hist_level"))
+      return rc;
+    DevGuard dg(key->device);
+    with_shape(key->K, [&](auto sh) {
+      hist_level_impl<decltype(sh)>(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins, node_dev, nnodes,
+                                    tile_rows, out_dev, cnt_dev, (hipStream_t)stream);
     });
     return XHE_OK;
   });
@@ -2815,6 +2918,34 @@ int xhe_hist_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const u
     if (rc != XHE_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
     if (cnt) HIPCHK(hipMemcpyAsync(cnt, dcnt.p, nb, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    return XHE_OK;
+  });
+}
+
+int xhe_hist_level_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                        int64_t bins_stride, int nfeat, int nbins, const uint16_t* node, int nnodes, int tile_rows,
+                        uint32_t* out, int32_t* cnt) {
+  return guarded([&]() -> int {
+    if (int rc = hist_level_args(key, c, n_rows, bins, bins_stride, nfeat, nbins, node, nnodes, tile_rows, out,
+                                 "xhe_hist_level_host"))
+      return rc;
+    DevGuard dg(key->device);
+    Stream st;
+    const size_t cb = (size_t)n_rows * key->n2w * 4, bb = ((size_t)(nfeat - 1) * bins_stride + n_rows) * 2,
+                 nn = (size_t)nnodes * nfeat * nbins, ob = nn * key->n2w * 4;
+    DevBuf dc(cb, st.s), db(bb, st.s), dn((size_t)n_rows * 2, st.s), dout(ob, st.s), dcnt(nn * 4, st.s);
+    if (n_rows > 0) {
+      HIPCHK(hipMemcpyAsync(dc.p, c, cb, hipMemcpyHostToDevice, st.s));
+      HIPCHK(hipMemcpyAsync(db.p, bins, bb, hipMemcpyHostToDevice, st.s));
+      HIPCHK(hipMemcpyAsync(dn.p, node, (size_t)n_rows * 2, hipMemcpyHostToDevice, st.s));
+    }
+    int rc = xhe_hist_level(key, dc.as<uint32_t>(), n_rows, db.as<uint16_t>(), bins_stride, nfeat, nbins,
+                            dn.as<uint16_t>(), nnodes, tile_rows, dout.as<uint32_t>(),
+                            cnt ? dcnt.as<int32_t>() : nullptr, st.s);
+    if (rc != XHE_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
+    if (cnt) HIPCHK(hipMemcpyAsync(cnt, dcnt.p, nn * 4, hipMemcpyDeviceToHost, st.s));
     HIPCHK(hipStreamSynchronize(st.s));
     return XHE_OK;
   });

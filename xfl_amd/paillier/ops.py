@@ -493,6 +493,30 @@ def hist_words(ctx, cw, bins, nbins, rows=None):
     return out, cnt
 
 
+def hist_level_words(ctx, cw, bins, nbins, nodes, nnodes):
+    """out[(v * nfeat + f) * nbins + b] = prod of the rows r of cw with
+    nodes[r] == v and bins[f][r] == b mod n^2, and their number: every node
+    of a tree level in one xhe_hist_level call through host buffers. bins:
+    [nfeat, n_rows] uint16 ids (>= nbins: dropped for that feature); nodes:
+    [n_rows] uint16 slots (>= nnodes: the row is skipped). -> ([nnodes * nfeat
+    * nbins, n2w] uint32, the counts as int32)."""
+    cw = _u32(cw)
+    bins = np.ascontiguousarray(bins, dtype=np.uint16)
+    nodes = np.ascontiguousarray(nodes, dtype=np.uint16).reshape(-1)
+    n_rows = cw.shape[0]
+    if bins.ndim != 2 or bins.shape[1] != n_rows or nodes.shape[0] != n_rows:
+        raise ValueError("hist_level: bins must be [nfeat, n_rows] and nodes [n_rows]")
+    nfeat, total = bins.shape[0], int(nnodes) * bins.shape[0] * int(nbins)
+    out = np.empty((total, n2w_of(ctx)), dtype=np.uint32)
+    cnt = np.empty(total, dtype=np.int32)
+    dk = ctx.device_key(ctx.own_device())
+    nat.check(nat.lib().xhe_hist_level_host(dk.handle, _vp(cw) if n_rows else None, n_rows,
+                                            _vp(bins) if n_rows else None, n_rows, nfeat, int(nbins),
+                                            _vp(nodes) if n_rows else None, int(nnodes), 0, _vp(out), _vp(cnt)),
+              "hist_level")
+    return out, cnt
+
+
 def segscan_dev(ctx, dk, cd, seg):
     """segscan_words on device words -> device [count, n2w]"""
     from . import resident

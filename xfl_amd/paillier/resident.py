@@ -767,6 +767,30 @@ def hist(dk, c, bins_d, nbins, rows=None, tile_rows=0):
     return out, cnt
 
 
+def hist_level(dk, c, bins_d, nbins, node_d, nnodes, tile_rows=0):
+    """Per-(node, feature, bin) sums and counts of the device ciphertext rows c
+    [n_rows, n2w] in one call (xhe_hist_level): bins_d as hist's, node_d a
+    device int16 tensor [n_rows] holding uint16 node slots (an id >= nnodes
+    skips the row) -> (device [nnodes * nfeat * nbins, n2w] words, device int32
+    [nnodes * nfeat * nbins] counts). Nothing here waits for the kernels."""
+    torch = _torch()
+    dev = dk.device
+    n_rows, nfeat = c.shape[0], bins_d.shape[0]
+    if bins_d.dim() != 2 or bins_d.element_size() != 2 or bins_d.stride(1) != 1:
+        raise ValueError("hist_level: bins must be a [nfeat, stride] tensor of 16-bit ids, rows contiguous")
+    if node_d.dim() != 1 or node_d.element_size() != 2 or node_d.shape[0] != n_rows or not node_d.is_contiguous():
+        raise ValueError("hist_level: nodes must be a contiguous [n_rows] tensor of 16-bit ids")
+    total = int(nnodes) * nfeat * int(nbins)
+    with _On(dev):
+        out = torch.empty((total, dk.n2w), dtype=torch.int32, device=f"cuda:{dev}")
+        cnt = torch.empty(total, dtype=torch.int32, device=f"cuda:{dev}")
+        src = c.contiguous()
+    nat.check(nat.lib().xhe_hist_level(dk.handle, _dp(src), n_rows, _dp(bins_d), bins_d.stride(0), nfeat, int(nbins),
+                                       _dp(node_d), int(nnodes), int(tile_rows), _dp(out), _dp(cnt), _sp(dev)),
+              "hist_level")
+    return out, cnt
+
+
 def multiexp(dk, bases, idx, kw_, kbits, win_bits=0):
     """out[j] = prod_t bases[idx[j][t]]^k[j][t] mod n^2 on device bases; idx
     and k host arrays (validated here: the device entry point trusts them)"""

@@ -350,6 +350,83 @@ def histograms(arr, bins, nbins: int = None, rows=None):
         return PaillierArray._concat_same_type(parts).reshape((nfeat, nbins)), counts
 
 
+def level_histograms(arr, bins, nodes, nnodes: int = None, nbins: int = None):
+    """histograms() for every node of a tree level in ONE device call
+    (xhe_hist_level): what a level-wise trainer's loop of
+    histograms(arr, bins, rows=<the node's samples>) over the level's nodes
+    computes (xgb_actor.py cal_hist_for_node, run for all nodes of a level).
+    arr, bins, nbins: as histograms. nodes: one level-local node slot per
+    element of arr; a negative or NaN slot, or one >= nnodes, leaves the row out
+    of every node (a finished leaf, an unsampled row). nnodes defaults to the
+    largest slot + 1. Returns (sums, counts): sums a PaillierArray of shape
+    (nnodes, nfeat, nbins) at the column's exponent, in HBM when the input is;
+    counts an int64 array of that shape. Needs only the public key.
+
+    The device path serves one exponent, nbins <= 4096 and nnodes <= 4096;
+    anything else is the loop of histograms(rows=...) per node."""
+    from .paillier import PaillierCiphertext, ops, resident
+    from .paillier.array import NA_EXP, PaillierArray, _Fallback, _result
+    if isinstance(arr, np.ndarray) and arr.dtype == object and arr.ndim == 1 and \
+            all(isinstance(c, PaillierCiphertext) for c in arr):
+        arr = PaillierArray(arr)
+    if not isinstance(arr, PaillierArray):
+        raise TypeError("level_histograms takes a PaillierArray or an object array of PaillierCiphertext")
+    if arr.ndim != 1:
+        raise ValueError("level_histograms takes a 1-D array")
+    ctx = arr.context
+    if ctx is None:
+        raise ValueError("ciphertext array without a context: pass one to Paillier.ciphertext_from")
+
+    def ints(a):  # negative for NaN / non-finite
+        a = np.asarray(a)
+        if a.dtype.kind in "iu":
+            return a.astype(np.int64)
+        af = a.astype(np.float64)
+        return np.where(np.isfinite(af), af, -1).astype(np.int64)
+    ids = ints(bins.to_numpy().T if hasattr(bins, "columns") else bins)
+    if ids.ndim != 2 or ids.shape[1] != arr.size or ids.shape[0] < 1:
+        raise ValueError(f"level_histograms: bins must be [nfeat, {arr.size}]")
+    nd = ints(nodes).reshape(-1)
+    if nd.shape[0] != arr.size:
+        raise ValueError(f"level_histograms: nodes must have {arr.size} entries")
+    if nbins is None:
+        nbins = max(1, int(ids.max()) + 1) if ids.size else 1
+    if nnodes is None:
+        nnodes = max(1, int(nd.max()) + 1) if nd.size else 1
+    nbins, nnodes = int(nbins), int(nnodes)
+    if nbins < 1 or nnodes < 1:
+        raise ValueError("level_histograms: nbins and nnodes must be positive")
+    ids = np.where((ids < 0) | (ids >= nbins), -1, ids)
+    nd = np.where((nd < 0) | (nd >= nnodes), -1, nd)
+    if arr._has_na():
+        nd[arr.isna()] = -1
+    nfeat = ids.shape[0]
+    shape = (nnodes, nfeat, nbins)
+    try:
+        used = arr.exponents[nd >= 0]
+        used = used[used != NA_EXP]
+        if nbins > 4096 or nnodes > 4096 or (used.size and int(used.min()) != int(used.max())):
+            raise _Fallback()
+        e0 = int(used[0]) if used.size else 0
+        n2w = ops.n2w_of(ctx)
+        x = arr._aligned_words(n2w)
+        b16 = np.where(ids < 0, 0xFFFF, ids).astype(np.uint16)
+        n16 = np.where(nd < 0, 0xFFFF, nd).astype(np.uint16)
+        exps = np.full(nnodes * nfeat * nbins, e0, dtype=np.int32)
+        dev = resident.device_for(ctx, -1, x.size, 4 * n2w)
+        if dev is None:
+            w, cnt = ops.hist_level_words(ctx, x.words, b16, nbins, n16, nnodes)
+            return _result(ctx, w, exps, shape), cnt.astype(np.int64).reshape(shape)
+        out, cnt = resident.hist_level(ctx.device_key(dev), x._dw(dev), resident.upload(b16.view(np.int16), dev), nbins,
+                                       resident.upload(n16.view(np.int16), dev), nnodes)
+        counts = resident.download(cnt, np.int32).astype(np.int64).reshape(shape)
+        return PaillierArray.from_device(ctx, out, exps, shape), counts
+    except _Fallback:
+        per = [histograms(arr, ids, nbins=nbins, rows=np.flatnonzero(nd == v)) for v in range(nnodes)]
+        sums = PaillierArray._concat_same_type([s.reshape(-1) for s, _ in per]).reshape(shape)
+        return sums, np.stack([c for _, c in per])
+
+
 def unpack_columns(cols, count: int, num: int, k: int):
     """decrypt_unpack's index mapping: cols[t * num + i][j] (the num * k digit
     columns of the packed plaintexts) -> out[i][j * k + t], cut to count."""
