@@ -11,10 +11,11 @@
  * gives the thread-local message. A key handle is immutable after creation
  * and may be shared between threads; calls on distinct streams are reentrant.
  *
- * Ciphertext operands: the eleven entry points that read ciphertext words -
+ * Ciphertext operands: the twelve entry points that read ciphertext words -
  * xhe_decrypt, xhe_mulmod, xhe_powmod, xhe_pack, xhe_invert, xhe_segprod,
- * xhe_segscan, xhe_hist, xhe_hist_level, xhe_multiexp and xhe_bucketexp (and
- * their _host variants) - accept ANY value in
+ * xhe_segscan, xhe_hist, xhe_hist_level, xhe_hist_level_sub (its rows and its
+ * parent rows), xhe_multiexp and xhe_bucketexp (and their _host variants) -
+ * accept ANY value in
  * [0, 2^(32 n2w))
  * in an operand row, not only residues below n^2: a received payload is not
  * reduced on its way into a device array (xhe_wire_decode, xhe_wire_scan and
@@ -266,6 +267,44 @@ int xhe_hist_level(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, co
                    int64_t bins_stride, int nfeat, int nbins, const uint16_t* node_dev, int nnodes, int tile_rows,
                    uint32_t* out_dev, int32_t* cnt_dev, void* stream);
 
+/* Level-wise histogram by subtraction: the result of xhe_hist_level for a
+ * level whose slots 2v and 2v + 1 are the children of slot v of the level
+ * above, given that level's histogram. Of every pair only the child with
+ * fewer rows is multiplied from its rows (a tie builds the left one); the
+ * other child is
+ *   out = parent[v] * built^-1 mod n^2 per (feature, bin),
+ *   cnt = parent_cnt[v] - built_cnt,
+ * the same words the direct product over its rows gives. A pair without a row
+ * in either child (a finished leaf's slots) gets ones and zero counts in both
+ * slots, whatever the parent rows hold. c, bins, bins_stride, nfeat, nbins,
+ * node, tile_rows, out, cnt and the output layout: as the direct call; nnodes
+ * must be even. parent: nnodes / 2 * nfeat * nbins ciphertext rows in the
+ * direct call's output layout for the level above (any values below
+ * 2^(32 n2w), taken mod n^2); parent_cnt: the matching counts, required when
+ * cnt is given. Every output is below n^2.
+ * Precondition (the caller's data, trusted as `rows` is in xhe_hist): for
+ * every pair that holds a row, the rows of slots 2v and 2v + 1 are exactly the
+ * rows that made parent[v], under the same bin matrix. Otherwise the sibling
+ * is the quotient of unrelated products.
+ * XHE_EINVAL: an odd nnodes, a missing parent (or parent_cnt with cnt),
+ * whatever the direct call rejects, out overlapping c or parent. XHE_ENOINV:
+ * some built (feature, bin) product has no inverse mod n^2 (as xhe_invert
+ * reports it; out and cnt are then unspecified). Enqueues on `stream` and
+ * synchronises it ONCE, inside the batch inversion of the built rows (the
+ * inverse of the product tree's root is the host's, as in xhe_invert and
+ * xhe_bucketexp with signs); the backward pass is enqueued after it and the
+ * call returns without waiting for it. Timed as "k_hist_level_sub" under
+ * xhe_profile (its new stages as "k_sub_pick", "k_sib_fwd", "k_sib_bwd", the
+ * build as the direct call's stages). */
+int xhe_hist_level_sub(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const uint16_t* bins_dev,
+                       int64_t bins_stride, int nfeat, int nbins, const uint16_t* node_dev, int nnodes,
+                       const uint32_t* parent_dev, const int32_t* parent_cnt_dev, int tile_rows, uint32_t* out_dev,
+                       int32_t* cnt_dev, void* stream);
+/* Host only, no device work: 1 when the planner (paths.hpp level_sub) expects
+ * the subtraction to beat the direct call at this shape, 0 otherwise (always 0
+ * for an odd nnodes or fewer than 2 nodes). */
+int xhe_hist_level_sub_route(const xhe_key* key, int64_t n_rows, int nnodes, int nfeat, int nbins);
+
 /* Encrypted matrix-vector product as a multi-exponentiation: the object-dtype
  * np.matmul(enc[B], X[B, D]) of logistic_regression/trainer.py:166 (and
  * linear_regression/trainer.py:207, poisson_regression/trainer.py:267,
@@ -365,6 +404,11 @@ int xhe_hist_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const u
 int xhe_hist_level_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
                         int64_t bins_stride, int nfeat, int nbins, const uint16_t* node, int nnodes, int tile_rows,
                         uint32_t* out, int32_t* cnt);
+/* xhe_hist_level_sub on host buffers. */
+int xhe_hist_level_sub_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                            int64_t bins_stride, int nfeat, int nbins, const uint16_t* node, int nnodes,
+                            const uint32_t* parent, const int32_t* parent_cnt, int tile_rows, uint32_t* out,
+                            int32_t* cnt);
 /* xhe_pack: count ciphertexts in, ceil(count/k) out. */
 int xhe_pack_host(const xhe_key* key, const uint32_t* c, int64_t count, int k, int shift_bits, uint32_t* out);
 int xhe_mulmod_host(const xhe_key* key, const uint32_t* a, const int32_t* ea, const uint32_t* b, const int32_t* eb,

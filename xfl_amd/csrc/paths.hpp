@@ -309,6 +309,44 @@ inline int level_fold_passes(int64_t n_rows, int tile_rows, int chunk) {
   return p;
 }
 
+// --------------------------------------------- histogram subtraction
+// xhe_hist_level_sub (hist_sub_dev.hpp) multiplies only the smaller child of
+// every pair of level slots from its rows and takes the sibling as parent /
+// built. Products mod n^2 of a level, nfeat times
+//   direct     n_rows
+//   subtract   n_rows / 2 + 4 (nnodes / 2) nbins
+// (the built children hold at most half the rows - the host does not know the
+// real split, so the plan takes the balanced bound - and the sibling pass
+// costs four products per built (pair, feature, bin) row). The route
+// subtracts when direct >= kSubMinSaving x subtract, for an even nnodes >= 2.
+// kSubMinSaving is a measured figure, not the model's 1 (DESIGN "Histogram
+// subtraction", profiles/r27/hist_sub/): on config 5 (100 k rows x 64 features
+// x 256 bins, 2048 bits) the balanced level was faster by subtraction at every
+// node count measured, 2 to 64, by 2.7 ms of 24 at 64 nodes against a spread of
+// 0.6 ms; 64 nodes is the model's ratio 1.208, the lowest one measured. The
+// route subtracts down to that ratio and no further: nothing beyond 64 nodes
+// (1.0 at 98 nodes) was measured.
+constexpr double kSubMinSaving = 1.2;
+
+inline bool level_sub(int64_t n_rows, int nnodes, int nfeat, int nbins) {
+  if (nnodes < 2 || (nnodes & 1) || n_rows < 1 || nfeat < 1 || nbins < 1) return false;
+  const double direct = (double)n_rows * nfeat;
+  const double sub = (0.5 * (double)n_rows + 4.0 * (nnodes / 2) * nbins) * nfeat;
+  return direct >= kSubMinSaving * sub;
+}
+
+// Rows per chunk of the sibling pass over M built rows: as many chunks as
+// kSibFillGroups lane groups (131072 lanes of 4) while a chunk keeps at least
+// kSibChunkMin rows - each chunk total costs the inversion tree about seven
+// products more - and at most kSibChunkMax = kRawChunk, the exit rows of Rpow.
+constexpr int kSibChunkMin = 4, kSibChunkMax = 32;
+constexpr int64_t kSibFillGroups = 32768;
+
+inline int sib_chunk(int64_t M) {
+  const int64_t c = M / kSibFillGroups;
+  return (int)(c < kSibChunkMin ? kSibChunkMin : c > kSibChunkMax ? kSibChunkMax : c);
+}
+
 enum class Horner {
   WAVE,   // 2048, 16 lanes: k_mexp_horner_wave, one 16-wave block per column (latency)
   LANES,  // k_mexp_horner

@@ -9,6 +9,7 @@
 #include <cstdio>
 #include <memory>
 #include <mutex>
+#include <optional>
 #include <atomic>
 #include <stdexcept>
 #include <unordered_map>
@@ -32,6 +33,7 @@
 #include "wire_unpack.hpp"
 #include "hist_dev.hpp"
 #include "hist_level_dev.hpp"
+#include "hist_sub_dev.hpp"
 #include "bucket_dev.hpp"
 
 using namespace xhe;
@@ -1427,22 +1429,27 @@ void hist_impl(const xhe_key* k, const uint32_t* c, const uint16_t* bins, int64_
 // level_tiles_max slots x features and the fold over the nodes' slot ranges,
 // which it reads on the device. Grids and workspaces are sized from the bound
 // on the slots; nothing is read back and nothing uploaded.
+// active: a bound on the rows whose id is below nnodes (n_rows for the plain
+// call; the subtraction's built children hold at most half of them), which
+// sizes the tile, the slots and the fold passes. label: the call's name under
+// xhe_profile, null inside a call that has its own.
 template <class Sh>
-void hist_level_impl(const xhe_key* k, const uint32_t* c, int64_t n_rows, const uint16_t* bins, int64_t bins_stride,
-                     int nfeat, int nbins, const uint16_t* node, int nnodes, int tile_rows, uint32_t* out,
-                     int32_t* cnt, hipStream_t s) {
+void hist_level_impl(const xhe_key* k, const uint32_t* c, int64_t n_rows, int64_t active, const uint16_t* bins,
+                     int64_t bins_stride, int nfeat, int nbins, const uint16_t* node, int nnodes, int tile_rows,
+                     uint32_t* out, int32_t* cnt, hipStream_t s, const char* label) {
   using MN2 = typename Sh::MN2;
   const int S4 = MN2::S4;
   auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
-  if (!tile_rows) tile_rows = paths::level_tile(n_rows, nnodes, nfeat, nbins);
-  const int64_t tmax = paths::level_tiles_max(n_rows, nnodes, tile_rows);
+  if (!tile_rows) tile_rows = paths::level_tile(active, nnodes, nfeat, nbins);
+  const int64_t tmax = paths::level_tiles_max(active, nnodes, tile_rows);
   const int gmax = paths::hist_group(nfeat, nbins, tile_rows, tmax, kChunk);
   if ((int64_t)gmax * nbins * tmax > INT32_MAX || tmax * tile_rows > INT32_MAX ||
       (int64_t)gmax * nbins * std::max<int64_t>(tmax, nnodes) * MN2::TPI > (int64_t)INT32_MAX * 256)
     throw std::logic_error("xhe_hist_level: problem too large for one call");
-  const int passes = paths::level_fold_passes(n_rows, tile_rows, kRawChunk);
+  const int passes = paths::level_fold_passes(active, tile_rows, kRawChunk);
   const size_t lds = (size_t)paths::hist_lds_bytes(tile_rows, nbins);
-  ProfScope ps("k_hist_level", s);
+  std::optional<ProfScope> ps;
+  if (label) ps.emplace(label, s);
   // node_cnt[nnodes] | cursor[nnodes] | tile_begin[nnodes + 1] | tile_node[tmax]
   DevBuf order, lv;
   lv = DevBuf((size_t)(3 * (int64_t)nnodes + 1 + tmax) * 4, s, DevBuf::kAsync);
@@ -1488,6 +1495,68 @@ void hist_level_impl(const xhe_key* k, const uint32_t* c, int64_t n_rows, const 
     launch(k_level_fold<MN2>, blocks((int64_t)nnodes * gn), dim3(256), s, k->kd, n2h<MN2>(k).N, part.as<uint32_t>(),
            ncols, gn, nbins, nnodes, f0, nfeat, tile_begin, passes, out);
   }
+}
+
+// Histogram subtraction (hist_sub_dev.hpp): the level's counts and one launch
+// pick the built child of every pair and remap the node ids; hist_level_impl
+// builds the npairs built children into a words workspace (its feature groups
+// bounded by kChunk as ever); one forward and one backward pass over all M =
+// npairs * nfeat * nbins built rows around invert_impl on the chunk totals,
+// whose host inverse is the call's one synchronisation. The sibling pass is not
+// cut into launch chunks - a second one would need a second inversion and a
+// second synchronisation - so its workspaces grow with M: the built words (half
+// of `out`) and the parked prefixes (S4 words a row).
+template <class Sh>
+int hist_level_sub_impl(const xhe_key* k, const uint32_t* c, int64_t n_rows, const uint16_t* bins, int64_t bins_stride,
+                        int nfeat, int nbins, const uint16_t* node, int nnodes, const uint32_t* parent,
+                        const int32_t* parent_cnt, int tile_rows, uint32_t* out, int32_t* cnt, hipStream_t s) {
+  using MN2 = typename Sh::MN2;
+  const int npairs = nnodes / 2;
+  const int64_t FB = (int64_t)nfeat * nbins, M = npairs * FB;
+  const int C = paths::sib_chunk(M);
+  const int64_t nchunks = (M + C - 1) / C;
+  if (M > INT32_MAX || nchunks * MN2::TPI > (int64_t)INT32_MAX * 256)
+    throw std::logic_error("xhe_hist_level_sub: problem too large for one call");
+  auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
+  const size_t rb = (size_t)k->n2w * 4;
+  ProfScope ps("k_hist_level_sub", s);
+  // (declared in reverse, filled in allocation order: DevBuf's note)
+  DevBuf inv, tot, pre, bcnt, built, remap, pk;
+  pk = DevBuf((size_t)(nnodes + npairs) * 4, s, DevBuf::kAsync);  // node_cnt[nnodes] | pick[npairs]
+  remap = DevBuf((size_t)n_rows * 2, s, DevBuf::kAsync);
+  built = DevBuf((size_t)M * rb, s, DevBuf::kAsync);
+  if (cnt) bcnt = DevBuf((size_t)M * 4, s, DevBuf::kAsync);
+  int32_t* node_cnt = pk.as<int32_t>();
+  uint32_t* pick = pk.as<uint32_t>() + nnodes;
+  {
+    ProfScope pp("k_sub_pick", s);
+    launch(k_hist_zero, dim3((unsigned)((nnodes + 255) / 256)), dim3(256), s, node_cnt, (int64_t)nnodes);
+    if (n_rows > 0) {
+      hipLaunchKernelGGL(k_level_count, dim3((unsigned)((n_rows + kLevelBlockRows - 1) / kLevelBlockRows)), dim3(256),
+                         (size_t)nnodes * 4, s, node, n_rows, nnodes, node_cnt);
+      HIPCHK(hipGetLastError());
+    }
+    launch(k_sub_pick, dim3((unsigned)((std::max<int64_t>(n_rows, npairs) + 255) / 256)), dim3(256), s, node, n_rows,
+           nnodes, node_cnt, remap.as<uint16_t>(), pick);
+  }
+  hist_level_impl<Sh>(k, c, n_rows, n_rows / 2, bins, bins_stride, nfeat, nbins, remap.as<uint16_t>(), npairs,
+                      tile_rows, built.as<uint32_t>(), cnt ? bcnt.as<int32_t>() : nullptr, s, nullptr);
+  pre = DevBuf((size_t)MN2::S4 * M * 4, s, DevBuf::kAsync);
+  tot = DevBuf((size_t)nchunks * rb, s, DevBuf::kAsync);
+  inv = DevBuf((size_t)nchunks * rb, s, DevBuf::kAsync);
+  {
+    ProfScope pf("k_sib_fwd", s);
+    launch((k_sib_fwd<MN2, Sh::RW2>), blocks(nchunks), dim3(256), s, k->kd, n2h<MN2>(k).N, built.as<uint32_t>(), M,
+           nchunks, pre.as<uint32_t>(), tot.as<uint32_t>());
+  }
+  // (synchronises the stream: the batch inversion's one scalar inverse is the host's)
+  const int rc = invert_impl<Sh, MN2>(k, tot.as<uint32_t>(), nchunks, inv.as<uint32_t>(), s);
+  if (rc != XHE_OK) return rc;
+  ProfScope pb("k_sib_bwd", s);
+  launch((k_sib_bwd<MN2, Sh::RW2>), blocks(nchunks), dim3(256), s, k->kd, n2h<MN2>(k).N, built.as<uint32_t>(),
+         cnt ? bcnt.as<int32_t>() : nullptr, parent, parent_cnt, pick, M, FB, nchunks, pre.as<uint32_t>(),
+         inv.as<uint32_t>(), out, cnt);
+  return XHE_OK;
 }
 
 // Bucket multi-exponentiation (bucket_dev.hpp). The columns run in groups
@@ -1881,11 +1950,48 @@ int xhe_hist_level(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, co
       return rc;
     DevGuard dg(key->device);
     with_shape(key->K, [&](auto sh) {
-      hist_level_impl<decltype(sh)>(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins, node_dev, nnodes,
-                                    tile_rows, out_dev, cnt_dev, (hipStream_t)stream);
+      hist_level_impl<decltype(sh)>(key, c_dev, n_rows, n_rows, bins_dev, bins_stride, nfeat, nbins, node_dev, nnodes,
+                                    tile_rows, out_dev, cnt_dev, (hipStream_t)stream, "k_hist_level");
     });
     return XHE_OK;
   });
+}
+
+namespace {
+int hist_level_sub_args(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                        int64_t bins_stride, int nfeat, int nbins, const uint16_t* node, int nnodes,
+                        const uint32_t* parent, const int32_t* parent_cnt, int tile_rows, const uint32_t* out,
+                        const int32_t* cnt, const char* who) {
+  if (int rc = hist_level_args(key, c, n_rows, bins, bins_stride, nfeat, nbins, node, nnodes, tile_rows, out, who))
+    return rc;
+  if (nnodes & 1) return fail(XHE_EINVAL, std::string(who) + ": nnodes must be even");
+  if (!parent || (cnt && !parent_cnt)) return fail(XHE_EINVAL, std::string(who) + ": parent rows or counts missing");
+  const size_t half = (size_t)(nnodes / 2) * nfeat * nbins * key->n2w;
+  if (out < parent + half && parent < out + 2 * half) return fail(XHE_EINVAL, std::string(who) + ": out overlaps parent");
+  return XHE_OK;
+}
+}  // namespace
+
+int xhe_hist_level_sub(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const uint16_t* bins_dev,
+                       int64_t bins_stride, int nfeat, int nbins, const uint16_t* node_dev, int nnodes,
+                       const uint32_t* parent_dev, const int32_t* parent_cnt_dev, int tile_rows, uint32_t* out_dev,
+                       int32_t* cnt_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (int rc = hist_level_sub_args(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins, node_dev, nnodes,
+                                     parent_dev, parent_cnt_dev, tile_rows, out_dev, cnt_dev, "xhe_hist_level_sub"))
+      return rc;
+    DevGuard dg(key->device);
+    return with_shape(key->K, [&](auto sh) -> int {
+      return hist_level_sub_impl<decltype(sh)>(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins, node_dev,
+                                               nnodes, parent_dev, parent_cnt_dev, tile_rows, out_dev, cnt_dev,
+                                               (hipStream_t)stream);
+    });
+  });
+}
+
+int xhe_hist_level_sub_route(const xhe_key* key, int64_t n_rows, int nnodes, int nfeat, int nbins) {
+  (void)key;  // (one constant serves every key size: DESIGN "Histogram subtraction")
+  return paths::level_sub(n_rows, nnodes, nfeat, nbins) ? 1 : 0;
 }
 
 namespace {
@@ -2943,6 +3049,38 @@ int xhe_hist_level_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, c
     int rc = xhe_hist_level(key, dc.as<uint32_t>(), n_rows, db.as<uint16_t>(), bins_stride, nfeat, nbins,
                             dn.as<uint16_t>(), nnodes, tile_rows, dout.as<uint32_t>(),
                             cnt ? dcnt.as<int32_t>() : nullptr, st.s);
+    if (rc != XHE_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
+    if (cnt) HIPCHK(hipMemcpyAsync(cnt, dcnt.p, nn * 4, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    return XHE_OK;
+  });
+}
+
+int xhe_hist_level_sub_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                            int64_t bins_stride, int nfeat, int nbins, const uint16_t* node, int nnodes,
+                            const uint32_t* parent, const int32_t* parent_cnt, int tile_rows, uint32_t* out,
+                            int32_t* cnt) {
+  return guarded([&]() -> int {
+    if (int rc = hist_level_sub_args(key, c, n_rows, bins, bins_stride, nfeat, nbins, node, nnodes, parent, parent_cnt,
+                                     tile_rows, out, cnt, "xhe_hist_level_sub_host"))
+      return rc;
+    DevGuard dg(key->device);
+    Stream st;
+    const size_t cb = (size_t)n_rows * key->n2w * 4, bb = ((size_t)(nfeat - 1) * bins_stride + n_rows) * 2,
+                 nn = (size_t)nnodes * nfeat * nbins, ob = nn * key->n2w * 4;
+    DevBuf dc(cb, st.s), db(bb, st.s), dn((size_t)n_rows * 2, st.s), dp(ob / 2, st.s), dpc(nn * 2, st.s),
+        dout(ob, st.s), dcnt(nn * 4, st.s);
+    if (n_rows > 0) {
+      HIPCHK(hipMemcpyAsync(dc.p, c, cb, hipMemcpyHostToDevice, st.s));
+      HIPCHK(hipMemcpyAsync(db.p, bins, bb, hipMemcpyHostToDevice, st.s));
+      HIPCHK(hipMemcpyAsync(dn.p, node, (size_t)n_rows * 2, hipMemcpyHostToDevice, st.s));
+    }
+    HIPCHK(hipMemcpyAsync(dp.p, parent, ob / 2, hipMemcpyHostToDevice, st.s));
+    if (cnt) HIPCHK(hipMemcpyAsync(dpc.p, parent_cnt, nn * 2, hipMemcpyHostToDevice, st.s));
+    int rc = xhe_hist_level_sub(key, dc.as<uint32_t>(), n_rows, db.as<uint16_t>(), bins_stride, nfeat, nbins,
+                                dn.as<uint16_t>(), nnodes, dp.as<uint32_t>(), cnt ? dpc.as<int32_t>() : nullptr,
+                                tile_rows, dout.as<uint32_t>(), cnt ? dcnt.as<int32_t>() : nullptr, st.s);
     if (rc != XHE_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
     if (cnt) HIPCHK(hipMemcpyAsync(cnt, dcnt.p, nn * 4, hipMemcpyDeviceToHost, st.s));

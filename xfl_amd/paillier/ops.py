@@ -517,6 +517,12 @@ def hist_level_words(ctx, cw, bins, nbins, nodes, nnodes):
     return out, cnt
 
 
+def hist_level_sub_route(ctx, dev, n_rows, nnodes, nfeat, nbins):
+    """whether the planner expects xhe_hist_level_sub to beat xhe_hist_level at this shape (no device work)"""
+    dk = ctx.device_key(dev)
+    return bool(nat.lib().xhe_hist_level_sub_route(dk.handle, int(n_rows), int(nnodes), int(nfeat), int(nbins)))
+
+
 def segscan_dev(ctx, dk, cd, seg):
     """segscan_words on device words -> device [count, n2w]"""
     from . import resident

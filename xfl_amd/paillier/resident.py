@@ -791,6 +791,34 @@ def hist_level(dk, c, bins_d, nbins, node_d, nnodes, tile_rows=0):
     return out, cnt
 
 
+def hist_level_sub(dk, c, bins_d, nbins, node_d, nnodes, parent_d, parent_cnt_d, tile_rows=0):
+    """hist_level by subtraction (xhe_hist_level_sub): slots 2v, 2v + 1 are the
+    children of slot v of the level above, whose histogram is parent_d (device
+    [nnodes / 2 * nfeat * nbins, n2w] words) and parent_cnt_d (device int32
+    counts); only the smaller child of each pair is multiplied from its rows.
+    Same result as hist_level. The call synchronises the stream once (the
+    batch inversion's host inverse)."""
+    torch = _torch()
+    dev = dk.device
+    n_rows, nfeat = c.shape[0], bins_d.shape[0]
+    if bins_d.dim() != 2 or bins_d.element_size() != 2 or bins_d.stride(1) != 1:
+        raise ValueError("hist_level_sub: bins must be a [nfeat, stride] tensor of 16-bit ids, rows contiguous")
+    if node_d.dim() != 1 or node_d.element_size() != 2 or node_d.shape[0] != n_rows or not node_d.is_contiguous():
+        raise ValueError("hist_level_sub: nodes must be a contiguous [n_rows] tensor of 16-bit ids")
+    total = int(nnodes) * nfeat * int(nbins)
+    if nnodes % 2 or parent_d.shape[0] * 2 != total or parent_cnt_d.shape[0] * 2 != total or \
+            parent_cnt_d.element_size() != 4:
+        raise ValueError("hist_level_sub: the parent histogram must hold nnodes / 2 * nfeat * nbins rows and counts")
+    with _On(dev):
+        out = torch.empty((total, dk.n2w), dtype=torch.int32, device=f"cuda:{dev}")
+        cnt = torch.empty(total, dtype=torch.int32, device=f"cuda:{dev}")
+        src, par, pcnt = c.contiguous(), parent_d.contiguous(), parent_cnt_d.contiguous()
+    nat.check(nat.lib().xhe_hist_level_sub(dk.handle, _dp(src), n_rows, _dp(bins_d), bins_d.stride(0), nfeat,
+                                           int(nbins), _dp(node_d), int(nnodes), _dp(par), _dp(pcnt), int(tile_rows),
+                                           _dp(out), _dp(cnt), _sp(dev)), "hist_level_sub")
+    return out, cnt
+
+
 def multiexp(dk, bases, idx, kw_, kbits, win_bits=0):
     """out[j] = prod_t bases[idx[j][t]]^k[j][t] mod n^2 on device bases; idx
     and k host arrays (validated here: the device entry point trusts them)"""

@@ -350,7 +350,25 @@ def histograms(arr, bins, nbins: int = None, rows=None):
         return PaillierArray._concat_same_type(parts).reshape((nfeat, nbins)), counts
 
 
-def level_histograms(arr, bins, nodes, nnodes: int = None, nbins: int = None):
+def _level_subtracts(ctx, dev, parent, subtract, n_rows, shape, e0):
+    """whether level_histograms takes the subtraction path on device `dev`"""
+    from .paillier import ops
+    from .paillier.array import PaillierArray
+    nnodes, nfeat, nbins = shape
+    if parent is None or subtract is False or nnodes % 2:
+        return False
+    sums, counts = parent
+    pshape = (nnodes // 2, nfeat, nbins)
+    if not isinstance(sums, PaillierArray) or sums.context is not ctx or sums.shape != pshape or \
+            np.shape(counts) != pshape:
+        return False
+    pe = sums.exponents
+    if int(pe.min()) != e0 or int(pe.max()) != e0:
+        return False
+    return True if subtract else ops.hist_level_sub_route(ctx, dev, n_rows, nnodes, nfeat, nbins)
+
+
+def level_histograms(arr, bins, nodes, nnodes: int = None, nbins: int = None, parent=None, subtract: bool = None):
     """histograms() for every node of a tree level in ONE device call
     (xhe_hist_level): what a level-wise trainer's loop of
     histograms(arr, bins, rows=<the node's samples>) over the level's nodes
@@ -361,6 +379,18 @@ def level_histograms(arr, bins, nodes, nnodes: int = None, nbins: int = None):
     largest slot + 1. Returns (sums, counts): sums a PaillierArray of shape
     (nnodes, nfeat, nbins) at the column's exponent, in HBM when the input is;
     counts an int64 array of that shape. Needs only the public key.
+
+    parent: the (sums, counts) a level_histograms call returned for the level
+    above, whose slot v split into this level's slots 2v and 2v + 1 (every row
+    of slot v, and no other, now sits in one of the two, under the same bins).
+    With it the device builds only the smaller child of every pair from its
+    rows and takes the sibling as parent / built per (feature, bin)
+    (xhe_hist_level_sub: histogram subtraction, about half the products); the
+    result is bit for bit the direct one. subtract: None = the library's planner
+    decides, True = always, False = never. The subtraction needs a resident
+    column, an even nnodes and a parent of shape (nnodes / 2, nfeat, nbins) at
+    the column's exponent; in every other case the direct call runs. It
+    synchronises the stream once.
 
     The device path serves one exponent, nbins <= 4096 and nnodes <= 4096;
     anything else is the loop of histograms(rows=...) per node."""
@@ -417,8 +447,14 @@ def level_histograms(arr, bins, nodes, nnodes: int = None, nbins: int = None):
         if dev is None:
             w, cnt = ops.hist_level_words(ctx, x.words, b16, nbins, n16, nnodes)
             return _result(ctx, w, exps, shape), cnt.astype(np.int64).reshape(shape)
-        out, cnt = resident.hist_level(ctx.device_key(dev), x._dw(dev), resident.upload(b16.view(np.int16), dev), nbins,
-                                       resident.upload(n16.view(np.int16), dev), nnodes)
+        bd, ndv = resident.upload(b16.view(np.int16), dev), resident.upload(n16.view(np.int16), dev)
+        if _level_subtracts(ctx, dev, parent, subtract, arr.size, shape, e0):
+            out, cnt = resident.hist_level_sub(ctx.device_key(dev), x._dw(dev), bd, nbins, ndv, nnodes,
+                                               parent[0]._dw(dev),
+                                               resident.upload(np.ascontiguousarray(parent[1], np.int32).reshape(-1),
+                                                               dev))
+        else:
+            out, cnt = resident.hist_level(ctx.device_key(dev), x._dw(dev), bd, nbins, ndv, nnodes)
         counts = resident.download(cnt, np.int32).astype(np.int64).reshape(shape)
         return PaillierArray.from_device(ctx, out, exps, shape), counts
     except _Fallback:
