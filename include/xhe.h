@@ -11,10 +11,11 @@
  * gives the thread-local message. A key handle is immutable after creation
  * and may be shared between threads; calls on distinct streams are reentrant.
  *
- * Ciphertext operands: the twelve entry points that read ciphertext words -
+ * Ciphertext operands: the thirteen entry points that read ciphertext words -
  * xhe_decrypt, xhe_mulmod, xhe_powmod, xhe_pack, xhe_invert, xhe_segprod,
  * xhe_segscan, xhe_hist, xhe_hist_level, xhe_hist_level_sub (its rows and its
- * parent rows), xhe_multiexp and xhe_bucketexp (and their _host variants) -
+ * parent rows), xhe_hist_sparse (its rows and its total), xhe_multiexp and
+ * xhe_bucketexp (and their _host variants) -
  * accept ANY value in
  * [0, 2^(32 n2w))
  * in an operand row, not only residues below n^2: a received payload is not
@@ -305,6 +306,41 @@ int xhe_hist_level_sub(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows
  * for an odd nnodes or fewer than 2 nodes). */
 int xhe_hist_level_sub_route(const xhe_key* key, int64_t n_rows, int nnodes, int nfeat, int nbins);
 
+/* Sparse-aware histogram: the result of xhe_hist - c, bins, bins_stride,
+ * nfeat, rows, count, tile_rows, out, cnt, the output layout and the argument
+ * checks are xhe_hist's, nbins in [1, 4095] - where of feature f only the
+ * entries outside its zero bin zero_bin_dev[f] are multiplied, and that bin is
+ * total / (the product of the feature's other entries) mod n^2. A zero bin >=
+ * nbins (0xFFFF by convention) marks the feature dense: every row multiplied,
+ * nothing rebuilt. An entry with an id >= nbins is dropped for its feature as
+ * in xhe_hist; it counts as an entry outside the zero bin (total holds it).
+ * total_dev: one ciphertext row (any value below 2^(32 n2w)) congruent to the
+ * product of the call's `count` elements, trusted as `parent` is in
+ * xhe_hist_level_sub; NULL: computed here with `count` products.
+ * nnz_bound: the caller's upper bound on the entries outside the zero bins
+ * over all features, a dense feature counting `count`. It sizes the call's
+ * grids and workspaces and is not trusted: the device compares the real count
+ * with it, and past it no kernel of the call stores outside the call's
+ * buffers and the call returns XHE_EINVAL (out and cnt are then undefined).
+ * Same words and counts as xhe_hist whenever every inverted product is a unit
+ * mod n^2; XHE_ENOINV otherwise, as xhe_invert reports it. An operand that is
+ * no unit but lies only in zero bins or under dense features is never
+ * inverted. count == 0 writes ones and zero counts. The call synchronises
+ * `stream` once (the batch inversion's one host inverse) and enqueues the zero
+ * bins behind it. zero_bin_dev is device memory, so a call without any sparse
+ * feature still runs that inversion (over ones): callers that hold the zero
+ * bins on the host call xhe_hist then, as xhe_hist_sparse_host does. Timed as
+ * "k_hist_sparse" under xhe_profile (its stages as "k_sparse_order",
+ * "k_sparse_tile", "k_sparse_fold", "k_sparse_zero"). */
+int xhe_hist_sparse(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const uint16_t* bins_dev,
+                    int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin_dev, const int32_t* rows_dev,
+                    int64_t count, int64_t nnz_bound, const uint32_t* total_dev, int tile_rows, uint32_t* out_dev,
+                    int32_t* cnt_dev, void* stream);
+/* Host only, no device work: 1 when the planner (paths.hpp hist_sparse)
+ * expects xhe_hist_sparse to beat xhe_hist for `nnz` entries outside the zero
+ * bins (a dense feature counting `count`), with or without a total. */
+int xhe_hist_sparse_route(const xhe_key* key, int64_t count, int nfeat, int nbins, int64_t nnz, int have_total);
+
 /* Encrypted matrix-vector product as a multi-exponentiation: the object-dtype
  * np.matmul(enc[B], X[B, D]) of logistic_regression/trainer.py:166 (and
  * linear_regression/trainer.py:207, poisson_regression/trainer.py:267,
@@ -400,6 +436,11 @@ int xhe_segscan_host(const xhe_key* key, const uint32_t* c, int64_t count, const
 int xhe_hist_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins, int64_t bins_stride,
                   int nfeat, int nbins, const int32_t* rows, int64_t count, int tile_rows, uint32_t* out,
                   int32_t* cnt);
+/* xhe_hist_sparse on host buffers (zero_bin and total host memory too); rows validated as in xhe_hist_host; the
+ * bound is the exact count, taken here. Without a sparse feature it is xhe_hist_host. */
+int xhe_hist_sparse_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                         int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin, const int32_t* rows,
+                         int64_t count, const uint32_t* total, int tile_rows, uint32_t* out, int32_t* cnt);
 /* xhe_hist_level on host buffers. */
 int xhe_hist_level_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
                         int64_t bins_stride, int nfeat, int nbins, const uint16_t* node, int nnodes, int tile_rows,

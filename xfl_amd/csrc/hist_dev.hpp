@@ -77,8 +77,10 @@ constexpr int hist_waves() {
 // base + i without row ids) by the bin ids fb[row] of one feature. The bin's
 // partial row goes to column bin * bin_stride of mypart ([S4][ncols] strided
 // rows), its count is added to cnt_f[bin] (null: no counts); mypark: the
-// block's tile_rows / kHistParkDiv parked rows.
-template <class MN2, int PW>
+// block's tile_rows / kHistParkDiv parked rows. Hidden (the sparse histogram's
+// lists, hist_sparse_dev.hpp): an id at or above nbins - 1 counts into the last
+// bin instead of dropping the element.
+template <class MN2, int PW, bool Hidden = false>
 XHE_DEV void hist_tile_block(KeyDev key, const uint32_t* __restrict__ Nn2, const uint32_t* __restrict__ words,
                              const uint16_t* __restrict__ fb, int nbins, const int32_t* __restrict__ rows_idx,
                              int64_t base, int m, int tile_rows, uint32_t* mypart, int64_t bin_stride, int ncols,
@@ -93,12 +95,17 @@ XHE_DEV void hist_tile_block(KeyDev key, const uint32_t* __restrict__ Nn2, const
   constexpr int S4 = MN2::S4, NGRP = 256 / MN2::TPI;
   const int tid = threadIdx.x, grp = tid / MN2::TPI;
   auto row_of = [&](int i) -> int64_t { return rows_idx ? (int64_t)rows_idx[base + i] : base + i; };
+  auto id_of = [&](int i) -> uint32_t {
+    const uint32_t id = fb[row_of(i)];
+    if constexpr (Hidden) return id < (uint32_t)nbins ? id : (uint32_t)nbins - 1u;
+    else return id;
+  };
 
   for (int b = tid; b < nbins; b += 256) A[b] = 0;
   if (tid == 0) s_total = s_nwork = s_nslots = 0;
   __syncthreads();
   for (int i = tid; i < m; i += 256) {
-    const uint32_t id = fb[row_of(i)];
+    const uint32_t id = id_of(i);
     if (id < (uint32_t)nbins) atomicAdd(&A[id], 1u);
   }
   __syncthreads();
@@ -111,7 +118,7 @@ XHE_DEV void hist_tile_block(KeyDev key, const uint32_t* __restrict__ Nn2, const
   }
   __syncthreads();
   for (int i = tid; i < m; i += 256) {
-    const uint32_t id = fb[row_of(i)];
+    const uint32_t id = id_of(i);
     if (id < (uint32_t)nbins) list[atomicAdd(&B[id], 1u)] = (uint16_t)i;
   }
   __syncthreads();

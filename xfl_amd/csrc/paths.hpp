@@ -347,6 +347,60 @@ inline int sib_chunk(int64_t M) {
   return (int)(c < kSibChunkMin ? kSibChunkMin : c > kSibChunkMax ? kSibChunkMax : c);
 }
 
+// ------------------------------------------------ sparse-aware histogram
+// xhe_hist_sparse (hist_sparse_dev.hpp) multiplies, per feature, only the
+// entries outside the feature's zero bin and rebuilds that bin from the
+// product T of all elements. The kept entries of a feature are compacted into
+// tile slots that each lie inside one feature, so the tile is hist_tile's for
+// the mean list length nnz_bound / nfeat and nbins + 1 internal bins, but not
+// above the power of two at or above that mean (floor kHistTileMin):
+// level_tile's reasoning with the feature in the node's place. A feature with
+// c kept entries takes ceil(c / tile) slots; the sum is at most floor(
+// nnz_bound / tile) + nfeat, which sizes every grid and workspace. Products
+// mod n^2 of a call:
+//   direct   nfeat count
+//   sparse   nnz + (T given ? 0 : count) + (nbins + 1) slots + nfeat (nbins + 4)
+// (a partial row per (slot, internal bin) to fold, and per feature the nbins
+// rows of Q_f, its share of the inversion tree and the two products of the
+// zero bin). The route takes the sparse call when direct >= kSparseMinSaving
+// x sparse. kSparseMinSaving is a measured figure, not the model's 1 (DESIGN
+// "Sparse-aware histogram", profiles/r28/hist_sparse/): on config 5 (100 k rows
+// x 64 features x 256 bins, 2048 bits, bin 0 every feature's zero bin), ms of
+// xhe_hist / xhe_hist_sparse and the model's ratio by the fraction d of rows
+// outside the zero bin:
+//   d      T given                  T computed
+//   0.5    18.44 / 14.71   1.865    18.49 / 19.47   1.812   (slower)
+//   0.25   18.44 / 10.03   3.493    18.54 / 14.74   3.312
+//   0.1    18.15 /  5.72   7.673    17.96 / 10.33   6.852
+//   0.05   17.41 /  4.51   12.455   17.18 /  9.07   10.426
+//   0.01   16.58 /  2.85   28.166   16.47 /  7.33   19.558
+// against a spread of 0.4 ms. 1.865 is the lowest ratio measured faster (by 3.7
+// ms) and 1.812 the one measured slower (by 1 ms: computing T took 3.9 ms,
+// thirteen times the `count` products the model charges), so the route stops
+// between them. Nothing between 1.865 and 3.312 was measured without T.
+constexpr int kSparseBinsMax = 4095;
+constexpr double kSparseMinSaving = 1.86;
+
+inline int sparse_tile(int64_t nnz_bound, int nfeat, int nbins) {
+  const int64_t mean = (nnz_bound + nfeat - 1) / (nfeat > 0 ? nfeat : 1);
+  int tile = hist_tile(mean, nfeat, nbins + 1);
+  int cap = kHistTileMin;
+  while (cap < kHistTileMax && cap < mean) cap <<= 1;
+  return tile < cap ? tile : cap;
+}
+
+inline int64_t sparse_tiles_max(int64_t nnz_bound, int nfeat, int tile_rows) { return nnz_bound / tile_rows + nfeat; }
+
+inline bool hist_sparse(int64_t count, int nfeat, int nbins, int64_t nnz, bool have_total) {
+  if (count < 1 || nfeat < 1 || nbins < 1 || nbins > kSparseBinsMax || nnz < 0 || nnz > (int64_t)nfeat * count)
+    return false;
+  const double slots = (double)sparse_tiles_max(nnz, nfeat, sparse_tile(nnz, nfeat, nbins));
+  const double direct = (double)nfeat * (double)count;
+  const double sparse =
+      (double)nnz + (have_total ? 0.0 : (double)count) + (nbins + 1.0) * slots + (double)nfeat * (nbins + 4.0);
+  return direct >= kSparseMinSaving * sparse;
+}
+
 enum class Horner {
   WAVE,   // 2048, 16 lanes: k_mexp_horner_wave, one 16-wave block per column (latency)
   LANES,  // k_mexp_horner

@@ -34,6 +34,7 @@
 #include "hist_dev.hpp"
 #include "hist_level_dev.hpp"
 #include "hist_sub_dev.hpp"
+#include "hist_sparse_dev.hpp"
 #include "bucket_dev.hpp"
 
 using namespace xhe;
@@ -1559,6 +1560,109 @@ int hist_level_sub_impl(const xhe_key* k, const uint32_t* c, int64_t n_rows, con
   return XHE_OK;
 }
 
+// Sparse-aware histogram (hist_sparse_dev.hpp). Grids and workspaces come from
+// the caller's bound on the kept entries; the counts stay on the device. The
+// slots run in launch groups of gt under the row cap (partial and parked rows,
+// hist_group's count per slot) and leave their folds in the accumulator rows,
+// nfeat * (nbins + 1) of them for the whole call. T, where the caller has
+// none, is xhe_hist's tile and stage B over one feature with one bin. The
+// flag is copied back ahead of the inversion and read behind its
+// synchronisation.
+template <class Sh>
+int hist_sparse_impl(const xhe_key* k, const uint32_t* c, int64_t n_rows, const uint16_t* bins, int64_t bins_stride,
+                     int nfeat, int nbins, const uint16_t* zero_bin, const int32_t* rows_idx, int64_t count,
+                     int64_t nnz_bound, const uint32_t* total, int tile_rows, uint32_t* out, int32_t* cnt,
+                     hipStream_t s) {
+  using MN2 = typename Sh::MN2;
+  const int S4 = MN2::S4, nb = nbins + 1;
+  auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
+  if (!tile_rows) tile_rows = paths::sparse_tile(nnz_bound, nfeat, nbins);
+  const int64_t tmax = paths::sparse_tiles_max(nnz_bound, nfeat, tile_rows);
+  const int64_t gt = std::max<int64_t>(1, std::min<int64_t>(tmax, kChunk / (nb + tile_rows / kHistParkDiv)));
+  const int64_t nacc = (int64_t)nfeat * nb, eb = (count + kSparseBlockElems - 1) / kSparseBlockElems;
+  if (nnz_bound > INT32_MAX || count > INT32_MAX || tmax > INT32_MAX || nfeat > 65535 || eb > INT32_MAX ||
+      nacc * MN2::TPI > (int64_t)INT32_MAX * 256 / 2)
+    throw std::logic_error("xhe_hist_sparse: problem too large for one call");
+  const size_t lds = (size_t)paths::hist_lds_bytes(tile_rows, nb);
+  const size_t rb = (size_t)k->n2w * 4;
+  ProfScope ps("k_hist_sparse", s);
+  // (declared in reverse, filled in allocation order: DevBuf's note)
+  DevBuf inv, qw, acc, tw, list, meta;
+  // nnz[nfeat] | cursor[nfeat] | nzsum[nfeat] | flag | hcnt[nacc] (zeroed) | tile_begin[nfeat + 1] | list_base[nfeat] | tile_node[tmax]
+  const int64_t nzero = 3 * (int64_t)nfeat + 1 + nacc;
+  meta = DevBuf((size_t)(nzero + 2 * (int64_t)nfeat + 1 + tmax) * 4, s, DevBuf::kAsync);
+  list = DevBuf((size_t)nnz_bound * 4, s, DevBuf::kAsync);
+  tw = DevBuf(rb, s, DevBuf::kAsync);
+  acc = DevBuf((size_t)S4 * nacc * 4, s, DevBuf::kAsync);
+  int32_t* nnz = meta.as<int32_t>();
+  int32_t *cursor = nnz + nfeat, *nzsum = cursor + nfeat, *flag = nzsum + nfeat, *hcnt = flag + 1;
+  int32_t *tile_begin = hcnt + nacc, *list_base = tile_begin + nfeat + 1, *tile_node = list_base + nfeat;
+  launch(k_hist_zero, dim3((unsigned)((nzero + 255) / 256)), dim3(256), s, nnz, nzero);
+  {
+    ProfScope po("k_sparse_order", s);
+    const dim3 grid((unsigned)eb, (unsigned)nfeat);
+    launch(k_sparse_count, grid, dim3(256), s, bins, bins_stride, nbins, zero_bin, rows_idx, count, nnz);
+    launch(k_sparse_plan, dim3(1), dim3(256), s, nnz, nfeat, tile_rows, nnz_bound, tmax, tile_begin, list_base,
+           tile_node, flag);
+    launch(k_sparse_scatter, grid, dim3(256), s, bins, bins_stride, nbins, zero_bin, rows_idx, count, list_base, cursor,
+           flag, list.as<int32_t>());
+  }
+  if (!total) {  // T from the rows themselves: one feature, one bin
+    DevBuf zb((size_t)(n_rows + 1) / 2 * 4, s, DevBuf::kAsync);
+    launch(k_hist_zero, dim3((unsigned)(((n_rows + 1) / 2 + 255) / 256)), dim3(256), s, zb.as<int32_t>(),
+           (n_rows + 1) / 2);
+    hist_rows<Sh>(k, c, zb.as<uint16_t>(), n_rows, 1, 1, rows_idx, count, 0, nullptr, s,
+                  [&](int, int, const DevBuf& cur) {
+                    launch(k_from_mont_rows<MN2>, blocks(1), dim3(256), s, k->kd, n2h<MN2>(k).N, cur.as<uint32_t>(),
+                           (int64_t)1, tw.as<uint32_t>());
+                  });
+    total = tw.as<uint32_t>();
+  }
+  for (int64_t t0 = 0; t0 < tmax; t0 += gt) {
+    const int ng = (int)std::min(gt, tmax - t0);
+    const int ncols = ng * nb;
+    const int passes = paths::level_fold_passes(std::min<int64_t>(count, (int64_t)ng * tile_rows), tile_rows, kRawChunk);
+    DevBuf park, part;
+    part = DevBuf((size_t)S4 * ncols * 4, s, DevBuf::kAsync);
+    park = DevBuf((size_t)ng * (tile_rows / kHistParkDiv) * S4 * 4, s, DevBuf::kAsync);
+    {
+      ProfScope pt("k_sparse_tile", s);
+      hipLaunchKernelGGL((k_sparse_tile<MN2, Sh::RW2>), dim3((unsigned)ng), dim3(256), lds, s, k->kd, n2h<MN2>(k).N, c,
+                         bins, bins_stride, nb, list.as<int32_t>(), nnz, tile_begin, list_base, tile_node, tile_rows,
+                         t0, ncols, part.as<uint32_t>(), park.as<uint32_t>(), hcnt);
+      HIPCHK(hipGetLastError());
+    }
+    ProfScope pf("k_sparse_fold", s);
+    for (int p = 0; p < passes; ++p)
+      launch(k_sparse_fold_pass<MN2>, blocks((int64_t)ncols), dim3(256), s, k->kd, n2h<MN2>(k).N, part.as<uint32_t>(),
+             ncols, nb, t0, ng, tile_begin, tile_node, flag, p);
+    launch(k_sparse_acc<MN2>, blocks(nacc), dim3(256), s, k->kd, n2h<MN2>(k).N, part.as<uint32_t>(), ncols, nb, nfeat,
+           t0, ng, tile_begin, flag, passes, t0 == 0 ? 1 : 0, acc.as<uint32_t>());
+  }
+  {
+    ProfScope pf("k_sparse_fold", s);
+    launch(k_sparse_out<MN2>, blocks(nacc), dim3(256), s, k->kd, n2h<MN2>(k).N, acc.as<uint32_t>(), nfeat, nbins,
+           zero_bin, hcnt, flag, out, cnt, nzsum);
+  }
+  ProfScope pz("k_sparse_zero", s);
+  std::vector<int64_t> seg((size_t)nfeat + 1);
+  for (int64_t i = 0; i <= nfeat; ++i) seg[(size_t)i] = i * nb;
+  const DevBuf q = reduce_segments<Sh, MN2>(k, std::move(acc), nacc, std::move(seg), s);
+  qw = DevBuf((size_t)nfeat * rb, s, DevBuf::kAsync);
+  inv = DevBuf((size_t)nfeat * rb, s, DevBuf::kAsync);
+  launch(k_from_mont_rows<MN2>, blocks(nfeat), dim3(256), s, k->kd, n2h<MN2>(k).N, q.as<uint32_t>(), (int64_t)nfeat,
+         qw.as<uint32_t>());
+  int32_t over = 0;
+  HIPCHK(hipMemcpyAsync(&over, flag, 4, hipMemcpyDeviceToHost, s));
+  // (synchronises the stream: the batch inversion's one scalar inverse is the host's)
+  const int rc = invert_impl<Sh, MN2>(k, qw.as<uint32_t>(), nfeat, inv.as<uint32_t>(), s);
+  if (over) return fail(XHE_EINVAL, "xhe_hist_sparse: more entries outside the zero bins than nnz_bound");
+  if (rc != XHE_OK) return rc;
+  launch((k_sparse_zero<MN2, Sh::RW2>), blocks(nfeat), dim3(256), s, k->kd, n2h<MN2>(k).N, inv.as<uint32_t>(), total,
+         nfeat, nbins, zero_bin, count, nzsum, out, cnt);
+  return XHE_OK;
+}
+
 // Bucket multi-exponentiation (bucket_dev.hpp). The columns run in groups
 // whose digit matrix stays within kBucketDigitCap ids (and hist_rows groups
 // the (column, window) features within kChunk rows below that); every group
@@ -1992,6 +2096,46 @@ int xhe_hist_level_sub(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows
 int xhe_hist_level_sub_route(const xhe_key* key, int64_t n_rows, int nnodes, int nfeat, int nbins) {
   (void)key;  // (one constant serves every key size: DESIGN "Histogram subtraction")
   return paths::level_sub(n_rows, nnodes, nfeat, nbins) ? 1 : 0;
+}
+
+namespace {
+int hist_sparse_args(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins, int64_t bins_stride,
+                     int nfeat, int nbins, const uint16_t* zero_bin, const int32_t* rows, int64_t count,
+                     int64_t nnz_bound, const uint32_t* total, int tile_rows, const uint32_t* out, const char* who) {
+  if (int rc = hist_args(key, c, n_rows, bins, bins_stride, nfeat, nbins, rows, count, tile_rows, out, who)) return rc;
+  if (nbins > paths::kSparseBinsMax) return fail(XHE_EINVAL, std::string(who) + ": nbins must be in [1, 4095]");
+  if (!zero_bin || nnz_bound < 0) return fail(XHE_EINVAL, std::string(who) + ": zero bins missing or a negative nnz_bound");
+  if (total && out < total + key->n2w && total < out + (size_t)nfeat * nbins * key->n2w)
+    return fail(XHE_EINVAL, std::string(who) + ": out overlaps total");
+  return XHE_OK;
+}
+}  // namespace
+
+int xhe_hist_sparse(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const uint16_t* bins_dev,
+                    int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin_dev, const int32_t* rows_dev,
+                    int64_t count, int64_t nnz_bound, const uint32_t* total_dev, int tile_rows, uint32_t* out_dev,
+                    int32_t* cnt_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (int rc = hist_sparse_args(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins, zero_bin_dev, rows_dev, count,
+                                  nnz_bound, total_dev, tile_rows, out_dev, "xhe_hist_sparse"))
+      return rc;
+    DevGuard dg(key->device);
+    return with_shape(key->K, [&](auto sh) -> int {
+      if (count == 0) {  // ones and zero counts, as xhe_hist writes them
+        hist_impl<decltype(sh)>(key, c_dev, bins_dev, bins_stride, nfeat, nbins, rows_dev, count, tile_rows, out_dev,
+                                cnt_dev, (hipStream_t)stream);
+        return XHE_OK;
+      }
+      return hist_sparse_impl<decltype(sh)>(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins, zero_bin_dev,
+                                            rows_dev, count, nnz_bound, total_dev, tile_rows, out_dev, cnt_dev,
+                                            (hipStream_t)stream);
+    });
+  });
+}
+
+int xhe_hist_sparse_route(const xhe_key* key, int64_t count, int nfeat, int nbins, int64_t nnz, int have_total) {
+  (void)key;  // (one constant serves every key size: DESIGN "Sparse-aware histogram")
+  return paths::hist_sparse(count, nfeat, nbins, nnz, have_total != 0) ? 1 : 0;
 }
 
 namespace {
@@ -3021,6 +3165,52 @@ int xhe_hist_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const u
     int rc = xhe_hist(key, dc.as<uint32_t>(), n_rows, db.as<uint16_t>(), bins_stride, nfeat, nbins,
                       rows ? dr.as<int32_t>() : nullptr, count, tile_rows, dout.as<uint32_t>(),
                       cnt ? dcnt.as<int32_t>() : nullptr, st.s);
+    if (rc != XHE_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
+    if (cnt) HIPCHK(hipMemcpyAsync(cnt, dcnt.p, nb, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    return XHE_OK;
+  });
+}
+
+int xhe_hist_sparse_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                         int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin, const int32_t* rows,
+                         int64_t count, const uint32_t* total, int tile_rows, uint32_t* out, int32_t* cnt) {
+  return guarded([&]() -> int {
+    if (int rc = hist_sparse_args(key, c, n_rows, bins, bins_stride, nfeat, nbins, zero_bin, rows, count, 0, total,
+                                  tile_rows, out, "xhe_hist_sparse_host"))
+      return rc;
+    for (int64_t i = 0; rows && i < count; ++i)
+      if (rows[i] < 0 || rows[i] >= n_rows) return fail(XHE_EINVAL, "xhe_hist_sparse_host: row id out of range");
+    // the bound is the exact count here; without a sparse feature the dense call serves (no inversion, no wait in it)
+    int64_t nnz = 0;
+    bool any = false;
+    for (int f = 0; f < nfeat; ++f) {
+      const uint16_t z = zero_bin[f];
+      if (z >= nbins) {
+        nnz += count;
+        continue;
+      }
+      any = true;
+      const uint16_t* fb = bins + (size_t)f * bins_stride;
+      for (int64_t i = 0; i < count; ++i) nnz += fb[rows ? rows[i] : i] != z;
+    }
+    if (!any) return xhe_hist_host(key, c, n_rows, bins, bins_stride, nfeat, nbins, rows, count, tile_rows, out, cnt);
+    DevGuard dg(key->device);
+    Stream st;
+    const size_t cb = (size_t)n_rows * key->n2w * 4, bb = ((size_t)(nfeat - 1) * bins_stride + n_rows) * 2,
+                 ob = (size_t)nfeat * nbins * key->n2w * 4, nb = (size_t)nfeat * nbins * 4, tb = (size_t)key->n2w * 4;
+    DevBuf dc(cb, st.s), db(bb, st.s), dz((size_t)nfeat * 2, st.s), dr(rows ? (size_t)count * 4 : 0, st.s),
+        dt(total ? tb : 0, st.s), dout(ob, st.s), dcnt(nb, st.s);
+    if (n_rows > 0) HIPCHK(hipMemcpyAsync(dc.p, c, cb, hipMemcpyHostToDevice, st.s));
+    if (n_rows > 0 && bins) HIPCHK(hipMemcpyAsync(db.p, bins, bb, hipMemcpyHostToDevice, st.s));
+    HIPCHK(hipMemcpyAsync(dz.p, zero_bin, (size_t)nfeat * 2, hipMemcpyHostToDevice, st.s));
+    if (rows && count > 0) HIPCHK(hipMemcpyAsync(dr.p, rows, (size_t)count * 4, hipMemcpyHostToDevice, st.s));
+    if (total) HIPCHK(hipMemcpyAsync(dt.p, total, tb, hipMemcpyHostToDevice, st.s));
+    int rc = xhe_hist_sparse(key, dc.as<uint32_t>(), n_rows, db.as<uint16_t>(), bins_stride, nfeat, nbins,
+                             dz.as<uint16_t>(), rows ? dr.as<int32_t>() : nullptr, count, nnz,
+                             total ? dt.as<uint32_t>() : nullptr, tile_rows, dout.as<uint32_t>(),
+                             cnt ? dcnt.as<int32_t>() : nullptr, st.s);
     if (rc != XHE_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
     if (cnt) HIPCHK(hipMemcpyAsync(cnt, dcnt.p, nb, hipMemcpyDeviceToHost, st.s));

@@ -493,6 +493,49 @@ def hist_words(ctx, cw, bins, nbins, rows=None):
     return out, cnt
 
 
+def hist_sparse_words(ctx, cw, bins, nbins, zero_bin, rows=None, total=None):
+    """hist_words through xhe_hist_sparse_host: zero_bin [nfeat] uint16, the bin
+    of each feature that is rebuilt from the total instead of multiplied (>=
+    nbins: a dense feature); total: [n2w] words of the product of the call's
+    elements, or None. Raises ZeroDivisionError when an inverted product has no
+    inverse mod n^2."""
+    cw = _u32(cw)
+    bins = np.ascontiguousarray(bins, dtype=np.uint16)
+    if bins.ndim != 2 or bins.shape[1] != cw.shape[0]:
+        raise ValueError("hist_sparse: bins must be [nfeat, n_rows]")
+    n_rows, nfeat = cw.shape[0], bins.shape[0]
+    zero_bin = np.ascontiguousarray(zero_bin, dtype=np.uint16).reshape(-1)
+    if zero_bin.shape[0] != nfeat:
+        raise ValueError("hist_sparse: one zero bin per feature")
+    count = n_rows
+    if rows is not None:
+        rows = _i32(rows).reshape(-1)
+        count = rows.shape[0]
+        if count and (rows.min() < 0 or rows.max() >= n_rows):
+            raise ValueError("hist_sparse: row id out of range")
+    n2w = n2w_of(ctx)
+    if total is not None:
+        total = _u32(total).reshape(-1)
+        if total.shape[0] != n2w:
+            raise ValueError("hist_sparse: total must be one ciphertext row")
+    out = np.empty((nfeat * nbins, n2w), dtype=np.uint32)
+    cnt = np.empty(nfeat * nbins, dtype=np.int32)
+    dk = ctx.device_key(ctx.own_device())
+    nat.check(nat.lib().xhe_hist_sparse_host(dk.handle, _vp(cw) if n_rows else None, n_rows,
+                                             _vp(bins) if n_rows else None, n_rows, nfeat, int(nbins), _vp(zero_bin),
+                                             _vp(rows) if rows is not None else None, count,
+                                             _vp(total) if total is not None else None, 0, _vp(out), _vp(cnt)),
+              "hist_sparse")  # (XHE_ENOINV: ZeroDivisionError)
+    return out, cnt
+
+
+def hist_sparse_route(ctx, dev, count, nfeat, nbins, nnz, have_total):
+    """whether the planner expects xhe_hist_sparse to beat xhe_hist at this shape and density (no device work)"""
+    dk = ctx.device_key(dev)
+    return bool(nat.lib().xhe_hist_sparse_route(dk.handle, int(count), int(nfeat), int(nbins), int(nnz),
+                                                int(bool(have_total))))
+
+
 def hist_level_words(ctx, cw, bins, nbins, nodes, nnodes):
     """out[(v * nfeat + f) * nbins + b] = prod of the rows r of cw with
     nodes[r] == v and bins[f][r] == b mod n^2, and their number: every node

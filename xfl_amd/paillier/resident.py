@@ -767,6 +767,39 @@ def hist(dk, c, bins_d, nbins, rows=None, tile_rows=0):
     return out, cnt
 
 
+def hist_sparse(dk, c, bins_d, nbins, zero_bin_d, nnz_bound, rows=None, total_d=None, tile_rows=0):
+    """hist by the sparse-aware call (xhe_hist_sparse): zero_bin_d a device
+    int16 tensor [nfeat] of uint16 bins (>= nbins: a dense feature) whose rows
+    are not multiplied but rebuilt from the total; nnz_bound the caller's bound
+    on the entries outside them (a dense feature counting every element;
+    ValueError when the device counts more); total_d a device row [n2w] holding
+    the product of the call's elements, or None. Same result as hist. The call
+    synchronises the stream once; ZeroDivisionError when an inverted product
+    has no inverse mod n^2."""
+    torch = _torch()
+    dev = dk.device
+    n_rows, nfeat = c.shape[0], bins_d.shape[0]
+    if bins_d.dim() != 2 or bins_d.element_size() != 2 or bins_d.stride(1) != 1:
+        raise ValueError("hist_sparse: bins must be a [nfeat, stride] tensor of 16-bit ids, rows contiguous")
+    if rows is not None and (rows.dim() != 1 or rows.dtype != torch.int32 or not rows.is_contiguous()):
+        raise ValueError("hist_sparse: rows must be a contiguous int32 tensor")
+    if zero_bin_d.dim() != 1 or zero_bin_d.element_size() != 2 or zero_bin_d.shape[0] != nfeat or \
+            not zero_bin_d.is_contiguous():
+        raise ValueError("hist_sparse: zero bins must be a contiguous [nfeat] tensor of 16-bit ids")
+    if total_d is not None and (total_d.numel() != dk.n2w or total_d.element_size() != 4):
+        raise ValueError("hist_sparse: total must be one ciphertext row")
+    count = n_rows if rows is None else rows.shape[0]
+    with _On(dev):
+        out = torch.empty((nfeat * nbins, dk.n2w), dtype=torch.int32, device=f"cuda:{dev}")
+        cnt = torch.empty(nfeat * nbins, dtype=torch.int32, device=f"cuda:{dev}")
+        src = c.contiguous()
+        tot = None if total_d is None else total_d.contiguous()
+    nat.check(nat.lib().xhe_hist_sparse(dk.handle, _dp(src), n_rows, _dp(bins_d), bins_d.stride(0), nfeat, int(nbins),
+                                        _dp(zero_bin_d), _dp(rows), count, int(nnz_bound), _dp(tot), int(tile_rows),
+                                        _dp(out), _dp(cnt), _sp(dev)), "hist_sparse")
+    return out, cnt
+
+
 def hist_level(dk, c, bins_d, nbins, node_d, nnodes, tile_rows=0):
     """Per-(node, feature, bin) sums and counts of the device ciphertext rows c
     [n_rows, n2w] in one call (xhe_hist_level): bins_d as hist's, node_d a

@@ -272,7 +272,34 @@ def cumsum_segments(arr, lengths):
         return PaillierArray._from_sequence(res) if arr._has_na() else _wrap(res)
 
 
-def histograms(arr, bins, nbins: int = None, rows=None):
+def _zero_bins(default_bin, nfeat, nbins):
+    """default_bin as one uint16 zero bin per feature (0xFFFF: dense), or None when no feature has one"""
+    if default_bin is None:
+        return None
+    db = np.asarray([-1 if d is None else d for d in np.asarray(default_bin, dtype=object).reshape(-1)],
+                    dtype=np.int64)
+    if db.size == 1:
+        db = np.repeat(db, nfeat)
+    if db.size != nfeat:
+        raise ValueError("histograms: default_bin must be one bin or one per feature")
+    zb = np.where((db < 0) | (db >= nbins), 0xFFFF, db).astype(np.uint16)
+    return zb if (zb != 0xFFFF).any() else None
+
+
+def _total_row(ctx, total, e0, n2w):
+    """the [n2w] host words of `total` (a ciphertext or a one-element array) at exponent e0"""
+    from .paillier import PaillierCiphertext
+    from .paillier.array import PaillierArray
+    if isinstance(total, PaillierCiphertext):
+        total = PaillierArray(np.array([total], dtype=object))
+    if not isinstance(total, PaillierArray) or total.size != 1 or total._has_na():
+        raise ValueError("histograms: total must be a ciphertext or a one-element array")
+    if int(total.exponents[0]) != e0:
+        raise ValueError("histograms: total must be at the column's exponent")
+    return np.array(total._aligned_words(n2w).words, dtype=np.uint32).reshape(n2w)  # (a copy: the words are read-only)
+
+
+def histograms(arr, bins, nbins: int = None, rows=None, default_bin=None, total=None, sparse: bool = None):
     """Every feature's per-bin sums and counts of one ciphertext column in ONE
     device call (xhe_hist): what the per-column
     DataFrame.groupby(feature)[column].agg({'count', 'sum'}) loops of
@@ -288,8 +315,22 @@ def histograms(arr, bins, nbins: int = None, rows=None):
     0 - at the inputs' common exponent and in HBM when the input is; counts an
     int64 array of the same shape. Needs only the public key.
 
+    default_bin: an int, or one per feature - the bin that holds the feature's
+    value 0 on one-hot, count or mostly-zero data; None or a negative entry
+    marks the feature dense. The rows in it are then not multiplied: the bin is
+    what is left of the product of all selected elements (xhe_hist_sparse), the
+    same ciphertexts bit for bit. total: that product, a ciphertext or a
+    one-element array at the column's exponent (the parent node's histogram has
+    it in any feature's bins), else it is computed. sparse: None asks the
+    planner with the entries outside the default bins counted from `bins`, True
+    forces the sparse call, False never takes it. Raises ZeroDivisionError when
+    a product that has to be inverted is no unit mod n^2 (never for
+    ciphertexts of this key).
+
     The device path serves arrays with one exponent and nbins <= 4096; anything
-    else takes the drop-in's groupby sum feature by feature."""
+    else takes the drop-in's groupby sum feature by feature. Mixed exponents,
+    missing entries and more than 4095 bins keep the dense path whatever
+    default_bin says."""
     from .paillier import PaillierCiphertext, ops, resident
     from .paillier.array import NA_EXP, PaillierArray, _Fallback, _result
     if isinstance(arr, np.ndarray) and arr.dtype == object and arr.ndim == 1 and \
@@ -335,11 +376,31 @@ def histograms(arr, bins, nbins: int = None, rows=None):
         u16 = np.where(ids < 0, 0xFFFF, ids).astype(np.uint16)
         exps = np.full(nfeat * nbins, e0, dtype=np.int32)
         dev = resident.device_for(ctx, -1, x.size, 4 * n2w)
+        count = arr.size if rows is None else rows.size
+        zb = None
+        if sparse is not False and nbins <= 4095 and count and not arr._has_na():
+            zb = _zero_bins(default_bin, nfeat, nbins)
+        if zb is not None:
+            picked = u16 if rows is None else u16[:, rows]
+            nnz = int(((picked != zb[:, None]) | (zb[:, None] == 0xFFFF)).sum())
+            if not sparse and not ops.hist_sparse_route(ctx, ctx.own_device() if dev is None else dev, count, nfeat,
+                                                        nbins, nnz, total is not None):
+                zb = None
+        tw = _total_row(ctx, total, e0, n2w) if zb is not None and total is not None else None
         if dev is None:
-            w, cnt = ops.hist_words(ctx, x.words, u16, nbins, rows)
+            if zb is not None:
+                w, cnt = ops.hist_sparse_words(ctx, x.words, u16, nbins, zb, rows, tw)
+            else:
+                w, cnt = ops.hist_words(ctx, x.words, u16, nbins, rows)
             return _result(ctx, w, exps, (nfeat, nbins)), cnt.astype(np.int64).reshape(nfeat, nbins)
         rd = None if rows is None else resident.upload_async(rows.astype(np.int32), dev)
-        out, cnt = resident.hist(ctx.device_key(dev), x._dw(dev), resident.upload(u16.view(np.int16), dev), nbins, rd)
+        bd = resident.upload(u16.view(np.int16), dev)
+        if zb is not None:
+            out, cnt = resident.hist_sparse(ctx.device_key(dev), x._dw(dev), bd, nbins,
+                                            resident.upload_async(zb.view(np.int16), dev), nnz, rd,
+                                            None if tw is None else resident.upload_async(tw, dev))
+        else:
+            out, cnt = resident.hist(ctx.device_key(dev), x._dw(dev), bd, nbins, rd)
         counts = resident.download(cnt, np.int32).astype(np.int64).reshape(nfeat, nbins)
         return PaillierArray.from_device(ctx, out, exps, (nfeat, nbins)), counts
     except _Fallback:
