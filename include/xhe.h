@@ -11,10 +11,11 @@
  * gives the thread-local message. A key handle is immutable after creation
  * and may be shared between threads; calls on distinct streams are reentrant.
  *
- * Ciphertext operands: the thirteen entry points that read ciphertext words -
+ * Ciphertext operands: the fourteen entry points that read ciphertext words -
  * xhe_decrypt, xhe_mulmod, xhe_powmod, xhe_pack, xhe_invert, xhe_segprod,
  * xhe_segscan, xhe_hist, xhe_hist_level, xhe_hist_level_sub (its rows and its
- * parent rows), xhe_hist_sparse (its rows and its total), xhe_multiexp and
+ * parent rows), xhe_hist_sparse (its rows and its total),
+ * xhe_hist_level_sparse (its rows and its totals), xhe_multiexp and
  * xhe_bucketexp (and their _host variants) -
  * accept ANY value in
  * [0, 2^(32 n2w))
@@ -341,6 +342,45 @@ int xhe_hist_sparse(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, c
  * bins (a dense feature counting `count`), with or without a total. */
 int xhe_hist_sparse_route(const xhe_key* key, int64_t count, int nfeat, int nbins, int64_t nnz, int have_total);
 
+/* Level-wise sparse histogram: the result of xhe_hist_level - c, bins,
+ * bins_stride, nfeat, node, nnodes, tile_rows, out, cnt, the output layout and
+ * the argument checks are xhe_hist_level's, nbins in [1, 4095] - where of
+ * (node v, feature f) only the entries outside the feature's zero bin
+ * zero_bin_dev[f] are multiplied, and that bin is total[v] / (the product of
+ * (v, f)'s other entries) mod n^2. A zero bin >= nbins (0xFFFF by convention)
+ * marks the feature dense. An entry with an id >= nbins is dropped for its
+ * feature as in xhe_hist_level; it counts as an entry outside the zero bin
+ * (total[v] holds it). A row with a node id >= nnodes is skipped everywhere and
+ * is in no total.
+ * total_dev: nnodes ciphertext rows (any values below 2^(32 n2w)), row v
+ * congruent to the product of node v's rows, trusted as `parent` is in
+ * xhe_hist_level_sub; NULL: computed here with n_rows products.
+ * nnz_bound: the caller's upper bound on the entries outside the zero bins over
+ * all features, counted over the rows with a node id < nnodes, a dense feature
+ * counting every such row. It sizes the call's grids and workspaces and is not
+ * trusted: the device compares the real count with it, and past it no kernel
+ * of the call stores outside the call's buffers and the call returns
+ * XHE_EINVAL (out and cnt are then undefined).
+ * Same words and counts as xhe_hist_level whenever every inverted product is a
+ * unit mod n^2; XHE_ENOINV otherwise, as xhe_invert reports it. An operand that
+ * is no unit but lies only in zero bins or under dense features is never
+ * inverted. n_rows == 0 writes ones and zero counts. XHE_EINVAL also for out
+ * overlapping c or total. The call synchronises `stream` once (the batch
+ * inversion's one host inverse over the nnodes x nfeat products) and enqueues
+ * the zero bins behind it; as with xhe_hist_sparse, a caller that holds the
+ * zero bins on the host and has no sparse feature calls xhe_hist_level. Timed
+ * as "k_hist_level_sparse" under xhe_profile (its stages as "k_lsp_order",
+ * "k_lsp_totals", "k_lsp_tile", "k_lsp_fold", "k_lsp_zero"). */
+int xhe_hist_level_sparse(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const uint16_t* bins_dev,
+                          int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin_dev,
+                          const uint16_t* node_dev, int nnodes, int64_t nnz_bound, const uint32_t* total_dev,
+                          int tile_rows, uint32_t* out_dev, int32_t* cnt_dev, void* stream);
+/* Host only, no device work: 1 when the planner (paths.hpp level_sparse)
+ * expects xhe_hist_level_sparse to beat xhe_hist_level for `nnz` entries
+ * outside the zero bins, with or without totals. */
+int xhe_hist_level_sparse_route(const xhe_key* key, int64_t n_rows, int nnodes, int nfeat, int nbins, int64_t nnz,
+                                int have_total);
+
 /* Encrypted matrix-vector product as a multi-exponentiation: the object-dtype
  * np.matmul(enc[B], X[B, D]) of logistic_regression/trainer.py:166 (and
  * linear_regression/trainer.py:207, poisson_regression/trainer.py:267,
@@ -445,6 +485,12 @@ int xhe_hist_sparse_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, 
 int xhe_hist_level_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
                         int64_t bins_stride, int nfeat, int nbins, const uint16_t* node, int nnodes, int tile_rows,
                         uint32_t* out, int32_t* cnt);
+/* xhe_hist_level_sparse on host buffers (zero_bin and total host memory too); the bound is the exact count, taken
+ * here. Without a sparse feature it is xhe_hist_level_host. */
+int xhe_hist_level_sparse_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                               int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin,
+                               const uint16_t* node, int nnodes, const uint32_t* total, int tile_rows, uint32_t* out,
+                               int32_t* cnt);
 /* xhe_hist_level_sub on host buffers. */
 int xhe_hist_level_sub_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
                             int64_t bins_stride, int nfeat, int nbins, const uint16_t* node, int nnodes,

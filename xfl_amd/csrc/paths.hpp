@@ -401,6 +401,92 @@ inline bool hist_sparse(int64_t count, int nfeat, int nbins, int64_t nnz, bool h
   return direct >= kSparseMinSaving * sparse;
 }
 
+// ------------------------------------------- level-wise sparse histogram
+// xhe_hist_level_sparse (hist_level_sparse_dev.hpp): xhe_hist_sparse with the
+// nnodes x nfeat groups (node, feature) in the features' place. sparse_tile's
+// reasoning holds per group: hist_tile for the mean list length nnz_bound /
+// groups and nbins + 1 internal bins, but not above the power of two at or
+// above that mean (floor kHistTileMin). At deep levels the mean group is a few
+// dozen entries, the tile is the floor and most groups are one short slot: a
+// larger tile would only lengthen the slot's LDS passes over ids it does not
+// have. The slots are at most floor(nnz_bound / tile) + groups, which sizes
+// every grid and workspace.
+// The route's model counts in units of one entry of the dense level call (3.2
+// ns on config 5), with weights fitted to the stage times of the measured
+// tables (DESIGN "Level-wise sparse histogram", JSON in
+// profiles/r29/hist_level_sparse/):
+//   direct   nfeat n_rows + kLevelGroupCost groups nbins
+//   sparse   kLspEntryCost nnz + kLspFoldCost (nbins + 1) slots + 4 groups + kLspFixedCost
+//            + (totals given ? 0 : kLspTotalCost n_rows)
+// - the dense call pays per (node, feature), but how much depends on the data:
+//   with a heavy zero bin it takes 19 ms at 2 nodes, 33 to 40 at 64 and 108 at
+//   256 for the same 6.4 M entries (5 us a group), with uniform bins (d = 1.0)
+//   17 ms at 2 nodes and 23.6 at 64 (1.6 us a group). The model charges the
+//   smaller figure, two entries' time per bin of every group, since the route
+//   does not know the skew;
+// - an entry of a slot costs 1.16 dense entries (the row id list in between);
+// - a partial row per (slot, internal bin) to fold and reduce, 0.9 each (0.6
+//   to 0.8 us a slot at 257 bins), and per group the inversion tree's share and
+//   the two products of the zero bin;
+// - 3 ms that no shape gets under - the order launches, the fold and zero
+//   stages at their smallest, the synchronisation - as 930 k entries;
+// - the totals: 5.2 to 5.8 ms per 100 k rows, seventeen entries a row.
+// The route takes the sparse call when direct >= kLevelSparseMinSaving x
+// sparse. Over the 48 measured points (1 to 256 nodes, d 0.05 to 1.0, with and
+// without totals; ms of xhe_hist_level / xhe_hist_level_sparse) around the
+// crossover:
+//   ratio   nodes  d     totals     dense / sparse ms
+//   0.916   1      0.8   given      18.48 / 20.04   slower
+//   0.918   2      0.8   given      19.85 / 19.87   a tie
+//   0.955   16     0.8   given      25.13 / 19.69   faster, not taken
+//   1.001   2      0.5   computed   20.54 / 20.39   a tie
+//   1.010   64     0.8   given      36.31 / 27.45   faster, not taken
+//   1.024   16     0.5   computed   26.25 / 20.50   faster, not taken
+//   1.059   64     0.5   computed   40.05 / 27.04   faster
+//   1.092   1      0.65  given      18.76 / 15.15   faster
+//   1.095   2      0.65  given      20.23 / 19.37   faster by 4 %
+// Every point the route takes at 1.05 (23 of the 48) was measured faster, by 4
+// % to 4.1 x; no point measured slower or tied has a ratio above 1.001 (full
+// density, d = 1.0, is 0.63 to 0.85 at every node count and 1.3 to 1.8 x
+// slower). The price of charging the dense call its uniform-bins cost is on
+// the other side: between 0.84 and 1.03 five points measured faster by 7 to 32
+// % are left to the dense call (sparse=True takes them). Only config 5's shape
+// and key size were measured; the weights per bin and per slot follow the
+// kernels' structure but were not measured at another nbins. Nothing above 256
+// nodes was measured either: there the model promises the most and the
+// accumulator rows double the call's memory, so the route leaves levels beyond
+// kLevelSparseNodesMeasured to the dense call.
+constexpr double kLevelSparseMinSaving = 1.05;
+constexpr int kLevelSparseNodesMeasured = 256;
+constexpr double kLevelGroupCost = 2.0, kLspEntryCost = 1.16, kLspFoldCost = 0.9, kLspFixedCost = 930000.0,
+                 kLspTotalCost = 17.0;
+
+inline int level_sparse_tile(int64_t nnz_bound, int nnodes, int nfeat, int nbins) {
+  const int64_t groups = (int64_t)(nnodes > 0 ? nnodes : 1) * (nfeat > 0 ? nfeat : 1);
+  const int64_t mean = (nnz_bound + groups - 1) / groups;
+  int tile = hist_tile(mean, (int)(groups < (1 << 30) ? groups : (1 << 30)), nbins + 1);
+  int cap = kHistTileMin;
+  while (cap < kHistTileMax && cap < mean) cap <<= 1;
+  return tile < cap ? tile : cap;
+}
+
+inline int64_t level_sparse_tiles_max(int64_t nnz_bound, int nnodes, int nfeat, int tile_rows) {
+  return nnz_bound / tile_rows + (int64_t)nnodes * nfeat;
+}
+
+inline bool level_sparse(int64_t n_rows, int nnodes, int nfeat, int nbins, int64_t nnz, bool have_total) {
+  if (n_rows < 1 || nnodes < 1 || nnodes > kLevelSparseNodesMeasured || nfeat < 1 || nbins < 1 ||
+      nbins > kSparseBinsMax || nnz < 0 || nnz > (int64_t)nfeat * n_rows)
+    return false;
+  const int tile = level_sparse_tile(nnz, nnodes, nfeat, nbins);
+  const double slots = (double)level_sparse_tiles_max(nnz, nnodes, nfeat, tile);
+  const double groups = (double)nnodes * nfeat;
+  const double direct = (double)nfeat * (double)n_rows + kLevelGroupCost * groups * nbins;
+  const double sparse = kLspEntryCost * (double)nnz + kLspFoldCost * (nbins + 1.0) * slots + 4.0 * groups +
+                        kLspFixedCost + (have_total ? 0.0 : kLspTotalCost * (double)n_rows);
+  return direct >= kLevelSparseMinSaving * sparse;
+}
+
 enum class Horner {
   WAVE,   // 2048, 16 lanes: k_mexp_horner_wave, one 16-wave block per column (latency)
   LANES,  // k_mexp_horner

@@ -35,6 +35,7 @@
 #include "hist_level_dev.hpp"
 #include "hist_sub_dev.hpp"
 #include "hist_sparse_dev.hpp"
+#include "hist_level_sparse_dev.hpp"
 #include "bucket_dev.hpp"
 
 using namespace xhe;
@@ -1663,6 +1664,116 @@ int hist_sparse_impl(const xhe_key* k, const uint32_t* c, int64_t n_rows, const 
   return XHE_OK;
 }
 
+// Level-wise sparse histogram (hist_level_sparse_dev.hpp): hist_sparse_impl
+// with the nnodes * nfeat groups in the features' place. The caller's bound
+// sizes the list, the slot table and every grid; the accumulator rows, one per
+// (group, internal bin), are about the size of `out`. Without totals the
+// per-node products and row counts are hist_level_impl's over one feature with
+// one bin; with them the counts are k_level_count's. The flag is copied back
+// ahead of the inversion and read behind its synchronisation.
+template <class Sh>
+int hist_level_sparse_impl(const xhe_key* k, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                           int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin, const uint16_t* node,
+                           int nnodes, int64_t nnz_bound, const uint32_t* total, int tile_rows, uint32_t* out,
+                           int32_t* cnt, hipStream_t s) {
+  using MN2 = typename Sh::MN2;
+  const int S4 = MN2::S4, nb = nbins + 1;
+  auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
+  if (!tile_rows) tile_rows = paths::level_sparse_tile(nnz_bound, nnodes, nfeat, nbins);
+  const int64_t G = (int64_t)nnodes * nfeat;
+  const int64_t tmax = paths::level_sparse_tiles_max(nnz_bound, nnodes, nfeat, tile_rows);
+  const int64_t gt = std::max<int64_t>(1, std::min<int64_t>(tmax, kChunk / (nb + tile_rows / kHistParkDiv)));
+  const int64_t nacc = G * nb, rblocks = (n_rows + kLspBlockRows - 1) / kLspBlockRows;
+  const int fc = lsp_feat_chunk(nnodes, nfeat);
+  if (nnz_bound > INT32_MAX || n_rows > INT32_MAX || tmax > INT32_MAX || nfeat > 65535 || G > INT32_MAX / 2 ||
+      nacc * MN2::TPI > (int64_t)INT32_MAX * 256 / 2)
+    throw std::logic_error("xhe_hist_level_sparse: problem too large for one call");
+  const size_t lds = (size_t)paths::hist_lds_bytes(tile_rows, nb);
+  const size_t rb = (size_t)k->n2w * 4;
+  ProfScope ps("k_hist_level_sparse", s);
+  // (declared in reverse, filled in allocation order: DevBuf's note)
+  DevBuf inv, qw, acc, tw, list, meta;
+  // nnz[G] | cursor[G] | nzsum[G] | flag | node_cnt[nnodes] | hcnt[nacc] (zeroed) | tile_begin[G + 1] | list_base[G] | tile_node[tmax]
+  const int64_t nzero = 3 * G + 1 + nnodes + nacc;
+  meta = DevBuf((size_t)(nzero + 2 * G + 1 + tmax) * 4, s, DevBuf::kAsync);
+  list = DevBuf((size_t)std::max<int64_t>(nnz_bound, 1) * 4, s, DevBuf::kAsync);
+  if (!total) tw = DevBuf((size_t)nnodes * rb, s, DevBuf::kAsync);
+  acc = DevBuf((size_t)S4 * nacc * 4, s, DevBuf::kAsync);
+  int32_t* nnz = meta.as<int32_t>();
+  int32_t *cursor = nnz + G, *nzsum = cursor + G, *flag = nzsum + G, *node_cnt = flag + 1, *hcnt = node_cnt + nnodes;
+  int32_t *tile_begin = hcnt + nacc, *list_base = tile_begin + G + 1, *tile_node = list_base + G;
+  launch(k_hist_zero, dim3((unsigned)((nzero + 255) / 256)), dim3(256), s, nnz, nzero);
+  {
+    ProfScope po("k_lsp_order", s);
+    const dim3 grid((unsigned)rblocks, (unsigned)((nfeat + fc - 1) / fc));
+    hipLaunchKernelGGL(k_lsp_count, grid, dim3(256), (size_t)nnodes * fc * 4, s, bins, bins_stride, nfeat, nbins,
+                       zero_bin, node, n_rows, nnodes, fc, nnz);
+    HIPCHK(hipGetLastError());
+    launch(k_sparse_plan, dim3(1), dim3(256), s, nnz, (int)G, tile_rows, nnz_bound, tmax, tile_begin, list_base,
+           tile_node, flag);
+    hipLaunchKernelGGL(k_lsp_scatter, grid, dim3(256), (size_t)nnodes * fc * 8, s, bins, bins_stride, nfeat, nbins,
+                       zero_bin, node, n_rows, nnodes, fc, list_base, cursor, flag, list.as<int32_t>());
+    HIPCHK(hipGetLastError());
+  }
+  {
+    ProfScope pt("k_lsp_totals", s);
+    if (!total) {  // T_v and count_v from the rows in place: the level call over one feature with one bin
+      DevBuf zb((size_t)(n_rows + 1) / 2 * 4, s, DevBuf::kAsync);
+      launch(k_hist_zero, dim3((unsigned)(((n_rows + 1) / 2 + 255) / 256)), dim3(256), s, zb.as<int32_t>(),
+             (n_rows + 1) / 2);
+      hist_level_impl<Sh>(k, c, n_rows, n_rows, zb.as<uint16_t>(), n_rows, 1, 1, node, nnodes, 0, tw.as<uint32_t>(),
+                          node_cnt, s, nullptr);
+      total = tw.as<uint32_t>();
+    } else {
+      hipLaunchKernelGGL(k_level_count, dim3((unsigned)((n_rows + kLevelBlockRows - 1) / kLevelBlockRows)), dim3(256),
+                         (size_t)nnodes * 4, s, node, n_rows, nnodes, node_cnt);
+      HIPCHK(hipGetLastError());
+    }
+  }
+  for (int64_t t0 = 0; t0 < tmax; t0 += gt) {
+    const int ng = (int)std::min(gt, tmax - t0);
+    const int ncols = ng * nb;
+    const int passes = paths::level_fold_passes(std::min<int64_t>(n_rows, (int64_t)ng * tile_rows), tile_rows, kRawChunk);
+    DevBuf park, part;
+    part = DevBuf((size_t)S4 * ncols * 4, s, DevBuf::kAsync);
+    park = DevBuf((size_t)ng * (tile_rows / kHistParkDiv) * S4 * 4, s, DevBuf::kAsync);
+    {
+      ProfScope pt("k_lsp_tile", s);
+      hipLaunchKernelGGL((k_lsp_tile<MN2, Sh::RW2>), dim3((unsigned)ng), dim3(256), lds, s, k->kd, n2h<MN2>(k).N, c, bins,
+                         bins_stride, nfeat, nb, list.as<int32_t>(), nnz, tile_begin, list_base, tile_node, tile_rows, t0,
+                         ncols, part.as<uint32_t>(), park.as<uint32_t>(), hcnt);
+      HIPCHK(hipGetLastError());
+    }
+    ProfScope pf("k_lsp_fold", s);
+    for (int p = 0; p < passes; ++p)
+      launch(k_sparse_fold_pass<MN2>, blocks((int64_t)ncols), dim3(256), s, k->kd, n2h<MN2>(k).N, part.as<uint32_t>(),
+             ncols, nb, t0, ng, tile_begin, tile_node, flag, p);
+    launch(k_lsp_acc<MN2>, blocks((int64_t)ncols), dim3(256), s, k->kd, n2h<MN2>(k).N, part.as<uint32_t>(), ncols, nb,
+           nacc, t0, ng, tile_begin, tile_node, passes, acc.as<uint32_t>());
+  }
+  {
+    ProfScope pf("k_lsp_fold", s);
+    launch(k_lsp_out<MN2>, blocks(nacc), dim3(256), s, k->kd, n2h<MN2>(k).N, acc.as<uint32_t>(), G, nfeat, nbins,
+           zero_bin, tile_begin, hcnt, flag, out, cnt, nzsum);
+  }
+  ProfScope pz("k_lsp_zero", s);
+  std::vector<int64_t> seg((size_t)G + 1);
+  for (int64_t i = 0; i <= G; ++i) seg[(size_t)i] = i * nb;
+  const DevBuf q = reduce_segments<Sh, MN2>(k, std::move(acc), nacc, std::move(seg), s);
+  qw = DevBuf((size_t)G * rb, s, DevBuf::kAsync);
+  inv = DevBuf((size_t)G * rb, s, DevBuf::kAsync);
+  launch(k_from_mont_rows<MN2>, blocks(G), dim3(256), s, k->kd, n2h<MN2>(k).N, q.as<uint32_t>(), G, qw.as<uint32_t>());
+  int32_t over = 0;
+  HIPCHK(hipMemcpyAsync(&over, flag, 4, hipMemcpyDeviceToHost, s));
+  // (synchronises the stream: the batch inversion's one scalar inverse is the host's)
+  const int rc = invert_impl<Sh, MN2>(k, qw.as<uint32_t>(), G, inv.as<uint32_t>(), s);
+  if (over) return fail(XHE_EINVAL, "xhe_hist_level_sparse: more entries outside the zero bins than nnz_bound");
+  if (rc != XHE_OK) return rc;
+  launch((k_lsp_zero<MN2, Sh::RW2>), blocks(G), dim3(256), s, k->kd, n2h<MN2>(k).N, inv.as<uint32_t>(), total, G, nfeat,
+         nbins, zero_bin, node_cnt, nzsum, out, cnt);
+  return XHE_OK;
+}
+
 // Bucket multi-exponentiation (bucket_dev.hpp). The columns run in groups
 // whose digit matrix stays within kBucketDigitCap ids (and hist_rows groups
 // the (column, window) features within kChunk rows below that); every group
@@ -2136,6 +2247,49 @@ int xhe_hist_sparse(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, c
 int xhe_hist_sparse_route(const xhe_key* key, int64_t count, int nfeat, int nbins, int64_t nnz, int have_total) {
   (void)key;  // (one constant serves every key size: DESIGN "Sparse-aware histogram")
   return paths::hist_sparse(count, nfeat, nbins, nnz, have_total != 0) ? 1 : 0;
+}
+
+namespace {
+int hist_level_sparse_args(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                           int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin, const uint16_t* node,
+                           int nnodes, int64_t nnz_bound, const uint32_t* total, int tile_rows, const uint32_t* out,
+                           const char* who) {
+  if (int rc = hist_level_args(key, c, n_rows, bins, bins_stride, nfeat, nbins, node, nnodes, tile_rows, out, who))
+    return rc;
+  if (nbins > paths::kSparseBinsMax) return fail(XHE_EINVAL, std::string(who) + ": nbins must be in [1, 4095]");
+  if (!zero_bin || nnz_bound < 0) return fail(XHE_EINVAL, std::string(who) + ": zero bins missing or a negative nnz_bound");
+  if (total && out < total + (size_t)nnodes * key->n2w && total < out + (size_t)nnodes * nfeat * nbins * key->n2w)
+    return fail(XHE_EINVAL, std::string(who) + ": out overlaps total");
+  return XHE_OK;
+}
+}  // namespace
+
+int xhe_hist_level_sparse(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const uint16_t* bins_dev,
+                          int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin_dev,
+                          const uint16_t* node_dev, int nnodes, int64_t nnz_bound, const uint32_t* total_dev,
+                          int tile_rows, uint32_t* out_dev, int32_t* cnt_dev, void* stream) {
+  return guarded([&]() -> int {
+    if (int rc = hist_level_sparse_args(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins, zero_bin_dev, node_dev,
+                                        nnodes, nnz_bound, total_dev, tile_rows, out_dev, "xhe_hist_level_sparse"))
+      return rc;
+    DevGuard dg(key->device);
+    return with_shape(key->K, [&](auto sh) -> int {
+      if (n_rows == 0) {  // ones and zero counts, as xhe_hist_level writes them
+        hist_level_impl<decltype(sh)>(key, c_dev, n_rows, n_rows, bins_dev, bins_stride, nfeat, nbins, node_dev, nnodes,
+                                      tile_rows, out_dev, cnt_dev, (hipStream_t)stream, "k_hist_level_sparse");
+        return XHE_OK;
+      }
+      return hist_level_sparse_impl<decltype(sh)>(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins, zero_bin_dev,
+                                                  node_dev, nnodes, nnz_bound, total_dev, tile_rows, out_dev, cnt_dev,
+                                                  (hipStream_t)stream);
+    });
+  });
+}
+
+int xhe_hist_level_sparse_route(const xhe_key* key, int64_t n_rows, int nnodes, int nfeat, int nbins, int64_t nnz,
+                                int have_total) {
+  (void)key;  // (one constant serves every key size: DESIGN "Level-wise sparse histogram")
+  return paths::level_sparse(n_rows, nnodes, nfeat, nbins, nnz, have_total != 0) ? 1 : 0;
 }
 
 namespace {
@@ -3239,6 +3393,55 @@ int xhe_hist_level_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, c
     int rc = xhe_hist_level(key, dc.as<uint32_t>(), n_rows, db.as<uint16_t>(), bins_stride, nfeat, nbins,
                             dn.as<uint16_t>(), nnodes, tile_rows, dout.as<uint32_t>(),
                             cnt ? dcnt.as<int32_t>() : nullptr, st.s);
+    if (rc != XHE_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
+    if (cnt) HIPCHK(hipMemcpyAsync(cnt, dcnt.p, nn * 4, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    return XHE_OK;
+  });
+}
+
+int xhe_hist_level_sparse_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                               int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin,
+                               const uint16_t* node, int nnodes, const uint32_t* total, int tile_rows, uint32_t* out,
+                               int32_t* cnt) {
+  return guarded([&]() -> int {
+    if (int rc = hist_level_sparse_args(key, c, n_rows, bins, bins_stride, nfeat, nbins, zero_bin, node, nnodes, 0,
+                                        total, tile_rows, out, "xhe_hist_level_sparse_host"))
+      return rc;
+    // the bound is the exact count here; without a sparse feature the dense call serves (no inversion, no wait in it)
+    int64_t nnz = 0, valid = 0;
+    bool any = false;
+    for (int64_t i = 0; i < n_rows; ++i) valid += node[i] < nnodes;
+    for (int f = 0; f < nfeat; ++f) {
+      const uint16_t z = zero_bin[f];
+      if (z >= nbins) {
+        nnz += valid;
+        continue;
+      }
+      any = true;
+      const uint16_t* fb = bins + (size_t)f * bins_stride;
+      for (int64_t i = 0; i < n_rows; ++i) nnz += node[i] < nnodes && fb[i] != z;
+    }
+    if (!any)
+      return xhe_hist_level_host(key, c, n_rows, bins, bins_stride, nfeat, nbins, node, nnodes, tile_rows, out, cnt);
+    DevGuard dg(key->device);
+    Stream st;
+    const size_t cb = (size_t)n_rows * key->n2w * 4, bb = ((size_t)(nfeat - 1) * bins_stride + n_rows) * 2,
+                 nn = (size_t)nnodes * nfeat * nbins, ob = nn * key->n2w * 4, tb = (size_t)nnodes * key->n2w * 4;
+    DevBuf dc(cb, st.s), db(bb, st.s), dz((size_t)nfeat * 2, st.s), dn((size_t)n_rows * 2, st.s),
+        dt(total ? tb : 0, st.s), dout(ob, st.s), dcnt(nn * 4, st.s);
+    if (n_rows > 0) {
+      HIPCHK(hipMemcpyAsync(dc.p, c, cb, hipMemcpyHostToDevice, st.s));
+      HIPCHK(hipMemcpyAsync(db.p, bins, bb, hipMemcpyHostToDevice, st.s));
+      HIPCHK(hipMemcpyAsync(dn.p, node, (size_t)n_rows * 2, hipMemcpyHostToDevice, st.s));
+    }
+    HIPCHK(hipMemcpyAsync(dz.p, zero_bin, (size_t)nfeat * 2, hipMemcpyHostToDevice, st.s));
+    if (total) HIPCHK(hipMemcpyAsync(dt.p, total, tb, hipMemcpyHostToDevice, st.s));
+    int rc = xhe_hist_level_sparse(key, dc.as<uint32_t>(), n_rows, db.as<uint16_t>(), bins_stride, nfeat, nbins,
+                                   dz.as<uint16_t>(), dn.as<uint16_t>(), nnodes, nnz,
+                                   total ? dt.as<uint32_t>() : nullptr, tile_rows, dout.as<uint32_t>(),
+                                   cnt ? dcnt.as<int32_t>() : nullptr, st.s);
     if (rc != XHE_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
     if (cnt) HIPCHK(hipMemcpyAsync(cnt, dcnt.p, nn * 4, hipMemcpyDeviceToHost, st.s));

@@ -429,7 +429,18 @@ def _level_subtracts(ctx, dev, parent, subtract, n_rows, shape, e0):
     return True if subtract else ops.hist_level_sub_route(ctx, dev, n_rows, nnodes, nfeat, nbins)
 
 
-def level_histograms(arr, bins, nodes, nnodes: int = None, nbins: int = None, parent=None, subtract: bool = None):
+def _total_rows(ctx, total, nnodes, e0, n2w):
+    """the [nnodes, n2w] host words of `total` (a PaillierArray of nnodes ciphertexts) at exponent e0"""
+    from .paillier.array import PaillierArray
+    if not isinstance(total, PaillierArray) or total.size != nnodes or total._has_na():
+        raise ValueError("level_histograms: total must be a PaillierArray of nnodes ciphertexts")
+    if int(total.exponents.min()) != e0 or int(total.exponents.max()) != e0:
+        raise ValueError("level_histograms: total must be at the column's exponent")
+    return np.array(total.reshape(-1)._aligned_words(n2w).words, dtype=np.uint32).reshape(nnodes, n2w)
+
+
+def level_histograms(arr, bins, nodes, nnodes: int = None, nbins: int = None, parent=None, subtract: bool = None,
+                     default_bin=None, total=None, sparse: bool = None):
     """histograms() for every node of a tree level in ONE device call
     (xhe_hist_level): what a level-wise trainer's loop of
     histograms(arr, bins, rows=<the node's samples>) over the level's nodes
@@ -452,6 +463,17 @@ def level_histograms(arr, bins, nodes, nnodes: int = None, nbins: int = None, pa
     column, an even nnodes and a parent of shape (nnodes / 2, nfeat, nbins) at
     the column's exponent; in every other case the direct call runs. It
     synchronises the stream once.
+
+    default_bin, sparse: as histograms - the rows in a feature's default bin
+    are not multiplied; per node the bin is what is left of the node's product
+    (xhe_hist_level_sparse), the same ciphertexts bit for bit. total: those
+    per-node products, a PaillierArray of nnodes ciphertexts at the column's
+    exponent (the level above has them in any feature's bins), else they are
+    computed. sparse=None asks the planner with the entries outside the default
+    bins counted from `bins`. Where the subtraction is taken the call stays on
+    it: the two are not combined. More than 4095 bins keep the dense path.
+    Raises ZeroDivisionError when a product that has to be inverted is no unit
+    mod n^2 (never for ciphertexts of this key).
 
     The device path serves one exponent, nbins <= 4096 and nnodes <= 4096;
     anything else is the loop of histograms(rows=...) per node."""
@@ -505,11 +527,29 @@ def level_histograms(arr, bins, nodes, nnodes: int = None, nbins: int = None, pa
         n16 = np.where(nd < 0, 0xFFFF, nd).astype(np.uint16)
         exps = np.full(nnodes * nfeat * nbins, e0, dtype=np.int32)
         dev = resident.device_for(ctx, -1, x.size, 4 * n2w)
+        subtracts = dev is not None and _level_subtracts(ctx, dev, parent, subtract, arr.size, shape, e0)
+        zb = None
+        if sparse is not False and nbins <= 4095 and arr.size and not subtracts:
+            zb = _zero_bins(default_bin, nfeat, nbins)
+        if zb is not None:
+            live = b16[:, n16 != 0xFFFF]
+            nnz = int(((live != zb[:, None]) | (zb[:, None] == 0xFFFF)).sum())
+            if not sparse and not ops.hist_level_sparse_route(ctx, ctx.own_device() if dev is None else dev, arr.size,
+                                                              nnodes, nfeat, nbins, nnz, total is not None):
+                zb = None
+        tw = _total_rows(ctx, total, nnodes, e0, n2w) if zb is not None and total is not None else None
         if dev is None:
-            w, cnt = ops.hist_level_words(ctx, x.words, b16, nbins, n16, nnodes)
+            if zb is not None:
+                w, cnt = ops.hist_level_sparse_words(ctx, x.words, b16, nbins, n16, nnodes, zb, tw)
+            else:
+                w, cnt = ops.hist_level_words(ctx, x.words, b16, nbins, n16, nnodes)
             return _result(ctx, w, exps, shape), cnt.astype(np.int64).reshape(shape)
         bd, ndv = resident.upload(b16.view(np.int16), dev), resident.upload(n16.view(np.int16), dev)
-        if _level_subtracts(ctx, dev, parent, subtract, arr.size, shape, e0):
+        if zb is not None:
+            out, cnt = resident.hist_level_sparse(ctx.device_key(dev), x._dw(dev), bd, nbins, ndv, nnodes,
+                                                  resident.upload_async(zb.view(np.int16), dev), nnz,
+                                                  None if tw is None else resident.upload_async(tw, dev))
+        elif subtracts:
             out, cnt = resident.hist_level_sub(ctx.device_key(dev), x._dw(dev), bd, nbins, ndv, nnodes,
                                                parent[0]._dw(dev),
                                                resident.upload(np.ascontiguousarray(parent[1], np.int32).reshape(-1),
