@@ -11,11 +11,12 @@
  * gives the thread-local message. A key handle is immutable after creation
  * and may be shared between threads; calls on distinct streams are reentrant.
  *
- * Ciphertext operands: the fourteen entry points that read ciphertext words -
+ * Ciphertext operands: the fifteen entry points that read ciphertext words -
  * xhe_decrypt, xhe_mulmod, xhe_powmod, xhe_pack, xhe_invert, xhe_segprod,
  * xhe_segscan, xhe_hist, xhe_hist_level, xhe_hist_level_sub (its rows and its
  * parent rows), xhe_hist_sparse (its rows and its total),
- * xhe_hist_level_sparse (its rows and its totals), xhe_multiexp and
+ * xhe_hist_level_sparse (its rows and its totals), xhe_hist_level_sub_sparse
+ * (its rows, its parent rows and its totals), xhe_multiexp and
  * xhe_bucketexp (and their _host variants) -
  * accept ANY value in
  * [0, 2^(32 n2w))
@@ -381,6 +382,64 @@ int xhe_hist_level_sparse(const xhe_key* key, const uint32_t* c_dev, int64_t n_r
 int xhe_hist_level_sparse_route(const xhe_key* key, int64_t n_rows, int nnodes, int nfeat, int nbins, int64_t nnz,
                                 int have_total);
 
+/* Subtraction on the sparse level histogram: the result of xhe_hist_level,
+ * words and counts bit for bit, with both savings - of every pair of slots 2v,
+ * 2v + 1 only the child with fewer rows is built (a tie builds the left one,
+ * as in xhe_hist_level_sub), and of it only the entries outside the features'
+ * zero bins are multiplied (as in xhe_hist_level_sparse). c, bins, bins_stride,
+ * nfeat, node, nnodes (even), parent, parent_cnt, tile_rows, out, cnt: as
+ * xhe_hist_level_sub, with its precondition on the parent; zero_bin_dev,
+ * nnz_bound, total_dev: as xhe_hist_level_sparse; nbins in [1, 4095].
+ * With z = zero_bin[f] < nbins, T the built child's product, Q the product of
+ * the built child's entries of feature f outside bin z (those with an id >=
+ * nbins included):
+ *   built child    b != z: the product of its entries    z: T * Q^-1
+ *   its sibling    b != z: parent * built^-1             z: parent[z] * Q * T^-1
+ *   counts         built: the entries; z: count_v - those outside z;
+ *                  sibling: parent_cnt - built
+ * all mod n^2. Where the built child has no entry in a bin b != z the sibling
+ * is parent mod n^2 and nothing is inverted for it. A feature with a zero bin
+ * >= nbins is dense: every bin of it is an ordinary bin. A pair without a row
+ * gets ones and zero counts in both slots.
+ * total_dev: nnodes ciphertext rows (any values below 2^(32 n2w)), row v
+ * congruent to the product of slot v's rows, trusted; only the built
+ * children's rows are read. NULL: computed here, for the built children only
+ * (at most n_rows / 2 products).
+ * nnz_bound: xhe_hist_level_sparse's - the entries outside the zero bins over
+ * all rows with a node id < nnodes - hence an upper bound for the built half.
+ * It is not trusted: the device compares the built children's real count with
+ * it, and past it no kernel of the call stores outside the call's buffers and
+ * the call returns XHE_EINVAL (out and cnt are then undefined).
+ * Everything that is inverted - the non-empty built cells outside the zero
+ * bins, the nnodes / 2 * nfeat products Q and the nnodes / 2 totals T - goes
+ * through ONE batch inversion: one host inverse, one synchronisation of
+ * `stream`; the backward pass and the zero bins are enqueued behind it.
+ * XHE_ENOINV when any of them is no unit mod n^2 (out and cnt are then
+ * unspecified). This is xhe_hist_level_sub's rule, not
+ * xhe_hist_level_sparse's: an operand row that is no unit fails the call
+ * wherever it lies in a BUILT child, its zero bins included (T holds it); one
+ * in the larger child of its pair is never inverted and the result is exact.
+ * XHE_EINVAL: whatever xhe_hist_level_sub or xhe_hist_level_sparse rejects
+ * (out overlapping c, parent or total included). n_rows == 0 writes ones and
+ * zero counts. Every output is below n^2. Timed as "k_hist_level_sub_sparse"
+ * under xhe_profile (its stages as "k_sub_pick", "k_lsp_order",
+ * "k_sss_totals", "k_lsp_tile", "k_lsp_fold", "k_sss_mark", "k_sss_fill",
+ * "k_sss_fwd", "k_sss_bwd", "k_sss_zero"). */
+int xhe_hist_level_sub_sparse(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const uint16_t* bins_dev,
+                              int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin_dev,
+                              const uint16_t* node_dev, int nnodes, const uint32_t* parent_dev,
+                              const int32_t* parent_cnt_dev, int64_t nnz_bound, const uint32_t* total_dev,
+                              int tile_rows, uint32_t* out_dev, int32_t* cnt_dev, void* stream);
+/* Host only, no device work: 1 when the planner (paths.hpp level_sub_sparse)
+ * expects xhe_hist_level_sub_sparse to beat both xhe_hist_level_sparse and
+ * xhe_hist_level_sub for `nnz` entries outside the zero bins, with or without
+ * totals. The model is fitted to measurements on 2 to 64 nodes with 5 % to 80 %
+ * of the entries outside the zero bins and answers 1 only inside that range, on
+ * the points measured faster than both by a margin; always 0 for an odd nnodes,
+ * fewer than 2 or more than 64 nodes. */
+int xhe_hist_level_sub_sparse_route(const xhe_key* key, int64_t n_rows, int nnodes, int nfeat, int nbins, int64_t nnz,
+                                    int have_total);
+
 /* Encrypted matrix-vector product as a multi-exponentiation: the object-dtype
  * np.matmul(enc[B], X[B, D]) of logistic_regression/trainer.py:166 (and
  * linear_regression/trainer.py:207, poisson_regression/trainer.py:267,
@@ -496,6 +555,12 @@ int xhe_hist_level_sub_host(const xhe_key* key, const uint32_t* c, int64_t n_row
                             int64_t bins_stride, int nfeat, int nbins, const uint16_t* node, int nnodes,
                             const uint32_t* parent, const int32_t* parent_cnt, int tile_rows, uint32_t* out,
                             int32_t* cnt);
+/* xhe_hist_level_sub_sparse on host buffers (zero_bin, parent and total host memory too); the bound is the exact
+ * count, taken here. Without a sparse feature it is xhe_hist_level_sub_host. */
+int xhe_hist_level_sub_sparse_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                                   int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin,
+                                   const uint16_t* node, int nnodes, const uint32_t* parent, const int32_t* parent_cnt,
+                                   const uint32_t* total, int tile_rows, uint32_t* out, int32_t* cnt);
 /* xhe_pack: count ciphertexts in, ceil(count/k) out. */
 int xhe_pack_host(const xhe_key* key, const uint32_t* c, int64_t count, int k, int shift_bits, uint32_t* out);
 int xhe_mulmod_host(const xhe_key* key, const uint32_t* a, const int32_t* ea, const uint32_t* b, const int32_t* eb,

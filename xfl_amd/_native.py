@@ -89,6 +89,14 @@ SIGNATURES = {
                                                   ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, ctypes.c_int, _vp, _vp]),
     "xhe_hist_level_sparse_route": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
                                                    ctypes.c_int64, ctypes.c_int]),
+    "xhe_hist_level_sub_sparse": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int,
+                                                 ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, ctypes.c_int64, _vp,
+                                                 ctypes.c_int, _vp, _vp, _vp]),
+    "xhe_hist_level_sub_sparse_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int,
+                                                      ctypes.c_int, _vp, _vp, ctypes.c_int, _vp, _vp, _vp,
+                                                      ctypes.c_int, _vp, _vp]),
+    "xhe_hist_level_sub_sparse_route": (ctypes.c_int, [_vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, ctypes.c_int,
+                                                       ctypes.c_int64, ctypes.c_int]),
     "xhe_gather_rows": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp]),
     "xhe_scatter_rows": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp]),
     "xhe_multiexp": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, _vp, ctypes.c_int, ctypes.c_int, ctypes.c_int64,

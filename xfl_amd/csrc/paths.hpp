@@ -487,6 +487,82 @@ inline bool level_sparse(int64_t n_rows, int nnodes, int nfeat, int nbins, int64
   return direct >= kLevelSparseMinSaving * sparse;
 }
 
+// ------------------------------- subtraction on the sparse level histogram
+// xhe_hist_level_sub_sparse (hist_sub_sparse_dev.hpp): the smaller child of
+// every pair, and of it only the entries outside the zero bins. The build is
+// the level-sparse call's on npairs = nnodes / 2 nodes; its tile and slot bound
+// take the caller's whole nnz_bound (the device checks the built half against
+// it: the host does not know the split), so
+//   tile   level_sparse_tile(nnz_bound, npairs, ...)
+//   slots  level_sparse_tiles_max(nnz_bound, npairs, ...)
+// The inversion list holds the built cells with an entry outside their zero bin
+// - no more than there are cells, M = npairs nfeat nbins, nor than entries -
+// then one Q per group and one T per pair: sub_sparse_list bounds it and sizes
+// the chains' grids, the parked prefixes and the chunk totals.
+inline int64_t sub_sparse_list(int64_t M, int64_t nnz_bound, int64_t groups, int npairs) {
+  return (nnz_bound < M ? nnz_bound : M) + groups + npairs;
+}
+
+// The route, in level_sparse's units (one entry of the dense level call, 3.2
+// ns on config 5): three linear costs fitted by least squares to the measured
+// table (DESIGN "Subtraction on the sparse level histogram",
+// profiles/r30/hist_level_sub_sparse/: config 5 at 2, 16 and 64 uniformly
+// drawn nodes, d = 0.05 .. 0.8 of the entries outside the zero bins, with and
+// without totals). groups = nnodes nfeat, M = (nnodes / 2) nfeat nbins cells:
+//   sparse    kSssSparseFixed + kSssSparseEntry nnz + kSssSparseGroup groups
+//             + (totals given ? 0 : kSssSparseTotal n_rows)
+//   sub       nfeat n_rows / 2 + kSssSubFixed + kSssSubEntry nnz + kSssSubCell M
+//   combined  kSssFixed + kSssEntry nnz / 2 + kSssCell M + kSssListed min(nnz / 2, M)
+//             + (totals given ? 0 : kSssTotal n_rows / 2)
+// The planner does not know the split and takes the balanced one, as level_sub
+// does. A listed cell costs 3.5 entries on top of the 2.6 every cell costs (the
+// mark, the fill or the four chain products); the built children's totals cost
+// what all the nodes' totals cost (hist_level_impl walks every row's node id).
+// The fit is within 2.3 ms of every measured call, which is more than the 0.5 to
+// 1.5 ms by which the combined call beats the sparse one at 64 nodes, so the
+// route keeps margins: the combined call runs when the sparse call costs at
+// least kSubSparseOverSparse and the subtraction at least kSubSparseOverSub
+// times as much. The second margin is the skewed split's: with 10 % of every
+// pair's rows in the built child the subtraction gains more than the combined
+// call, and the measured sub / combined ratio fell from 1.05 to 0.82 (2 nodes, d
+// = 0.8, totals given: the one point where the split turned a win into a loss)
+// and from 1.39 to 1.12 at d = 0.5. At these margins the route takes five of
+// the 24 measured (nodes, d, totals) points - 2 nodes at d = 0.2 and 0.5 and 16
+// nodes at d = 0.5 with totals given, 64 nodes at d = 0.05 with and without -
+// each measured faster than both others by 5 to 28 % in the uniform and in the
+// skewed table; it takes no point measured slower in either, and leaves the
+// other winners to subtract=True with sparse=True. It answers 1 only inside
+// the measured range: an even nnodes of 2 .. kSubSparseNodesMeasured and
+// kSubSparseDensityMin <= nnz / (nfeat n_rows) <= kSubSparseDensityMax. Only
+// config 5's shape and key size were measured.
+constexpr double kSssSparseFixed = 1114000.0, kSssSparseEntry = 0.958, kSssSparseGroup = 601.0, kSssSparseTotal = 17.0;
+constexpr double kSssSubFixed = 1042000.0, kSssSubEntry = 0.132, kSssSubCell = 8.65;
+constexpr double kSssFixed = 1223000.0, kSssEntry = 1.208, kSssCell = 2.566, kSssListed = 3.469, kSssTotal = 33.7;
+constexpr double kSubSparseOverSparse = 1.10, kSubSparseOverSub = 1.40;
+constexpr int kSubSparseNodesMeasured = 64;
+constexpr double kSubSparseDensityMin = 0.05, kSubSparseDensityMax = 0.8;
+
+// The combined call's cost above (an even nnodes)
+inline double level_sub_sparse_cost(int64_t n_rows, int nnodes, int nfeat, int nbins, int64_t nnz, bool have_total) {
+  const double half = 0.5 * (double)nnz, M = 0.5 * (double)nnodes * nfeat * nbins;
+  return kSssFixed + kSssEntry * half + kSssCell * M + kSssListed * (half < M ? half : M) +
+         (have_total ? 0.0 : kSssTotal * 0.5 * (double)n_rows);
+}
+
+inline bool level_sub_sparse(int64_t n_rows, int nnodes, int nfeat, int nbins, int64_t nnz, bool have_total) {
+  if (n_rows < 1 || nnodes < 2 || (nnodes & 1) || nnodes > kSubSparseNodesMeasured || nfeat < 1 || nbins < 1 ||
+      nbins > kSparseBinsMax || nnz < 0)
+    return false;
+  const double entries = (double)nfeat * (double)n_rows;
+  if ((double)nnz < kSubSparseDensityMin * entries || (double)nnz > kSubSparseDensityMax * entries) return false;
+  const double groups = (double)nnodes * nfeat, M = 0.5 * groups * nbins;
+  const double combined = level_sub_sparse_cost(n_rows, nnodes, nfeat, nbins, nnz, have_total);
+  const double sparse = kSssSparseFixed + kSssSparseEntry * (double)nnz + kSssSparseGroup * groups +
+                        (have_total ? 0.0 : kSssSparseTotal * (double)n_rows);
+  const double sub = 0.5 * entries + kSssSubFixed + kSssSubEntry * (double)nnz + kSssSubCell * M;
+  return sparse >= kSubSparseOverSparse * combined && sub >= kSubSparseOverSub * combined;
+}
+
 enum class Horner {
   WAVE,   // 2048, 16 lanes: k_mexp_horner_wave, one 16-wave block per column (latency)
   LANES,  // k_mexp_horner

@@ -36,6 +36,7 @@
 #include "hist_sub_dev.hpp"
 #include "hist_sparse_dev.hpp"
 #include "hist_level_sparse_dev.hpp"
+#include "hist_sub_sparse_dev.hpp"
 #include "bucket_dev.hpp"
 
 using namespace xhe;
@@ -1774,6 +1775,157 @@ int hist_level_sparse_impl(const xhe_key* k, const uint32_t* c, int64_t n_rows, 
   return XHE_OK;
 }
 
+// Subtraction on the sparse level histogram (hist_sub_sparse_dev.hpp):
+// hist_level_sub_impl's pick, then hist_level_sparse_impl's order, tile, fold
+// and out stages on the remapped ids with the npairs pairs as nodes - the built
+// cells land as words in a workspace, their counts stay in hcnt - and the
+// sparse sibling stage: mark, fill, one forward and one backward chain pass
+// over the inversion list around invert_impl, the zero bins behind it. The
+// list's length stays on the device; paths::sub_sparse_list bounds it for the
+// grids, the parked prefixes and the chunk totals. The flag is copied back
+// ahead of the inversion and read behind its synchronisation.
+template <class Sh>
+int hist_level_sub_sparse_impl(const xhe_key* k, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                               int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin,
+                               const uint16_t* node, int nnodes, const uint32_t* parent, const int32_t* parent_cnt,
+                               int64_t nnz_bound, const uint32_t* total, int tile_rows, uint32_t* out, int32_t* cnt,
+                               hipStream_t s) {
+  using MN2 = typename Sh::MN2;
+  constexpr int PW = Sh::RW2;
+  const int S4 = MN2::S4, nb = nbins + 1, npairs = nnodes / 2;
+  auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
+  if (!tile_rows) tile_rows = paths::level_sparse_tile(nnz_bound, npairs, nfeat, nbins);
+  const int64_t G = (int64_t)npairs * nfeat, FB = (int64_t)nfeat * nbins, M = npairs * FB;
+  const int64_t tmax = paths::level_sparse_tiles_max(nnz_bound, npairs, nfeat, tile_rows);
+  const int64_t gt = std::max<int64_t>(1, std::min<int64_t>(tmax, kChunk / (nb + tile_rows / kHistParkDiv)));
+  const int64_t nacc = G * nb, rblocks = (n_rows + kLspBlockRows - 1) / kLspBlockRows;
+  const int fc = lsp_feat_chunk(npairs, nfeat);
+  const int64_t cap = std::max<int64_t>(1, std::min(M, nnz_bound)), lmax = paths::sub_sparse_list(M, nnz_bound, G, npairs);
+  const int C = paths::sib_chunk(lmax);
+  const int64_t nchunks = (lmax + C - 1) / C;
+  if (nnz_bound > INT32_MAX || n_rows > INT32_MAX || tmax > INT32_MAX || nfeat > 65535 || G > INT32_MAX / 2 ||
+      M > INT32_MAX / 2 || lmax > INT32_MAX || nacc * MN2::TPI > (int64_t)INT32_MAX * 256 / 2 ||
+      M * MN2::TPI > (int64_t)INT32_MAX * 256 / 2)
+    throw std::logic_error("xhe_hist_level_sub_sparse: problem too large for one call");
+  const size_t lds = (size_t)paths::hist_lds_bytes(tile_rows, nb);
+  const size_t rb = (size_t)k->n2w * 4;
+  ProfScope ps("k_hist_level_sub_sparse", s);
+  // (declared in reverse, filled in allocation order: DevBuf's note)
+  DevBuf inv, tot, pre, sinv, qw, cells, built, acc, tw, list, remap, meta;
+  // nnz[G] | cursor[G] | nzsum[G] | flag | ncell | node_cnt[nnodes] | hcnt[nacc] (zeroed) | tile_begin[G + 1] |
+  // list_base[G] | tile_node[tmax] | pick[npairs]
+  const int64_t nzero = 3 * G + 2 + nnodes + nacc;
+  meta = DevBuf((size_t)(nzero + 2 * G + 1 + tmax + npairs) * 4, s, DevBuf::kAsync);
+  remap = DevBuf((size_t)n_rows * 2, s, DevBuf::kAsync);
+  list = DevBuf((size_t)std::max<int64_t>(nnz_bound, 1) * 4, s, DevBuf::kAsync);
+  tw = DevBuf((size_t)(npairs + 1) * rb, s, DevBuf::kAsync);  // T per pair where the caller has none | the one
+  acc = DevBuf((size_t)S4 * nacc * 4, s, DevBuf::kAsync);
+  built = DevBuf((size_t)M * rb, s, DevBuf::kAsync);
+  cells = DevBuf((size_t)cap * 4, s, DevBuf::kAsync);
+  int32_t* nnz = meta.as<int32_t>();
+  int32_t *cursor = nnz + G, *nzsum = cursor + G, *flag = nzsum + G, *ncell = flag + 1, *node_cnt = ncell + 1;
+  int32_t *hcnt = node_cnt + nnodes, *tile_begin = hcnt + nacc, *list_base = tile_begin + G + 1;
+  int32_t* tile_node = list_base + G;
+  uint32_t* pick = reinterpret_cast<uint32_t*>(tile_node + tmax);
+  uint32_t* one = tw.as<uint32_t>() + (size_t)npairs * PW;
+  launch(k_hist_zero, dim3((unsigned)((nzero + 255) / 256)), dim3(256), s, nnz, nzero);
+  {
+    ProfScope pp("k_sub_pick", s);
+    hipLaunchKernelGGL(k_level_count, dim3((unsigned)((n_rows + kLevelBlockRows - 1) / kLevelBlockRows)), dim3(256),
+                       (size_t)nnodes * 4, s, node, n_rows, nnodes, node_cnt);
+    HIPCHK(hipGetLastError());
+    launch(k_sub_pick, dim3((unsigned)((std::max<int64_t>(n_rows, npairs) + 255) / 256)), dim3(256), s, node, n_rows,
+           nnodes, node_cnt, remap.as<uint16_t>(), pick);
+  }
+  {
+    ProfScope po("k_lsp_order", s);
+    const dim3 grid((unsigned)rblocks, (unsigned)((nfeat + fc - 1) / fc));
+    hipLaunchKernelGGL(k_lsp_count, grid, dim3(256), (size_t)npairs * fc * 4, s, bins, bins_stride, nfeat, nbins,
+                       zero_bin, remap.as<uint16_t>(), n_rows, npairs, fc, nnz);
+    HIPCHK(hipGetLastError());
+    launch(k_sparse_plan, dim3(1), dim3(256), s, nnz, (int)G, tile_rows, nnz_bound, tmax, tile_begin, list_base,
+           tile_node, flag);
+    hipLaunchKernelGGL(k_lsp_scatter, grid, dim3(256), (size_t)npairs * fc * 8, s, bins, bins_stride, nfeat, nbins,
+                       zero_bin, remap.as<uint16_t>(), n_rows, npairs, fc, list_base, cursor, flag, list.as<int32_t>());
+    HIPCHK(hipGetLastError());
+  }
+  if (!total) {  // T of the built children only: the level call over one feature with one bin on the remapped ids
+    ProfScope pt("k_sss_totals", s);
+    DevBuf zb((size_t)(n_rows + 1) / 2 * 4, s, DevBuf::kAsync);
+    launch(k_hist_zero, dim3((unsigned)(((n_rows + 1) / 2 + 255) / 256)), dim3(256), s, zb.as<int32_t>(),
+           (n_rows + 1) / 2);
+    hist_level_impl<Sh>(k, c, n_rows, n_rows / 2, zb.as<uint16_t>(), n_rows, 1, 1, remap.as<uint16_t>(), npairs, 0,
+                        tw.as<uint32_t>(), nullptr, s, nullptr);
+  }
+  for (int64_t t0 = 0; t0 < tmax; t0 += gt) {
+    const int ng = (int)std::min(gt, tmax - t0);
+    const int ncols = ng * nb;
+    const int passes = paths::level_fold_passes(std::min<int64_t>(n_rows, (int64_t)ng * tile_rows), tile_rows, kRawChunk);
+    DevBuf park, part;
+    part = DevBuf((size_t)S4 * ncols * 4, s, DevBuf::kAsync);
+    park = DevBuf((size_t)ng * (tile_rows / kHistParkDiv) * S4 * 4, s, DevBuf::kAsync);
+    {
+      ProfScope pt("k_lsp_tile", s);
+      hipLaunchKernelGGL((k_lsp_tile<MN2, PW>), dim3((unsigned)ng), dim3(256), lds, s, k->kd, n2h<MN2>(k).N, c, bins,
+                         bins_stride, nfeat, nb, list.as<int32_t>(), nnz, tile_begin, list_base, tile_node, tile_rows, t0,
+                         ncols, part.as<uint32_t>(), park.as<uint32_t>(), hcnt);
+      HIPCHK(hipGetLastError());
+    }
+    ProfScope pf("k_lsp_fold", s);
+    for (int p = 0; p < passes; ++p)
+      launch(k_sparse_fold_pass<MN2>, blocks((int64_t)ncols), dim3(256), s, k->kd, n2h<MN2>(k).N, part.as<uint32_t>(),
+             ncols, nb, t0, ng, tile_begin, tile_node, flag, p);
+    launch(k_lsp_acc<MN2>, blocks((int64_t)ncols), dim3(256), s, k->kd, n2h<MN2>(k).N, part.as<uint32_t>(), ncols, nb,
+           nacc, t0, ng, tile_begin, tile_node, passes, acc.as<uint32_t>());
+  }
+  {
+    ProfScope pf("k_lsp_fold", s);
+    launch(k_lsp_out<MN2>, blocks(nacc), dim3(256), s, k->kd, n2h<MN2>(k).N, acc.as<uint32_t>(), G, nfeat, nbins,
+           zero_bin, tile_begin, hcnt, flag, built.as<uint32_t>(), nullptr, nzsum);
+  }
+  {
+    ProfScope pm("k_sss_mark", s);
+    launch(k_sss_mark, dim3((unsigned)((M + 255) / 256)), dim3(256), s, hcnt, zero_bin, nfeat, nbins, M, cap,
+           cells.as<int32_t>(), ncell, one, PW);
+  }
+  {
+    ProfScope pl("k_sss_fill", s);
+    launch((k_sss_fill<MN2, PW>), blocks(M), dim3(256), s, k->kd, n2h<MN2>(k).N, hcnt, flag, zero_bin, nfeat, nbins, M,
+           FB, parent, parent_cnt, pick, out, cnt);
+  }
+  std::vector<int64_t> seg((size_t)G + 1);
+  for (int64_t i = 0; i <= G; ++i) seg[(size_t)i] = i * nb;
+  const DevBuf q = reduce_segments<Sh, MN2>(k, std::move(acc), nacc, std::move(seg), s);
+  qw = DevBuf((size_t)G * rb, s, DevBuf::kAsync);
+  sinv = DevBuf((size_t)(G + npairs) * rb, s, DevBuf::kAsync);
+  pre = DevBuf((size_t)S4 * lmax * 4, s, DevBuf::kAsync);
+  tot = DevBuf((size_t)nchunks * rb, s, DevBuf::kAsync);
+  inv = DevBuf((size_t)nchunks * rb, s, DevBuf::kAsync);
+  launch(k_from_mont_rows<MN2>, blocks(G), dim3(256), s, k->kd, n2h<MN2>(k).N, q.as<uint32_t>(), G, qw.as<uint32_t>());
+  const SssList L{cells.as<int32_t>(), ncell, cap, G, npairs, total ? 1 : 0, built.as<uint32_t>(), qw.as<uint32_t>(),
+                  total ? total : tw.as<uint32_t>(), pick};
+  {
+    ProfScope pf("k_sss_fwd", s);
+    launch((k_sss_fwd<MN2, PW>), blocks(nchunks), dim3(256), s, k->kd, n2h<MN2>(k).N, L, nchunks, (int)lmax,
+           pre.as<uint32_t>(), tot.as<uint32_t>());
+  }
+  int32_t over = 0;
+  HIPCHK(hipMemcpyAsync(&over, flag, 4, hipMemcpyDeviceToHost, s));
+  // (synchronises the stream: the batch inversion's one scalar inverse is the host's)
+  const int rc = invert_impl<Sh, MN2>(k, tot.as<uint32_t>(), nchunks, inv.as<uint32_t>(), s);
+  if (over) return fail(XHE_EINVAL, "xhe_hist_level_sub_sparse: more entries outside the zero bins than nnz_bound");
+  if (rc != XHE_OK) return rc;
+  {
+    ProfScope pb("k_sss_bwd", s);
+    launch((k_sss_bwd<MN2, PW>), blocks(nchunks), dim3(256), s, k->kd, n2h<MN2>(k).N, L, hcnt, nbins, parent, parent_cnt,
+           FB, nchunks, (int)lmax, pre.as<uint32_t>(), inv.as<uint32_t>(), one, sinv.as<uint32_t>(), out, cnt);
+  }
+  ProfScope pz("k_sss_zero", s);
+  launch((k_sss_zero<MN2, PW>), blocks(G), dim3(256), s, k->kd, n2h<MN2>(k).N, L, sinv.as<uint32_t>(), nfeat, nbins,
+         zero_bin, node_cnt, nzsum, parent, parent_cnt, out, cnt);
+  return XHE_OK;
+}
+
 // Bucket multi-exponentiation (bucket_dev.hpp). The columns run in groups
 // whose digit matrix stays within kBucketDigitCap ids (and hist_rows groups
 // the (column, window) features within kChunk rows below that); every group
@@ -2290,6 +2442,40 @@ int xhe_hist_level_sparse_route(const xhe_key* key, int64_t n_rows, int nnodes, 
                                 int have_total) {
   (void)key;  // (one constant serves every key size: DESIGN "Level-wise sparse histogram")
   return paths::level_sparse(n_rows, nnodes, nfeat, nbins, nnz, have_total != 0) ? 1 : 0;
+}
+
+int xhe_hist_level_sub_sparse(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const uint16_t* bins_dev,
+                              int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin_dev,
+                              const uint16_t* node_dev, int nnodes, const uint32_t* parent_dev,
+                              const int32_t* parent_cnt_dev, int64_t nnz_bound, const uint32_t* total_dev,
+                              int tile_rows, uint32_t* out_dev, int32_t* cnt_dev, void* stream) {
+  return guarded([&]() -> int {
+    const char* who = "xhe_hist_level_sub_sparse";
+    if (int rc = hist_level_sub_args(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins, node_dev, nnodes,
+                                     parent_dev, parent_cnt_dev, tile_rows, out_dev, cnt_dev, who))
+      return rc;
+    if (int rc = hist_level_sparse_args(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins, zero_bin_dev, node_dev,
+                                        nnodes, nnz_bound, total_dev, tile_rows, out_dev, who))
+      return rc;
+    DevGuard dg(key->device);
+    return with_shape(key->K, [&](auto sh) -> int {
+      if (n_rows == 0) {  // ones and zero counts, as xhe_hist_level writes them
+        hist_level_impl<decltype(sh)>(key, c_dev, n_rows, n_rows, bins_dev, bins_stride, nfeat, nbins, node_dev, nnodes,
+                                      tile_rows, out_dev, cnt_dev, (hipStream_t)stream, "k_hist_level_sub_sparse");
+        return XHE_OK;
+      }
+      return hist_level_sub_sparse_impl<decltype(sh)>(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins,
+                                                      zero_bin_dev, node_dev, nnodes, parent_dev, parent_cnt_dev,
+                                                      nnz_bound, total_dev, tile_rows, out_dev, cnt_dev,
+                                                      (hipStream_t)stream);
+    });
+  });
+}
+
+int xhe_hist_level_sub_sparse_route(const xhe_key* key, int64_t n_rows, int nnodes, int nfeat, int nbins, int64_t nnz,
+                                    int have_total) {
+  (void)key;  // (one constant serves every key size: DESIGN "Subtraction on the sparse level histogram")
+  return paths::level_sub_sparse(n_rows, nnodes, nfeat, nbins, nnz, have_total != 0) ? 1 : 0;
 }
 
 namespace {
@@ -3474,6 +3660,62 @@ int xhe_hist_level_sub_host(const xhe_key* key, const uint32_t* c, int64_t n_row
     int rc = xhe_hist_level_sub(key, dc.as<uint32_t>(), n_rows, db.as<uint16_t>(), bins_stride, nfeat, nbins,
                                 dn.as<uint16_t>(), nnodes, dp.as<uint32_t>(), cnt ? dpc.as<int32_t>() : nullptr,
                                 tile_rows, dout.as<uint32_t>(), cnt ? dcnt.as<int32_t>() : nullptr, st.s);
+    if (rc != XHE_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
+    if (cnt) HIPCHK(hipMemcpyAsync(cnt, dcnt.p, nn * 4, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    return XHE_OK;
+  });
+}
+
+int xhe_hist_level_sub_sparse_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,
+                                   int64_t bins_stride, int nfeat, int nbins, const uint16_t* zero_bin,
+                                   const uint16_t* node, int nnodes, const uint32_t* parent, const int32_t* parent_cnt,
+                                   const uint32_t* total, int tile_rows, uint32_t* out, int32_t* cnt) {
+  return guarded([&]() -> int {
+    const char* who = "xhe_hist_level_sub_sparse_host";
+    if (int rc = hist_level_sub_args(key, c, n_rows, bins, bins_stride, nfeat, nbins, node, nnodes, parent, parent_cnt,
+                                     tile_rows, out, cnt, who))
+      return rc;
+    if (int rc = hist_level_sparse_args(key, c, n_rows, bins, bins_stride, nfeat, nbins, zero_bin, node, nnodes, 0, total,
+                                        tile_rows, out, who))
+      return rc;
+    // the bound is the exact count here; without a sparse feature the plain subtraction serves
+    int64_t nnz = 0, valid = 0;
+    bool any = false;
+    for (int64_t i = 0; i < n_rows; ++i) valid += node[i] < nnodes;
+    for (int f = 0; f < nfeat; ++f) {
+      const uint16_t z = zero_bin[f];
+      if (z >= nbins) {
+        nnz += valid;
+        continue;
+      }
+      any = true;
+      const uint16_t* fb = bins + (size_t)f * bins_stride;
+      for (int64_t i = 0; i < n_rows; ++i) nnz += node[i] < nnodes && fb[i] != z;
+    }
+    if (!any)
+      return xhe_hist_level_sub_host(key, c, n_rows, bins, bins_stride, nfeat, nbins, node, nnodes, parent, parent_cnt,
+                                     tile_rows, out, cnt);
+    DevGuard dg(key->device);
+    Stream st;
+    const size_t cb = (size_t)n_rows * key->n2w * 4, bb = ((size_t)(nfeat - 1) * bins_stride + n_rows) * 2,
+                 nn = (size_t)nnodes * nfeat * nbins, ob = nn * key->n2w * 4, tb = (size_t)nnodes * key->n2w * 4;
+    DevBuf dc(cb, st.s), db(bb, st.s), dz((size_t)nfeat * 2, st.s), dn((size_t)n_rows * 2, st.s), dp(ob / 2, st.s),
+        dpc(nn * 2, st.s), dt(total ? tb : 0, st.s), dout(ob, st.s), dcnt(nn * 4, st.s);
+    if (n_rows > 0) {
+      HIPCHK(hipMemcpyAsync(dc.p, c, cb, hipMemcpyHostToDevice, st.s));
+      HIPCHK(hipMemcpyAsync(db.p, bins, bb, hipMemcpyHostToDevice, st.s));
+      HIPCHK(hipMemcpyAsync(dn.p, node, (size_t)n_rows * 2, hipMemcpyHostToDevice, st.s));
+    }
+    HIPCHK(hipMemcpyAsync(dz.p, zero_bin, (size_t)nfeat * 2, hipMemcpyHostToDevice, st.s));
+    HIPCHK(hipMemcpyAsync(dp.p, parent, ob / 2, hipMemcpyHostToDevice, st.s));
+    if (cnt) HIPCHK(hipMemcpyAsync(dpc.p, parent_cnt, nn * 2, hipMemcpyHostToDevice, st.s));
+    if (total) HIPCHK(hipMemcpyAsync(dt.p, total, tb, hipMemcpyHostToDevice, st.s));
+    int rc = xhe_hist_level_sub_sparse(key, dc.as<uint32_t>(), n_rows, db.as<uint16_t>(), bins_stride, nfeat, nbins,
+                                       dz.as<uint16_t>(), dn.as<uint16_t>(), nnodes, dp.as<uint32_t>(),
+                                       cnt ? dpc.as<int32_t>() : nullptr, nnz, total ? dt.as<uint32_t>() : nullptr,
+                                       tile_rows, dout.as<uint32_t>(), cnt ? dcnt.as<int32_t>() : nullptr, st.s);
     if (rc != XHE_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
     if (cnt) HIPCHK(hipMemcpyAsync(cnt, dcnt.p, nn * 4, hipMemcpyDeviceToHost, st.s));

@@ -600,6 +600,53 @@ def hist_level_sparse_route(ctx, dev, n_rows, nnodes, nfeat, nbins, nnz, have_to
                                                       int(nnz), int(bool(have_total))))
 
 
+def hist_level_sub_sparse_words(ctx, cw, bins, nbins, nodes, nnodes, zero_bin, parent, parent_cnt, total=None):
+    """hist_level_sparse_words by subtraction as well (xhe_hist_level_sub_sparse_host):
+    parent [nnodes / 2 * nfeat * nbins, n2w] words and parent_cnt int32 counts
+    of the level above; of every pair 2v, 2v + 1 only the smaller child's
+    entries outside the zero bins are multiplied. Raises ZeroDivisionError when
+    an inverted product has no inverse mod n^2."""
+    cw = _u32(cw)
+    bins = np.ascontiguousarray(bins, dtype=np.uint16)
+    nodes = np.ascontiguousarray(nodes, dtype=np.uint16).reshape(-1)
+    n_rows = cw.shape[0]
+    if bins.ndim != 2 or bins.shape[1] != n_rows or nodes.shape[0] != n_rows:
+        raise ValueError("hist_level_sub_sparse: bins must be [nfeat, n_rows] and nodes [n_rows]")
+    nfeat, n2w = bins.shape[0], n2w_of(ctx)
+    zero_bin = np.ascontiguousarray(zero_bin, dtype=np.uint16).reshape(-1)
+    if zero_bin.shape[0] != nfeat:
+        raise ValueError("hist_level_sub_sparse: one zero bin per feature")
+    nout = int(nnodes) * nfeat * int(nbins)
+    parent = _u32(parent).reshape(-1)
+    parent_cnt = np.ascontiguousarray(parent_cnt, dtype=np.int32).reshape(-1)
+    if int(nnodes) % 2 or parent.shape[0] * 2 != nout * n2w or parent_cnt.shape[0] * 2 != nout:
+        raise ValueError("hist_level_sub_sparse: the parent histogram must hold nnodes / 2 * nfeat * nbins rows and "
+                         "counts")
+    if total is not None:
+        total = _u32(total).reshape(-1)
+        if total.shape[0] != int(nnodes) * n2w:
+            raise ValueError("hist_level_sub_sparse: total must be nnodes ciphertext rows")
+    out = np.empty((nout, n2w), dtype=np.uint32)
+    cnt = np.empty(nout, dtype=np.int32)
+    dk = ctx.device_key(ctx.own_device())
+    nat.check(nat.lib().xhe_hist_level_sub_sparse_host(dk.handle, _vp(cw) if n_rows else None, n_rows,
+                                                       _vp(bins) if n_rows else None, n_rows, nfeat, int(nbins),
+                                                       _vp(zero_bin), _vp(nodes) if n_rows else None, int(nnodes),
+                                                       _vp(parent), _vp(parent_cnt),
+                                                       _vp(total) if total is not None else None, 0, _vp(out),
+                                                       _vp(cnt)),
+              "hist_level_sub_sparse")  # (XHE_ENOINV: ZeroDivisionError)
+    return out, cnt
+
+
+def hist_level_sub_sparse_route(ctx, dev, n_rows, nnodes, nfeat, nbins, nnz, have_total):
+    """whether the planner expects xhe_hist_level_sub_sparse to beat both xhe_hist_level_sparse and xhe_hist_level_sub
+    at this shape and density (no device work)"""
+    dk = ctx.device_key(dev)
+    return bool(nat.lib().xhe_hist_level_sub_sparse_route(dk.handle, int(n_rows), int(nnodes), int(nfeat), int(nbins),
+                                                          int(nnz), int(bool(have_total))))
+
+
 def hist_level_sub_route(ctx, dev, n_rows, nnodes, nfeat, nbins):
     """whether the planner expects xhe_hist_level_sub to beat xhe_hist_level at this shape (no device work)"""
     dk = ctx.device_key(dev)

@@ -856,6 +856,43 @@ def hist_level_sparse(dk, c, bins_d, nbins, node_d, nnodes, zero_bin_d, nnz_boun
     return out, cnt
 
 
+def hist_level_sub_sparse(dk, c, bins_d, nbins, node_d, nnodes, zero_bin_d, nnz_bound, parent_d, parent_cnt_d,
+                          total_d=None, tile_rows=0):
+    """hist_level with both savings (xhe_hist_level_sub_sparse): of every pair
+    of slots only the smaller child is built, and of it only the entries
+    outside the zero bins. zero_bin_d, nnz_bound, total_d as hist_level_sparse's,
+    parent_d, parent_cnt_d as hist_level_sub's. Same result as hist_level. The
+    call synchronises the stream once; ZeroDivisionError when an inverted
+    product has no inverse mod n^2."""
+    torch = _torch()
+    dev = dk.device
+    n_rows, nfeat = c.shape[0], bins_d.shape[0]
+    if bins_d.dim() != 2 or bins_d.element_size() != 2 or bins_d.stride(1) != 1:
+        raise ValueError("hist_level_sub_sparse: bins must be a [nfeat, stride] tensor of 16-bit ids, rows contiguous")
+    if node_d.dim() != 1 or node_d.element_size() != 2 or node_d.shape[0] != n_rows or not node_d.is_contiguous():
+        raise ValueError("hist_level_sub_sparse: nodes must be a contiguous [n_rows] tensor of 16-bit ids")
+    if zero_bin_d.dim() != 1 or zero_bin_d.element_size() != 2 or zero_bin_d.shape[0] != nfeat or \
+            not zero_bin_d.is_contiguous():
+        raise ValueError("hist_level_sub_sparse: zero bins must be a contiguous [nfeat] tensor of 16-bit ids")
+    nout = int(nnodes) * nfeat * int(nbins)
+    if nnodes % 2 or parent_d.shape[0] * 2 != nout or parent_cnt_d.shape[0] * 2 != nout or \
+            parent_cnt_d.element_size() != 4:
+        raise ValueError("hist_level_sub_sparse: the parent histogram must hold nnodes / 2 * nfeat * nbins rows and "
+                         "counts")
+    if total_d is not None and (total_d.numel() != int(nnodes) * dk.n2w or total_d.element_size() != 4):
+        raise ValueError("hist_level_sub_sparse: total must be nnodes ciphertext rows")
+    with _On(dev):
+        out = torch.empty((nout, dk.n2w), dtype=torch.int32, device=f"cuda:{dev}")
+        cnt = torch.empty(nout, dtype=torch.int32, device=f"cuda:{dev}")
+        src, par, pcnt = c.contiguous(), parent_d.contiguous(), parent_cnt_d.contiguous()
+        tot = None if total_d is None else total_d.contiguous()
+    nat.check(nat.lib().xhe_hist_level_sub_sparse(dk.handle, _dp(src), n_rows, _dp(bins_d), bins_d.stride(0), nfeat,
+                                                  int(nbins), _dp(zero_bin_d), _dp(node_d), int(nnodes), _dp(par),
+                                                  _dp(pcnt), int(nnz_bound), _dp(tot), int(tile_rows), _dp(out),
+                                                  _dp(cnt), _sp(dev)), "hist_level_sub_sparse")
+    return out, cnt
+
+
 def hist_level_sub(dk, c, bins_d, nbins, node_d, nnodes, parent_d, parent_cnt_d, tile_rows=0):
     """hist_level by subtraction (xhe_hist_level_sub): slots 2v, 2v + 1 are the
     children of slot v of the level above, whose histogram is parent_d (device

@@ -411,9 +411,8 @@ def histograms(arr, bins, nbins: int = None, rows=None, default_bin=None, total=
         return PaillierArray._concat_same_type(parts).reshape((nfeat, nbins)), counts
 
 
-def _level_subtracts(ctx, dev, parent, subtract, n_rows, shape, e0):
-    """whether level_histograms takes the subtraction path on device `dev`"""
-    from .paillier import ops
+def _level_parent_ok(ctx, parent, subtract, shape, e0):
+    """whether `parent` can serve a subtraction for a level of `shape` (the planner aside)"""
     from .paillier.array import PaillierArray
     nnodes, nfeat, nbins = shape
     if parent is None or subtract is False or nnodes % 2:
@@ -424,9 +423,15 @@ def _level_subtracts(ctx, dev, parent, subtract, n_rows, shape, e0):
             np.shape(counts) != pshape:
         return False
     pe = sums.exponents
-    if int(pe.min()) != e0 or int(pe.max()) != e0:
+    return int(pe.min()) == e0 and int(pe.max()) == e0
+
+
+def _level_subtracts(ctx, dev, parent, subtract, n_rows, shape, e0):
+    """whether level_histograms takes the subtraction path on device `dev`"""
+    from .paillier import ops
+    if not _level_parent_ok(ctx, parent, subtract, shape, e0):
         return False
-    return True if subtract else ops.hist_level_sub_route(ctx, dev, n_rows, nnodes, nfeat, nbins)
+    return True if subtract else ops.hist_level_sub_route(ctx, dev, n_rows, *shape)
 
 
 def _total_rows(ctx, total, nnodes, e0, n2w):
@@ -470,8 +475,13 @@ def level_histograms(arr, bins, nodes, nnodes: int = None, nbins: int = None, pa
     per-node products, a PaillierArray of nnodes ciphertexts at the column's
     exponent (the level above has them in any feature's bins), else they are
     computed. sparse=None asks the planner with the entries outside the default
-    bins counted from `bins`. Where the subtraction is taken the call stays on
-    it: the two are not combined. More than 4095 bins keep the dense path.
+    bins counted from `bins`. With a parent that qualifies and a default bin
+    the two savings combine in one call (xhe_hist_level_sub_sparse: only the
+    smaller child's entries outside the default bins are multiplied) when
+    subtract and sparse are both True, or when neither is False and the
+    planner expects that call to beat both others; otherwise the subtraction,
+    where it is taken, runs without the default bins. More than 4095 bins keep
+    the dense path.
     Raises ZeroDivisionError when a product that has to be inverted is no unit
     mod n^2 (never for ciphertexts of this key).
 
@@ -527,6 +537,23 @@ def level_histograms(arr, bins, nodes, nnodes: int = None, nbins: int = None, pa
         n16 = np.where(nd < 0, 0xFFFF, nd).astype(np.uint16)
         exps = np.full(nnodes * nfeat * nbins, e0, dtype=np.int32)
         dev = resident.device_for(ctx, -1, x.size, 4 * n2w)
+        # (the planner takes the combined call for 2 to 64 nodes only: no entry is counted for a level it cannot take)
+        if dev is not None and sparse is not False and nbins <= 4095 and arr.size and default_bin is not None and \
+                ((subtract and sparse) or nnodes <= 64) and _level_parent_ok(ctx, parent, subtract, shape, e0):
+            zb = _zero_bins(default_bin, nfeat, nbins)
+            if zb is not None:  # both savings in one call
+                live = b16[:, n16 != 0xFFFF]
+                nnz = int(((live != zb[:, None]) | (zb[:, None] == 0xFFFF)).sum())
+                if (subtract and sparse) or ops.hist_level_sub_sparse_route(ctx, dev, arr.size, nnodes, nfeat, nbins,
+                                                                            nnz, total is not None):
+                    tw = None if total is None else resident.upload_async(_total_rows(ctx, total, nnodes, e0, n2w), dev)
+                    out, cnt = resident.hist_level_sub_sparse(
+                        ctx.device_key(dev), x._dw(dev), resident.upload(b16.view(np.int16), dev), nbins,
+                        resident.upload(n16.view(np.int16), dev), nnodes, resident.upload_async(zb.view(np.int16), dev),
+                        nnz, parent[0]._dw(dev),
+                        resident.upload(np.ascontiguousarray(parent[1], np.int32).reshape(-1), dev), tw)
+                    counts = resident.download(cnt, np.int32).astype(np.int64).reshape(shape)
+                    return PaillierArray.from_device(ctx, out, exps, shape), counts
         subtracts = dev is not None and _level_subtracts(ctx, dev, parent, subtract, arr.size, shape, e0)
         zb = None
         if sparse is not False and nbins <= 4095 and arr.size and not subtracts:
