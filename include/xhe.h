@@ -11,9 +11,9 @@
  * gives the thread-local message. A key handle is immutable after creation
  * and may be shared between threads; calls on distinct streams are reentrant.
  *
- * Ciphertext operands: the fifteen entry points that read ciphertext words -
- * xhe_decrypt, xhe_mulmod, xhe_powmod, xhe_pack, xhe_invert, xhe_segprod,
- * xhe_segscan, xhe_hist, xhe_hist_level, xhe_hist_level_sub (its rows and its
+ * Ciphertext operands: the sixteen entry points that read ciphertext words -
+ * xhe_decrypt, xhe_mulmod, xhe_powmod, xhe_pack, xhe_invert, xhe_invert_dev,
+ * xhe_segprod, xhe_segscan, xhe_hist, xhe_hist_level, xhe_hist_level_sub (its rows and its
  * parent rows), xhe_hist_sparse (its rows and its total),
  * xhe_hist_level_sparse (its rows and its totals), xhe_hist_level_sub_sparse
  * (its rows, its parent rows and its totals), xhe_multiexp and
@@ -187,6 +187,20 @@ int xhe_pack(const xhe_key* key, const uint32_t* c_dev, int64_t count, int k, in
  * n^2. XHE_ENOINV when some c mod n^2 has no inverse (it shares a factor with
  * n, or is 0), whether c itself lies below n^2 or not. */
 int xhe_invert(const xhe_key* key, const uint32_t* c_dev, int64_t count, uint32_t* out_dev, void* stream);
+/* The same inverses with nothing left on the host: the product tree's root is
+ * inverted by one wavefront on the device (Bernstein-Yang divsteps in batches
+ * of 30, csrc/modinv_dev.hpp), so the call enqueues on `stream` and returns
+ * without synchronising and without any host copy; its workspaces are
+ * released in stream order. c: any values below 2^(32 n2w), taken mod n^2;
+ * out < n^2. status_dev[0] (device memory, required) is written on the stream:
+ * 0 when every c mod n^2 has an inverse, 1 when some has none; out is then
+ * unspecified (every store stays inside its count rows). The return value is
+ * XHE_OK in both cases: the caller reads the status after its own
+ * synchronisation. count == 0 writes status 0 and nothing else. XHE_EINVAL:
+ * a NULL key or status, a negative count, NULL c or out with count > 0.
+ * The root's inversion is timed as "k_modinv" under xhe_profile. */
+int xhe_invert_dev(const xhe_key* key, const uint32_t* c_dev, int64_t count, uint32_t* out_dev, int32_t* status_dev,
+                   void* stream);
 
 /* Homomorphic sum per segment (np.sum / pandas groupby('bin').sum() over
  * ciphertexts, decision_tree_trainer.py:151-160, xgb_actor.py:340-345,447-456):

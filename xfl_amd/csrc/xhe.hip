@@ -38,6 +38,7 @@
 #include "hist_level_sparse_dev.hpp"
 #include "hist_sub_sparse_dev.hpp"
 #include "bucket_dev.hpp"
+#include "modinv_dev.hpp"
 
 using namespace xhe;
 
@@ -209,6 +210,7 @@ struct xhe_key {
   int rand_bits = 0, rand_words = 0;
   uint32_t* d_blob = nullptr;
   uint32_t* d_tab = nullptr;
+  uint32_t* d_n2 = nullptr;  // n2_host on the device (k_modinv's modulus words)
   KeyDev kd{};
   std::vector<uint32_t> n_host;   // n words (for host-side checks)
   std::vector<uint32_t> n2_host;  // n^2 words (host inverse at the batch-inversion root)
@@ -469,6 +471,8 @@ void key_create_impl(xhe_key* k, const BigU& n, const BigU* p, const BigU* q, co
   HIPCHK(hipMalloc(&k->d_blob, im.words.size() * sizeof(uint32_t)));
   HIPCHK(hipMemcpy(k->d_blob, im.words.data(), im.words.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   k->kd = im.bind(k->d_blob);
+  HIPCHK(hipMalloc(&k->d_n2, k->n2_host.size() * sizeof(uint32_t)));
+  HIPCHK(hipMemcpy(k->d_n2, k->n2_host.data(), k->n2_host.size() * sizeof(uint32_t), hipMemcpyHostToDevice));
   if (!k->djn) return;
   if (k->priv) build_private_tables(k, im);
   else build_public_tables(k, im);
@@ -1068,8 +1072,13 @@ void pack_impl(const xhe_key* k, paths::Pow arith, const uint32_t* c, int64_t co
 }
 
 // Batch inversion mod n^2 via a product tree (Montgomery's trick in parallel).
-template <class Sh, class MN2 = typename Sh::MN2>
-int invert_impl(const xhe_key* k, const uint32_t* c, int64_t count, uint32_t* out, hipStream_t s) {
+// root(in, out) enqueues or computes the one scalar inverse of the batch,
+// n2w device words each, and returns XHE_OK or the code the call fails with;
+// rel: how the level-by-level tree's workspaces are released. Nothing here
+// synchronises; what root does is its own.
+template <class Sh, class MN2, class Root>
+int invert_tree(const xhe_key* k, const uint32_t* c, int64_t count, uint32_t* out, hipStream_t s,
+                DevBuf::Release rel, Root&& root) {
   const int S4 = MN2::S4;
   std::vector<int64_t> sizes{count};
   while (sizes.back() > 1) sizes.push_back((sizes.back() + 1) / 2);
@@ -1103,28 +1112,23 @@ int invert_impl(const xhe_key* k, const uint32_t* c, int64_t count, uint32_t* ou
              node(lv, l));
     }
     launch((k_wtree_out<KW, 16>), dim3(1), dim3(1024), s, k->kd, node(lv, nlev - 1), wds);
-    std::vector<uint32_t> root(k->n2w), yinv(k->n2w);
-    HIPCHK(hipMemcpyAsync(root.data(), wds, (size_t)k->n2w * 4, hipMemcpyDeviceToHost, s));
-    HIPCHK(hipStreamSynchronize(s));
-    if (!modinv_words(root.data(), k->n2_host.data(), k->n2w, yinv.data()))
-      return fail(XHE_ENOINV, "invert(a, b) no inverse exists");
-    HIPCHK(hipMemcpyAsync(wds + k->n2w, yinv.data(), (size_t)k->n2w * 4, hipMemcpyHostToDevice, s));
+    if (int rc = root(wds, wds + k->n2w)) return rc;
     launch((k_wtree_in<KW, 16>), dim3(1), dim3(1024), s, k->kd, wds + k->n2w, node(inv, nlev - 1));
     for (int l = nlev - 2; l >= 0; --l) {
       launch((k_wtree_down<KW, 16>), dim3((unsigned)sizes[l]), dim3(1024), s, k->kd, node(inv, l + 1), node(lv, l),
              sizes[l], node(inv, l));
     }
     launch((k_wtree_out<KW, 16>), dim3((unsigned)count), dim3(1024), s, k->kd, inv, out);
-    HIPCHK(hipStreamSynchronize(s));  // yinv is host memory of this frame
     return XHE_OK;
   } else no_path("invert (k_wtree_*)");
   }
-  // (freed synchronously on return; st_ is read by no kernel, kept so that the call allocates as it did)
+  // (with kSync freed synchronously on return; st_ is read by no kernel, kept so that the host-root call
+  // allocates as it did)
   DevBuf st_, scr_, inv_, lv_;
-  lv_ = DevBuf(tot * 4, s);
-  inv_ = DevBuf(tot * 4, s);
-  scr_ = DevBuf((size_t)(4 * (k->n2w + 1) + 2 * k->n2w + 8) * 4, s);
-  st_ = DevBuf(4, s);
+  lv_ = DevBuf(tot * 4, s, rel);
+  inv_ = DevBuf(tot * 4, s, rel);
+  scr_ = DevBuf((size_t)(4 * (k->n2w + 1) + 2 * k->n2w + 8) * 4, s, rel);
+  if (rel == DevBuf::kSync) st_ = DevBuf(4, s);
   uint32_t *lv = lv_.as<uint32_t>(), *inv = inv_.as<uint32_t>(), *scr = scr_.as<uint32_t>();
   auto blocks = [&](int64_t n) { return dim3((unsigned)((n * MN2::TPI + 255) / 256)); };
   launch(k_to_mont_rows<MN2>, blocks(count), dim3(256), s, k->kd, n2h<MN2>(k).N, c, count, lv);
@@ -1136,23 +1140,67 @@ int invert_impl(const xhe_key* k, const uint32_t* c, int64_t count, uint32_t* ou
   uint32_t* y_words = scr + 4 * (k->n2w + 1);
   uint32_t* r_words = y_words + k->n2w;
   launch(k_row_pack<MN2>, dim3(1), dim3(64), s, k->kd, n2h<MN2>(k).N, lv + top, r_words);
-  // The one scalar inverse of the batch (the tree root, (prod c_i) R) is a
-  // sequential extended Euclid: ~1 ms on a host core vs a single GPU lane's
-  // tens of milliseconds. Everything per element stays on the device.
-  std::vector<uint32_t> root(k->n2w), yinv(k->n2w);
-  HIPCHK(hipMemcpyAsync(root.data(), r_words, (size_t)k->n2w * 4, hipMemcpyDeviceToHost, s));
-  HIPCHK(hipStreamSynchronize(s));
-  if (!modinv_words(root.data(), k->n2_host.data(), k->n2w, yinv.data()))
-    return fail(XHE_ENOINV, "invert(a, b) no inverse exists");
-  HIPCHK(hipMemcpyAsync(y_words, yinv.data(), (size_t)k->n2w * 4, hipMemcpyHostToDevice, s));
+  // the one scalar inverse of the batch: of the tree root, (prod c_i) R
+  if (int rc = root(r_words, y_words)) return rc;
   launch(k_inv_to_row<MN2>, dim3(1), dim3(64), s, k->kd, n2h<MN2>(k).N, y_words, inv + top);
   for (size_t l = sizes.size() - 1; l >= 1; --l) {
     launch(k_tree_down<MN2>, blocks(sizes[l - 1]), dim3(256), s, k->kd, n2h<MN2>(k).N, inv + offs[l], sizes[l],
            lv + offs[l - 1], sizes[l - 1], inv + offs[l - 1]);
   }
   launch(k_from_mont_rows<MN2>, blocks(count), dim3(256), s, k->kd, n2h<MN2>(k).N, inv, count, out);
+  return XHE_OK;
+}
+
+// The tree with its root inverted on the host: a sequential extended Euclid
+// (faster than k_modinv at every size measured, DESIGN.md "Batch inversion
+// with the root on the device"). The stream is synchronised for the root
+// to arrive and again on return (yinv is host memory of this frame, and the
+// level-by-level tree's workspaces are freed synchronously).
+template <class Sh, class MN2 = typename Sh::MN2>
+int invert_impl(const xhe_key* k, const uint32_t* c, int64_t count, uint32_t* out, hipStream_t s) {
+  std::vector<uint32_t> root(k->n2w), yinv(k->n2w);
+  const int rc = invert_tree<Sh, MN2>(k, c, count, out, s, DevBuf::kSync, [&](const uint32_t* in, uint32_t* inv) {
+    HIPCHK(hipMemcpyAsync(root.data(), in, (size_t)k->n2w * 4, hipMemcpyDeviceToHost, s));
+    HIPCHK(hipStreamSynchronize(s));
+    if (!modinv_words(root.data(), k->n2_host.data(), k->n2w, yinv.data()))
+      return fail(XHE_ENOINV, "invert(a, b) no inverse exists");
+    HIPCHK(hipMemcpyAsync(inv, yinv.data(), (size_t)k->n2w * 4, hipMemcpyHostToDevice, s));
+    return (int)XHE_OK;
+  });
+  if (rc != XHE_OK) return rc;
   HIPCHK(hipStreamSynchronize(s));
   return XHE_OK;
+}
+
+// k_modinv on `count` rows of n2w words (one wavefront each); raises status[0]
+// and never clears it.
+void modinv_launch(const xhe_key* k, const uint32_t* in, int64_t count, uint32_t* out, int32_t* status,
+                   hipStream_t s) {
+  const int nb = modinv_max_batches(k->n2w);
+  auto go = [&](auto lpl) {
+    launch(k_modinv<decltype(lpl)::value>, dim3((unsigned)count), dim3(64), s, k->d_n2, k->n2w, in, count, out, status,
+           nb);
+  };
+  switch (modinv_lpl(k->n2w)) {
+    case 3: go(std::integral_constant<int, 3>{}); break;  // 2048-bit keys
+    case 4: go(std::integral_constant<int, 4>{}); break;  // 3072
+    case 5: go(std::integral_constant<int, 5>{}); break;  // 4096
+    case 9: go(std::integral_constant<int, 9>{}); break;  // 8192
+    default: no_path("modinv (k_modinv)");
+  }
+}
+
+// The tree with its root inverted by k_modinv: no host copy, no
+// synchronisation, every workspace released in stream order. A batch with a
+// non-unit has a non-unit root: status[0] = 1 and rows of zeros below it.
+template <class Sh, class MN2 = typename Sh::MN2>
+void invert_dev_impl(const xhe_key* k, const uint32_t* c, int64_t count, uint32_t* out, int32_t* status,
+                     hipStream_t s) {
+  (void)invert_tree<Sh, MN2>(k, c, count, out, s, DevBuf::kAsync, [&](const uint32_t* in, uint32_t* inv) {
+    ProfScope ps("k_modinv", s);
+    modinv_launch(k, in, 1, inv, status, s);
+    return (int)XHE_OK;
+  });
 }
 
 // Small host -> device uploads made while enqueuing (the segment plans):
@@ -2924,6 +2972,7 @@ void xhe_key_destroy(xhe_key* key) {
   if (hipGetDevice(&prev) == hipSuccess && prev != key->device) (void)hipSetDevice(key->device);
   if (key->d_blob) (void)hipFree(key->d_blob);
   if (key->d_tab) (void)hipFree(key->d_tab);
+  if (key->d_n2) (void)hipFree(key->d_n2);
   if (prev >= 0 && prev != key->device) (void)hipSetDevice(prev);
   delete key;
 }
@@ -3322,6 +3371,25 @@ int xhe_invert(const xhe_key* key, const uint32_t* c_dev, int64_t count, uint32_
       return row ? invert_impl<Sh, typename Sh::MN2X>(key, c_dev, count, out_dev, hs)
                  : invert_impl<Sh>(key, c_dev, count, out_dev, hs);
     });
+  });
+}
+
+int xhe_invert_dev(const xhe_key* key, const uint32_t* c_dev, int64_t count, uint32_t* out_dev, int32_t* status_dev,
+                   void* stream) {
+  return guarded([&]() -> int {
+    if (!key || !status_dev || count < 0 || (count > 0 && (!c_dev || !out_dev)))
+      return fail(XHE_EINVAL, "xhe_invert_dev: null argument or negative count");
+    DevGuard dg(key->device);
+    hipStream_t hs = (hipStream_t)stream;
+    launch(k_modinv_clear, dim3(1), dim3(64), hs, status_dev);
+    if (count == 0) return XHE_OK;
+    const bool row = paths::n2_shape(count, pins()) == paths::N2Shape::ROW16;
+    with_shape(key->K, [&](auto sh) {
+      using Sh = decltype(sh);
+      if (row) invert_dev_impl<Sh, typename Sh::MN2X>(key, c_dev, count, out_dev, status_dev, hs);
+      else invert_dev_impl<Sh>(key, c_dev, count, out_dev, status_dev, hs);
+    });
+    return XHE_OK;
   });
 }
 

@@ -309,6 +309,27 @@ def raw_mul_dev(dk, d, kabs, neg):
     return out
 
 
+def invert_rows_dev(dk, rows_dev, stream=None):
+    """rows^-1 mod n^2 on device words [count, n2w] (int32) -> (rows, status),
+    both device tensors, enqueued on `stream` (a torch stream; None: the
+    drop-in stream of the key's device) with no synchronisation and no host
+    copy (xhe_invert_dev). status[0] is 0 when every row is a unit mod n^2 and
+    1 otherwise (the rows are then unspecified); the caller reads it after its
+    own synchronisation."""
+    import torch
+
+    from . import resident
+    st = stream if stream is not None else resident.stream(dk.device)
+    with torch.cuda.device(dk.device), torch.cuda.stream(st):
+        src = rows_dev.contiguous()
+        out = torch.empty_like(src)
+        status = torch.empty(1, dtype=torch.int32, device=src.device)
+    nat.check(nat.lib().xhe_invert_dev(dk.handle, ctypes.c_void_p(src.data_ptr()), src.shape[0],
+                                       ctypes.c_void_p(out.data_ptr()), ctypes.c_void_p(status.data_ptr()),
+                                       ctypes.c_void_p(st.cuda_stream)), "invert_dev")
+    return out, status
+
+
 def gap_threshold(ctx):
     """Smallest alignment gap d with 1 << d >= min_value_for_negative: from
     there on _decrease_exponent_to's scalar takes _raw_mul's negative branch,
