@@ -11,9 +11,9 @@
  * gives the thread-local message. A key handle is immutable after creation
  * and may be shared between threads; calls on distinct streams are reentrant.
  *
- * Ciphertext operands: the sixteen entry points that read ciphertext words -
+ * Ciphertext operands: the seventeen entry points that read ciphertext words -
  * xhe_decrypt, xhe_mulmod, xhe_powmod, xhe_pack, xhe_invert, xhe_invert_dev,
- * xhe_segprod, xhe_segscan, xhe_hist, xhe_hist_level, xhe_hist_level_sub (its rows and its
+ * xhe_segprod, xhe_segscan, xhe_hist, xhe_hist_exp, xhe_hist_level, xhe_hist_level_sub (its rows and its
  * parent rows), xhe_hist_sparse (its rows and its total),
  * xhe_hist_level_sparse (its rows and its totals), xhe_hist_level_sub_sparse
  * (its rows, its parent rows and its totals), xhe_multiexp and
@@ -259,6 +259,42 @@ int xhe_segscan(const xhe_key* key, const uint32_t* c_dev, int64_t count, const 
 int xhe_hist(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const uint16_t* bins_dev, int64_t bins_stride,
              int nfeat, int nbins, const int32_t* rows_dev, int64_t count, int tile_rows, uint32_t* out_dev,
              int32_t* cnt_dev, void* stream);
+
+/* xhe_hist for ciphertext rows of mixed exponents (what Paillier.encrypt with
+ * precision=None produces: every float at its own frexp exponent; the
+ * reference's groupby sums align them pair by pair, paillier.py:106-123).
+ * c, bins, bins_stride, nfeat, nbins (1..4096), rows, count, cnt, the layout
+ * of out and the argument checks: as xhe_hist. e[r]: the exponent of
+ * ciphertext row r, indexed by row id like bins; NULL: every row at exponent
+ * 0, and the words are then xhe_hist's. For cell (f, b), with S the call's
+ * elements whose bins[f][r] == b and emin = min e[r] over S:
+ *   out[(f * nbins + b) * n2w ..] = prod_{r in S} c[r]^(2^(e[r] - emin)) mod
+ *     n^2, below n^2 (xhe_segprod's order-free fold: equal to any order of the
+ *     reference's pairwise adds while every gap is below the negative-branch
+ *     threshold);
+ *   eout[f * nbins + b] = emin (eout is required);
+ *   cnt[f * nbins + b] = |S| (cnt may be NULL).
+ * An empty cell gives 1, exponent 0 and count 0; count == 0 writes that to
+ * every cell. A bin id >= nbins drops the row for that feature. dmax: the
+ * caller's bound on max e - min e over the call's elements, trusted as in
+ * xhe_segprod and xhe_mulmod (the kernels clamp every gap to it: a wrong bound
+ * gives wrong products and never a wrong address); it must lie in
+ * [0, bitlen(n) - 2], else XHE_EINVAL - past that the reference takes
+ * _raw_mul's negative branch and its bits depend on the order of the adds, so
+ * such columns stay with xhe_segprod's callers. A cell costs its entries, one
+ * product more per distinct exponent among the entries of a tile, and at most
+ * its own exponent spread in squarings per tile and per fold level - never
+ * rows x gap (csrc/hist_exp_dev.hpp). tile_rows: as xhe_hist (0: paths.hpp
+ * hist_exp_tile); a tile whose ordering would not fit 64 KB of LDS with nbins
+ * is halved until it does, which changes no result. c: any values below
+ * 2^(32 n2w), taken mod n^2. Needs no private key; runs in the batch n^2 shape;
+ * enqueues on `stream` and returns without synchronising, workspaces released
+ * in stream order. out must not overlap c. Timed as "k_hist_exp" under
+ * xhe_profile. */
+int xhe_hist_exp(const xhe_key* key, const uint32_t* c_dev, const int32_t* e_dev, int64_t n_rows,
+                 const uint16_t* bins_dev, int64_t bins_stride, int nfeat, int nbins, const int32_t* rows_dev,
+                 int64_t count, int dmax, int tile_rows, uint32_t* out_dev, int32_t* eout_dev, int32_t* cnt_dev,
+                 void* stream);
 
 /* Level-wise histogram: xhe_hist for every node of a tree level in one call
  * (cal_hist_for_node over all nodes of a level), keyed by (node, feature,
@@ -549,6 +585,10 @@ int xhe_segscan_host(const xhe_key* key, const uint32_t* c, int64_t count, const
 int xhe_hist_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins, int64_t bins_stride,
                   int nfeat, int nbins, const int32_t* rows, int64_t count, int tile_rows, uint32_t* out,
                   int32_t* cnt);
+/* xhe_hist_exp on host buffers (e, eout host memory too); rows validated as in xhe_hist_host. */
+int xhe_hist_exp_host(const xhe_key* key, const uint32_t* c, const int32_t* e, int64_t n_rows, const uint16_t* bins,
+                      int64_t bins_stride, int nfeat, int nbins, const int32_t* rows, int64_t count, int dmax,
+                      int tile_rows, uint32_t* out, int32_t* eout, int32_t* cnt);
 /* xhe_hist_sparse on host buffers (zero_bin and total host memory too); rows validated as in xhe_hist_host; the
  * bound is the exact count, taken here. Without a sparse feature it is xhe_hist_host. */
 int xhe_hist_sparse_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins,

@@ -69,6 +69,11 @@ SIGNATURES = {
                                 ctypes.c_int64, ctypes.c_int, _vp, _vp, _vp]),
     "xhe_hist_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp,
                                      ctypes.c_int64, ctypes.c_int, _vp, _vp]),
+    "xhe_hist_exp": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                    _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, _vp, _vp, _vp]),
+    "xhe_hist_exp_host": (ctypes.c_int, [_vp, _vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int,
+                                         ctypes.c_int, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp, _vp,
+                                         _vp]),
     "xhe_hist_level": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int, _vp,
                                       ctypes.c_int, ctypes.c_int, _vp, _vp, _vp]),
     "xhe_hist_level_host": (ctypes.c_int, [_vp, _vp, ctypes.c_int64, _vp, ctypes.c_int64, ctypes.c_int, ctypes.c_int,

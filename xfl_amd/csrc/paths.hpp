@@ -273,6 +273,36 @@ inline int hist_group(int nfeat, int nbins, int tile_rows, int64_t tiles, int64_
   return (int)(g < 1 ? 1 : g > nfeat ? nfeat : g);
 }
 
+// ------------------------------------- histogram over mixed exponents
+// xhe_hist_exp (hist_exp_dev.hpp): k_hexp_tile orders a tile by (bin, exponent)
+// with a sort in LDS - a 4-byte key and a 2-byte index per element, two words
+// per bin, the work list and the parked rows' exponents (2 bytes per 16
+// elements). The tile is hist_tile's (the same products per block, plus the
+// squarings), halved while that does not fit the 64 KB a launch gets without
+// opting in (less the kernel's few static words): a capacity rule, no tuning.
+// It bites from 1761 bins on (8192 rows), and leaves 4096 rows at 4096 bins.
+// A caller's tile_rows goes through the same halving: the result does not
+// depend on the tile.
+constexpr int64_t kHistExpLdsMax = 65536 - 256;
+
+inline int64_t hist_exp_lds_bytes(int tile_rows, int nbins) {
+  return 6 * (int64_t)tile_rows + 8 * (int64_t)nbins + 4 * (int64_t)(tile_rows / 32) + 2 * (int64_t)(tile_rows / 16);
+}
+
+inline int hist_exp_fit(int tile_rows, int nbins) {
+  while (tile_rows > kHistTileMin && hist_exp_lds_bytes(tile_rows, nbins) > kHistExpLdsMax) tile_rows >>= 1;
+  return tile_rows;
+}
+
+inline int hist_exp_tile(int64_t count, int nfeat, int nbins) {
+  return hist_exp_fit(hist_tile(count, nfeat, nbins), nbins);
+}
+
+// The largest exponent spread xhe_hist_exp serves for an n of n_bits bits:
+// from n_bits - 1 on, 1 << gap reaches min_value_for_negative and the
+// reference's alignment takes _raw_mul's negative branch (xhe_mulmod).
+inline int hist_exp_dmax(int n_bits) { return n_bits - 2; }
+
 // ------------------------------------------- level-wise histogram
 // xhe_hist_level (hist_level_dev.hpp): every node of a tree level from one
 // pass. The rows are ordered by node into tile slots that each lie inside one

@@ -32,6 +32,7 @@
 #include "enc_obf_dev.hpp"
 #include "wire_unpack.hpp"
 #include "hist_dev.hpp"
+#include "hist_exp_dev.hpp"
 #include "hist_level_dev.hpp"
 #include "hist_sub_dev.hpp"
 #include "hist_sparse_dev.hpp"
@@ -1475,6 +1476,71 @@ void hist_impl(const xhe_key* k, const uint32_t* c, const uint16_t* bins, int64_
                 });
 }
 
+// Histogram over rows of mixed exponents (hist_exp_dev.hpp): stage A leaves a
+// Montgomery row, an exponent and a count per (feature, bin, tile); stage B
+// folds a cell's T triples by levels of k_hexp_fold, chunks of reduce_segments'
+// length (at most kRawChunk: a group's selection mask), at least one level -
+// the last one writes the caller's exponents and counts, so nothing is zeroed
+// beforehand - and k_from_mont_rows packs the words. The features run in
+// hist_rows' groups, a group's squaring rows (one per lane group of a block)
+// counted with its bins; every buffer is freed in stream order, nothing waits.
+template <class Sh>
+void hist_exp_impl(const xhe_key* k, const uint32_t* c, const int32_t* e, const uint16_t* bins, int64_t bins_stride,
+                   int nfeat, int nbins, const int32_t* rows_idx, int64_t count, int dmax, int tile_rows,
+                   uint32_t* out, int32_t* eout, int32_t* cnt, hipStream_t s) {
+  using MN2 = typename Sh::MN2;
+  constexpr int S4 = MN2::S4, NGRP = 256 / MN2::TPI;
+  constexpr int64_t kFill = 131072 / MN2::TPI;  // (reduce_segments')
+  auto blocks = [&](int64_t n) { return dim3((unsigned)std::max<int64_t>(1, (n * MN2::TPI + 255) / 256)); };
+  tile_rows = tile_rows ? paths::hist_exp_fit(tile_rows, nbins) : paths::hist_exp_tile(count, nfeat, nbins);
+  const int64_t T = std::max<int64_t>(1, (count + tile_rows - 1) / tile_rows);
+  const int gmax = paths::hist_group(nfeat, nbins + NGRP, tile_rows, T, kChunk);
+  if ((int64_t)gmax * nbins * T > INT32_MAX) throw std::logic_error("xhe_hist_exp: problem too large for one call");
+  const size_t lds = (size_t)paths::hist_exp_lds_bytes(tile_rows, nbins);
+  ProfScope ps("k_hist_exp", s);
+  for (int f0 = 0; f0 < nfeat; f0 += gmax) {
+    const int gf = std::min(gmax, nfeat - f0);
+    const int64_t nseg = (int64_t)gf * nbins;
+    int64_t t_in = T, n_in = nseg * T;
+    DevBuf cnt_in, exp_in, cur;
+    {
+      DevBuf sq, park;
+      cur = DevBuf((size_t)S4 * n_in * 4, s, DevBuf::kAsync);
+      exp_in = DevBuf((size_t)n_in * 4, s, DevBuf::kAsync);
+      cnt_in = DevBuf((size_t)n_in * 4, s, DevBuf::kAsync);
+      park = DevBuf((size_t)gf * T * (tile_rows / kHistParkDiv) * S4 * 4, s, DevBuf::kAsync);
+      sq = DevBuf((size_t)gf * T * NGRP * S4 * 4, s, DevBuf::kAsync);
+      hipLaunchKernelGGL((k_hexp_tile<MN2, Sh::RW2>), dim3((unsigned)(gf * T)), dim3(256), lds, s, k->kd,
+                         n2h<MN2>(k).N, c, e, bins, bins_stride, nbins, rows_idx, count, dmax, tile_rows, f0, gf, T,
+                         cur.as<uint32_t>(), exp_in.as<int32_t>(), cnt_in.as<int32_t>(), park.as<uint32_t>(),
+                         sq.as<uint32_t>());
+      HIPCHK(hipGetLastError());
+    }
+    do {
+      const int64_t C = std::max<int64_t>(4, std::min<int64_t>(kRawChunk, n_in / kFill));
+      const int64_t nch = (t_in + C - 1) / C, n_out = nseg * nch;
+      const bool last = nch == 1;
+      DevBuf cnt_out, exp_out, nxt;
+      nxt = DevBuf((size_t)S4 * n_out * 4, s, DevBuf::kAsync);
+      if (!last) {
+        exp_out = DevBuf((size_t)n_out * 4, s, DevBuf::kAsync);
+        cnt_out = DevBuf((size_t)n_out * 4, s, DevBuf::kAsync);
+      }
+      launch(k_hexp_fold<MN2>, blocks(n_out), dim3(256), s, k->kd, n2h<MN2>(k).N, cur.as<uint32_t>(),
+             exp_in.as<int32_t>(), cnt_in.as<int32_t>(), n_in, t_in, nch, n_out, dmax, nxt.as<uint32_t>(),
+             last ? eout + (size_t)f0 * nbins : exp_out.as<int32_t>(),
+             last ? (cnt ? cnt + (size_t)f0 * nbins : nullptr) : cnt_out.as<int32_t>());
+      cur = std::move(nxt);  // the level's inputs are freed here, in stream order
+      exp_in = std::move(exp_out);
+      cnt_in = std::move(cnt_out);
+      t_in = nch;
+      n_in = n_out;
+    } while (t_in > 1);
+    launch(k_from_mont_rows<MN2>, blocks(nseg), dim3(256), s, k->kd, n2h<MN2>(k).N, cur.as<uint32_t>(), nseg,
+           out + (size_t)f0 * nbins * k->n2w);
+  }
+}
+
 // Level-wise histogram (hist_level_dev.hpp): the row ids ordered by node into
 // tile slots (three small launches), then per feature group stage A over
 // level_tiles_max slots x features and the fold over the nodes' slot ranges,
@@ -2333,6 +2399,35 @@ int xhe_hist(const xhe_key* key, const uint32_t* c_dev, int64_t n_rows, const ui
     with_shape(key->K, [&](auto sh) {
       hist_impl<decltype(sh)>(key, c_dev, bins_dev, bins_stride, nfeat, nbins, rows_dev, count, tile_rows, out_dev,
                               cnt_dev, (hipStream_t)stream);
+    });
+    return XHE_OK;
+  });
+}
+
+namespace {
+int hist_exp_args(const xhe_key* key, const uint32_t* c, int64_t n_rows, const uint16_t* bins, int64_t bins_stride,
+                  int nfeat, int nbins, const int32_t* rows, int64_t count, int dmax, int tile_rows,
+                  const uint32_t* out, const int32_t* eout, const char* who) {
+  if (int rc = hist_args(key, c, n_rows, bins, bins_stride, nfeat, nbins, rows, count, tile_rows, out, who)) return rc;
+  if (!eout) return fail(XHE_EINVAL, std::string(who) + ": the exponent output is required");
+  if (dmax < 0 || dmax > paths::hist_exp_dmax(key->n_bits))
+    return fail(XHE_EINVAL, std::string(who) + ": dmax must be in [0, bitlen(n) - 2]");
+  return XHE_OK;
+}
+}  // namespace
+
+int xhe_hist_exp(const xhe_key* key, const uint32_t* c_dev, const int32_t* e_dev, int64_t n_rows,
+                 const uint16_t* bins_dev, int64_t bins_stride, int nfeat, int nbins, const int32_t* rows_dev,
+                 int64_t count, int dmax, int tile_rows, uint32_t* out_dev, int32_t* eout_dev, int32_t* cnt_dev,
+                 void* stream) {
+  return guarded([&]() -> int {
+    if (int rc = hist_exp_args(key, c_dev, n_rows, bins_dev, bins_stride, nfeat, nbins, rows_dev, count, dmax,
+                               tile_rows, out_dev, eout_dev, "xhe_hist_exp"))
+      return rc;
+    DevGuard dg(key->device);
+    with_shape(key->K, [&](auto sh) {
+      hist_exp_impl<decltype(sh)>(key, c_dev, e_dev, bins_dev, bins_stride, nfeat, nbins, rows_dev, count, dmax,
+                                  tile_rows, out_dev, eout_dev, cnt_dev, (hipStream_t)stream);
     });
     return XHE_OK;
   });
@@ -3575,6 +3670,37 @@ int xhe_hist_host(const xhe_key* key, const uint32_t* c, int64_t n_rows, const u
                       cnt ? dcnt.as<int32_t>() : nullptr, st.s);
     if (rc != XHE_OK) return rc;
     HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
+    if (cnt) HIPCHK(hipMemcpyAsync(cnt, dcnt.p, nb, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipStreamSynchronize(st.s));
+    return XHE_OK;
+  });
+}
+
+int xhe_hist_exp_host(const xhe_key* key, const uint32_t* c, const int32_t* e, int64_t n_rows, const uint16_t* bins,
+                      int64_t bins_stride, int nfeat, int nbins, const int32_t* rows, int64_t count, int dmax,
+                      int tile_rows, uint32_t* out, int32_t* eout, int32_t* cnt) {
+  return guarded([&]() -> int {
+    if (int rc = hist_exp_args(key, c, n_rows, bins, bins_stride, nfeat, nbins, rows, count, dmax, tile_rows, out,
+                               eout, "xhe_hist_exp_host"))
+      return rc;
+    for (int64_t i = 0; rows && i < count; ++i)
+      if (rows[i] < 0 || rows[i] >= n_rows) return fail(XHE_EINVAL, "xhe_hist_exp_host: row id out of range");
+    DevGuard dg(key->device);
+    Stream st;
+    const size_t cb = (size_t)n_rows * key->n2w * 4, bb = ((size_t)(nfeat - 1) * bins_stride + n_rows) * 2,
+                 ob = (size_t)nfeat * nbins * key->n2w * 4, nb = (size_t)nfeat * nbins * 4;
+    DevBuf dc(cb, st.s), de(e ? (size_t)n_rows * 4 : 0, st.s), db(bb, st.s), dr(rows ? (size_t)count * 4 : 0, st.s),
+        dout(ob, st.s), dexp(nb, st.s), dcnt(nb, st.s);
+    if (n_rows > 0) HIPCHK(hipMemcpyAsync(dc.p, c, cb, hipMemcpyHostToDevice, st.s));
+    if (n_rows > 0 && e) HIPCHK(hipMemcpyAsync(de.p, e, (size_t)n_rows * 4, hipMemcpyHostToDevice, st.s));
+    if (n_rows > 0 && bins) HIPCHK(hipMemcpyAsync(db.p, bins, bb, hipMemcpyHostToDevice, st.s));
+    if (rows && count > 0) HIPCHK(hipMemcpyAsync(dr.p, rows, (size_t)count * 4, hipMemcpyHostToDevice, st.s));
+    int rc = xhe_hist_exp(key, dc.as<uint32_t>(), e ? de.as<int32_t>() : nullptr, n_rows, db.as<uint16_t>(),
+                          bins_stride, nfeat, nbins, rows ? dr.as<int32_t>() : nullptr, count, dmax, tile_rows,
+                          dout.as<uint32_t>(), dexp.as<int32_t>(), cnt ? dcnt.as<int32_t>() : nullptr, st.s);
+    if (rc != XHE_OK) return rc;
+    HIPCHK(hipMemcpyAsync(out, dout.p, ob, hipMemcpyDeviceToHost, st.s));
+    HIPCHK(hipMemcpyAsync(eout, dexp.p, nb, hipMemcpyDeviceToHost, st.s));
     if (cnt) HIPCHK(hipMemcpyAsync(cnt, dcnt.p, nb, hipMemcpyDeviceToHost, st.s));
     HIPCHK(hipStreamSynchronize(st.s));
     return XHE_OK;

@@ -514,6 +514,47 @@ def hist_words(ctx, cw, bins, nbins, rows=None):
     return out, cnt
 
 
+def hist_exp_spread_max(ctx):
+    """the largest exponent spread xhe_hist_exp serves: bitlen(n) - 2, below gap_threshold"""
+    return int(ctx.n).bit_length() - 2
+
+
+def hist_exp_words(ctx, cw, exps, bins, nbins, rows=None):
+    """hist_words for rows of mixed exponents, through xhe_hist_exp_host: exps
+    [n_rows] int32, the exponent of every row of cw. Cell (f, b) is the
+    product of its rows r raised to 2^(exps[r] - emin), emin the smallest
+    exponent among them -> ([nfeat * nbins, n2w] uint32, [nfeat * nbins] int32
+    emin, [nfeat * nbins] int32 counts); an empty cell is (1, 0, 0). The
+    spread of the selected rows' exponents must not exceed
+    hist_exp_spread_max (ValueError)."""
+    cw = _u32(cw)
+    bins = np.ascontiguousarray(bins, dtype=np.uint16)
+    if bins.ndim != 2 or bins.shape[1] != cw.shape[0]:
+        raise ValueError("hist_exp: bins must be [nfeat, n_rows]")
+    n_rows, nfeat = cw.shape[0], bins.shape[0]
+    exps = _i32(exps).reshape(-1)
+    if exps.shape[0] != n_rows:
+        raise ValueError("hist_exp: one exponent per row")
+    count = n_rows
+    if rows is not None:
+        rows = _i32(rows).reshape(-1)
+        count = rows.shape[0]
+        if count and (rows.min() < 0 or rows.max() >= n_rows):
+            raise ValueError("hist_exp: row id out of range")
+    used = exps if rows is None else exps[rows]
+    dmax = int(used.max()) - int(used.min()) if count else 0
+    n2w = n2w_of(ctx)
+    out = np.empty((nfeat * nbins, n2w), dtype=np.uint32)
+    eout = np.empty(nfeat * nbins, dtype=np.int32)
+    cnt = np.empty(nfeat * nbins, dtype=np.int32)
+    dk = ctx.device_key(ctx.own_device())
+    nat.check(nat.lib().xhe_hist_exp_host(dk.handle, _vp(cw) if n_rows else None, _vp(exps) if n_rows else None,
+                                          n_rows, _vp(bins) if n_rows else None, n_rows, nfeat, int(nbins),
+                                          _vp(rows) if rows is not None else None, count, dmax, 0, _vp(out),
+                                          _vp(eout), _vp(cnt)), "hist_exp")
+    return out, eout, cnt
+
+
 def hist_sparse_words(ctx, cw, bins, nbins, zero_bin, rows=None, total=None):
     """hist_words through xhe_hist_sparse_host: zero_bin [nfeat] uint16, the bin
     of each feature that is rebuilt from the total instead of multiplied (>=

@@ -767,6 +767,36 @@ def hist(dk, c, bins_d, nbins, rows=None, tile_rows=0):
     return out, cnt
 
 
+def hist_exp(dk, c, exps_d, dmax, bins_d, nbins, rows=None, tile_rows=0):
+    """hist for rows of mixed exponents (xhe_hist_exp): exps_d a device int32
+    tensor [n_rows] of the rows' exponents (None: all 0), dmax the caller's
+    bound on the spread of the selected rows' exponents (trusted; at most
+    bitlen(n) - 2, else ValueError). Cell (f, b) is the product of its rows r
+    raised to 2^(exps[r] - emin) -> (device [nfeat * nbins, n2w] words, device
+    int32 [nfeat * nbins] emin, device int32 [nfeat * nbins] counts); an empty
+    cell is (1, 0, 0). Nothing here waits for the kernels."""
+    torch = _torch()
+    dev = dk.device
+    n_rows, nfeat = c.shape[0], bins_d.shape[0]
+    if bins_d.dim() != 2 or bins_d.element_size() != 2 or bins_d.stride(1) != 1:
+        raise ValueError("hist_exp: bins must be a [nfeat, stride] tensor of 16-bit ids, rows contiguous")
+    if rows is not None and (rows.dim() != 1 or rows.dtype != torch.int32 or not rows.is_contiguous()):
+        raise ValueError("hist_exp: rows must be a contiguous int32 tensor")
+    if exps_d is not None and (exps_d.shape != (n_rows,) or exps_d.dtype != torch.int32 or
+                               not exps_d.is_contiguous()):
+        raise ValueError("hist_exp: exps must be a contiguous int32 tensor, one exponent per row")
+    count = n_rows if rows is None else rows.shape[0]
+    with _On(dev):
+        out = torch.empty((nfeat * nbins, dk.n2w), dtype=torch.int32, device=f"cuda:{dev}")
+        eout = torch.empty(nfeat * nbins, dtype=torch.int32, device=f"cuda:{dev}")
+        cnt = torch.empty(nfeat * nbins, dtype=torch.int32, device=f"cuda:{dev}")
+        src = c.contiguous()
+    nat.check(nat.lib().xhe_hist_exp(dk.handle, _dp(src), _dp(exps_d), n_rows, _dp(bins_d), bins_d.stride(0), nfeat,
+                                     int(nbins), _dp(rows), count, int(dmax), int(tile_rows), _dp(out), _dp(eout),
+                                     _dp(cnt), _sp(dev)), "hist_exp")
+    return out, eout, cnt
+
+
 def hist_sparse(dk, c, bins_d, nbins, zero_bin_d, nnz_bound, rows=None, total_d=None, tile_rows=0):
     """hist by the sparse-aware call (xhe_hist_sparse): zero_bin_d a device
     int16 tensor [nfeat] of uint16 bins (>= nbins: a dense feature) whose rows

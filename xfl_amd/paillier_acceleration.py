@@ -312,7 +312,8 @@ def histograms(arr, bins, nbins: int = None, rows=None, default_bin=None, total=
     node's samples, repeats allowed), default all. Returns (sums, counts):
     sums a PaillierArray of shape (nfeat, nbins) - sums[f][b] what
     groupby(bins[f]).sum() gives for group b, an empty bin the encryption of
-    0 - at the inputs' common exponent and in HBM when the input is; counts an
+    0 - at the inputs' common exponent (mixed exponents: each cell at the
+    smallest of its own) and in HBM when the input is; counts an
     int64 array of the same shape. Needs only the public key.
 
     default_bin: an int, or one per feature - the bin that holds the feature's
@@ -327,10 +328,14 @@ def histograms(arr, bins, nbins: int = None, rows=None, default_bin=None, total=
     a product that has to be inverted is no unit mod n^2 (never for
     ciphertexts of this key).
 
-    The device path serves arrays with one exponent and nbins <= 4096; anything
-    else takes the drop-in's groupby sum feature by feature. Mixed exponents,
-    missing entries and more than 4095 bins keep the dense path whatever
-    default_bin says."""
+    The one-call path serves nbins <= 4096. A column of one exponent goes to
+    xhe_hist (or xhe_hist_sparse). A column of mixed exponents - what
+    Paillier.encrypt gives with precision=None - goes to xhe_hist_exp when it
+    has no missing entries and its selected exponents spread over at most
+    bitlen(n) - 2: every cell then comes back at its own smallest exponent,
+    the ciphertext the groupby sum gives bit for bit. Anything else takes the
+    drop-in's groupby sum feature by feature. Mixed exponents, missing entries
+    and more than 4095 bins keep the dense path whatever default_bin says."""
     from .paillier import PaillierCiphertext, ops, resident
     from .paillier.array import NA_EXP, PaillierArray, _Fallback, _result
     if isinstance(arr, np.ndarray) and arr.dtype == object and arr.ndim == 1 and \
@@ -368,12 +373,24 @@ def histograms(arr, bins, nbins: int = None, rows=None, default_bin=None, total=
     try:
         used = arr.exponents if rows is None else arr.exponents[rows]
         used = used[used != NA_EXP]
-        if nbins > 4096 or (used.size and int(used.min()) != int(used.max())):
+        spread = int(used.max()) - int(used.min()) if used.size else 0
+        if nbins > 4096 or (spread and (arr._has_na() or spread > ops.hist_exp_spread_max(ctx))):
             raise _Fallback()
         e0 = int(used[0]) if used.size else 0
         n2w = ops.n2w_of(ctx)
         x = arr._aligned_words(n2w)
         u16 = np.where(ids < 0, 0xFFFF, ids).astype(np.uint16)
+        if spread:  # mixed exponents: the dense call that aligns them (xhe_hist_exp), whatever default_bin says
+            ev = np.ascontiguousarray(arr.exponents, dtype=np.int32)
+            dev = resident.device_for(ctx, -1, x.size, 4 * n2w)
+            if dev is None:
+                w, eo, cnt = ops.hist_exp_words(ctx, x.words, ev, u16, nbins, rows)
+                return _result(ctx, w, eo, (nfeat, nbins)), cnt.astype(np.int64).reshape(nfeat, nbins)
+            rd = None if rows is None else resident.upload_async(rows.astype(np.int32), dev)
+            out, eo, cnt = resident.hist_exp(ctx.device_key(dev), x._dw(dev), resident.upload_async(ev, dev), spread,
+                                             resident.upload(u16.view(np.int16), dev), nbins, rd)
+            counts = resident.download(cnt, np.int32).astype(np.int64).reshape(nfeat, nbins)
+            return PaillierArray.from_device(ctx, out, resident.download(eo, np.int32), (nfeat, nbins)), counts
         exps = np.full(nfeat * nbins, e0, dtype=np.int32)
         dev = resident.device_for(ctx, -1, x.size, 4 * n2w)
         count = arr.size if rows is None else rows.size
